@@ -10,11 +10,23 @@ update) over one synthetic batch of (B, 20, 1, 224) fp32 windows already residen
 reference's run_train_epoch body (train_ards_detector.py:139-173).  N > 1: one process per GPU,
 each rank owns B windows (weak scaling), one RCCL all-reduce of the flat gradient bucket per step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run sets up, warms up (W steps), times exactly K steps, writes the last step's outputs when
+--dump-outputs DIR is given, and prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step = the milliseconds of one timed step, ...).  --min-seconds S repeats the K-step bracket until S seconds
+of timed work and reports the median bracket.
+
+--full adds everything that takes runs of its own (each can still be dropped with its --no-* switch):
   roofline     -- the dominant kernel family (implicit-GEMM conv on the fp32 MFMA pipe): algorithmic
                   FLOPs of its launches / their HIP-event durations, measured live on the launch stream
+                  (+ kernel_roofline, kernel_time_share, wgrad_tflops; --no-roofline)
+  extra        -- the forward-only step, densenet18, bf16, f32x3p, folds in flight (--no-extra)
   cpu_baseline -- the reference's CPU path (oracle/torch_ref.py, stock ATen ops, all host threads)
-                  timed on a bounded sample of the same workload (N=1, rank 0 only)
+                  timed on a bounded sample of the same workload (N=1, rank 0 only; --no-cpu-baseline)
+  allreduce_ms -- N > 1: the exchange step alone (20 eager all-reduces of the gradient bucket)
+
+--dump-outputs DIR: what the timed step returns and updates in its last step, as DIR/<name>.npy (float32 / float64,
+at most 64 MB in all): loss, logits, params / grads / momentum (the live parameters, the optimizer's order) and
+buffers (BatchNorm running statistics ...).  Inputs and initial weights are seeded, identical from run to run.
 """
 import argparse
 import json
@@ -50,10 +62,16 @@ def parse():
                     help='STRONG scaling: this many windows per step over ALL ranks (G / world per rank, as nn.DataParallel '
                          'scatters a batch; BASELINE configs[3]: 16 or 64 over 4 GPUs) instead of --batch per rank')
     ap.add_argument('--no-graph', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the roofline pass, the extras, the CPU baseline and (N > 1) the all-reduce alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=15.0)
-    ap.add_argument('--min-seconds', type=float, default=1.0, help='repeat the K-step timed bracket until this much timed work')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='repeat the K-step timed bracket until this much timed work and report the median bracket '
+                         '(default 0: one bracket of exactly --steps steps)')
     ap.add_argument('--max-rounds', type=int, default=200)
     ap.add_argument('--no-extra', action='store_true', help='skip the secondary densenet18 measurement')
     ap.add_argument('--storage', default=None, choices=['f32', 'bf16'],
@@ -337,6 +355,39 @@ def rocprof_in_graph_us(entry, dtype, batch):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64e6
+
+
+def dump_outputs(dirname, tr, model):
+    """The last step's results as float32 / float64 .npy files: the loss and logits train_step returns, and what it
+    updates in place (the live parameters, their gradients, the momentum buffer, the module buffers).  Arrays are
+    flattened in the trainer's parameter order; above DUMP_LIMIT_BYTES in all, every array is cut to a fixed stride."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    b = tr.bucket
+    spans = [(off, p.numel()) for p, off in zip(b.params, b.offsets)]
+
+    def flat(t):
+        return torch.cat([t[off:off + n] for off, n in spans]).detach().float().cpu().numpy()
+    out = {'loss': tr.last_loss.detach().float().cpu().numpy(), 'logits': tr.last_logits.detach().float().cpu().numpy(),
+           'params': flat(b.p), 'grads': flat(b.g)}
+    for k, v in sorted(tr.state.items()):
+        if v.numel() == b.p.numel():
+            out['momentum' if k == 'buf' else 'opt_' + k] = flat(v)
+    bufs = [t.detach().reshape(-1).double().cpu() for t in model.buffers()]
+    if bufs:
+        out['buffers'] = torch.cat(bufs).numpy()
+    total = sum(a.nbytes for a in out.values())
+    stride = int(np.ceil(total / DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        if stride > 1:
+            a = a.reshape(-1)[::stride]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    say('outputs of the last timed step -> %s (%s)' % (dirname, ', '.join(sorted(out))))
+
+
 def np_isfinite(v):
     return v == v and abs(v) != float('inf')
 
@@ -463,6 +514,8 @@ def main():
     loss = float(tr.last_loss)
     say('timed region done: %d rounds of %d steps, median %.3f ms/step (min %.3f, max %.3f)' %
         (len(rounds), args.steps, 1e3 * dt / args.steps, 1e3 * srt[0] / args.steps, 1e3 * srt[-1] / args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, model)       # before --full's passes, which step the same parameters
 
     seqs = world * B * NB * args.steps
     value = seqs / dt
@@ -500,7 +553,7 @@ def main():
     }
     if not np_isfinite(loss):
         raise SystemExit('bench: the loss went non-finite (%r) -- the step is broken, no number is reported' % loss)
-    if world > 1:
+    if world > 1 and args.full:
         # the exchange step alone: 20 eager all-reduces of the flat gradient bucket, back to back
         torch.cuda.synchronize()
         barrier()
@@ -541,7 +594,7 @@ def main():
             'alg_tflops': round(step_flops / per_gpu_dt / 1e12, 2), 'peak_tflops_bf16_mfma': PEAK_BF16_MFMA_TFLOPS,
             'frac_compute': round(step_flops / per_gpu_dt / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4), 'binding': 'hbm'}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented EAGER steps: HIP events around every C-ABI launch, on the launch stream
         kt = KernelTimer(lib, torch, act_bytes=2.0 if F_.storage_dtype() == 'bf16' else 4.0)
         names = [n for n in _lib.SIGNATURES if n not in ('da_version', 'da_conv_wgrad_workspace', 'da_stem_wgrad_workspace', 'da_bn_workspace', 'da_debug_set', 'da_bn_chunks', 'da_conv_wgrad_splits', 'da_conv_wgrad_plan', 'da_bn_debug_two_stage', 'da_bn_debug_target_blocks', 'da_abi_sizes', 'da_wino_debug_tail', 'da_wino_debug_pchunk', 'da_wino_debug_tapmod', 'da_stat_records_floats', 'da_head_groups', 'da_stem_bwd_partials', 'da_stem_bwd_workspace', 'da_wino_weights', 'da_wino4_weights',
@@ -661,7 +714,7 @@ def main():
             out['wgrad_tflops'] = round(wg['flops'] / (wg['total_ms'] * 1e-3) / 1e12, 2)
         out['eager_kernel_ms_per_step'] = round(tot / nprof, 3)
 
-    if world == 1 and not args.no_extra and not c5_shape:
+    if world == 1 and args.full and not args.no_extra and not c5_shape:
         # forward-only (run_test_epoch step: no_grad train-mode forward + loss + argmax), same batch, graph replayed
         for _ in range(3):
             tr.test_step(x, t)
@@ -676,7 +729,7 @@ def main():
                                                      'note': 'forward-only test step of %s, B=%d' % (args.backbone, B)}
         say('inference extra done')
 
-    if world == 1 and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape:
+    if world == 1 and args.full and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape:
         # (fp32 only: densenet's 64+32k channel counts have no bf16 kernels)
         # secondary figure: the reference's DEFAULT backbone (defaults.yml:18), same step definition, dropout active
         torch.manual_seed(0)
@@ -727,7 +780,7 @@ def main():
             dn['eager_kernel_ms_per_step'] = round(tot2 / 3, 3)
         say('densenet18 extra done')
 
-    if world == 1 and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape:
+    if world == 1 and args.full and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape:
         # BASELINE configs[2] ("resnet18-1D ... bf16"): same step with bf16 operands in the k3 s1 conv forward / data gradient
         F_.set_conv_dtype('bf16')
         F_.set_storage_dtype('bf16')
@@ -753,7 +806,7 @@ def main():
             F_.set_conv_dtype('f32')
         say('bf16 extra done')
 
-    if world == 1 and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape:
+    if world == 1 and args.full and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape:
         # the same fp32 step with the residual-block convs on the bf16 matrix cores through exact three-term splits
         # (--dtype f32x3p / --conv-dtype f32x3p: fp32 results, opt-in): the headline stays on the native fp32 kernels
         F_.set_conv_dtype('f32x3p')
@@ -783,7 +836,7 @@ def main():
             F_.set_conv_dtype('f32')
         say('f32x3p extra done')
 
-    if world == 1 and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape and not args.no_graph:
+    if world == 1 and args.full and not args.no_extra and args.backbone == 'resnet18' and args.dtype == 'f32' and not c5_shape and not args.no_graph:
         # two k-fold replicas side by side on this GPU (train_ards_detector --folds-in-flight 2): each its own model,
         # optimizer, captured step and stream, replayed round-robin; aggregate rate of the pair
         from deepards_amd.train import concurrent_streams
@@ -851,7 +904,7 @@ def main():
             trr.release_graphs()
         say('five-fold extra done')
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not c5_shape:      # the reference's CPU path cannot run the C5 shape
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not c5_shape:      # the reference's CPU path cannot run the C5 shape
         say('cpu baseline ...')
         out['cpu_baseline'] = cpu_baseline(args.backbone, B, args.cpu_seconds)
         out['speedup_vs_cpu_baseline'] = round(value / out['cpu_baseline']['value'], 1)

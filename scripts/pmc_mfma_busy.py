@@ -13,5 +13,5 @@ for k, c in acc.items():
     out[k] = {'launches': len(c['SQ_BUSY_CYCLES']), 'mfma_busy_frac': round((mf / 1024) / (bz / 32), 4),
               'lds_bank_conflict_frac_of_lds_active': round(sum(c.get('SQ_LDS_BANK_CONFLICT', [0])) / max(1.0, sum(c.get('SQ_LDS_IDX_ACTIVE', [1]))), 4)}
 print(json.dumps({'how': 'rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE '
-                         '-- python3 bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-extra --no-roofline; '
+                         '-- python3 bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-extra --no-roofline --min-seconds 1; '
                          'busy = (MFMA_BUSY / 1024 SIMDs) / (BUSY_CYCLES / 32 SEs), launch-summed', 'kernels': out}, indent=1))

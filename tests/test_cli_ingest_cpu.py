@@ -14,7 +14,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
-REF_PKL = '/root/reference/deepards/tests/test_dataset.pkl'
+REF_PKL = os.path.join(GOLD, 'test_dataset_masked.pkl')     # the reference's fixture pickle, ids / cohort masked
 
 
 # ---- configuration / command line -----------------------------------------------------------------------------------
@@ -89,8 +89,9 @@ def test_ingested_fixture_equals_the_golden_windows_and_keeps_the_patients():
     assert np.array_equal(ds0.windows, ds.windows) and float(ds0.scaling_factors[None][0][0]) == float(mu[0])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PKL), reason='build container only: the reference fixture does not travel')
 def test_reference_fixture_pickle_parses_inertly_to_the_committed_npz(tmp_path):
+    """The reference's tests/test_dataset.pkl with only payloads changed (oracle/make_golden_reference_files.py: patient
+    ids -> same-length tokens, the cohort frame / file list blanked): same opcodes and arrays, parsed inertly."""
     from deepards_amd import ingest
     ds = ingest.read_ards_dataset(REF_PKL)
     gold = ingest.load_npz(os.path.join(GOLD, 'test_dataset.npz'))
@@ -394,29 +395,28 @@ def test_spoofed_own_checkpoint_executes_nothing(tmp_path, where):
     assert not os.path.exists(marker)
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/deepards/models/resnet.py'),
-                    reason='build container only: needs the reference models importable')
 @pytest.mark.parametrize('legacy', [False, True])
 def test_checkpoint_pickled_by_the_real_reference_classes(tmp_path, legacy):
-    """The same with the REAL reference classes (imported from /root/reference, allowed: SURVEY 8c): their whole-module
-    pickle is read inertly and its weights load into this package's model, key for key."""
+    """The same with files pickled by the REAL reference classes (tests/golden/ref_checkpoint_resnet18_*.pth.gz, written
+    by oracle/make_golden_reference_files.py: every tensor a pattern of its key index): their whole-module pickle is read
+    inertly and its weights load into this package's model, key for key."""
+    import gzip
+    import json
     from deepards_amd import checkpoint as C
     import deepards_amd.models as M
-    sys.path.insert(0, '/root/reference')
-    try:
-        from deepards.models.resnet import resnet18
-        from deepards.models.torch_cnn_linear_network import CNNLinearNetwork
-        torch.manual_seed(0)
-        ref = CNNLinearNetwork(resnet18(), 20, 0)
-        path = str(tmp_path / 'r.pth')
-        torch.save(ref, path, _use_new_zipfile_serialization=not legacy)
-    finally:
-        sys.path.remove('/root/reference')
-        for k in [k for k in sys.modules if k == 'deepards' or k.startswith('deepards.')]:
-            del sys.modules[k]
+    path = str(tmp_path / 'r.pth')
+    with gzip.open(os.path.join(GOLD, 'ref_checkpoint_resnet18_%s.pth.gz' % ('legacy' if legacy else 'zip')), 'rb') as f:
+        open(path, 'wb').write(f.read())
+    keys = json.load(open(os.path.join(GOLD, 'ref_checkpoint_resnet18.json')))
+    assert C.checkpoint_kind(path) == 'foreign'
     mine = C.load_model_weights(path, lambda: M.CNNLinearNetwork(M.resnet18(), 20, 0))
-    assert list(mine.state_dict()) == list(ref.state_dict()) and len(mine.state_dict()) == 129
-    assert all(torch.equal(a, b) for a, b in zip(mine.state_dict().values(), ref.state_dict().values()))
+    assert list(mine.state_dict()) == keys and len(keys) == 129
+    for i, (k, v) in enumerate(mine.state_dict().items()):     # the generator's pattern, restated
+        if v.dtype.is_floating_point:
+            want = ((torch.arange(v.numel(), dtype=torch.float64) % 7) * 0.125 + (i + 1) * 0.01).to(v.dtype).view(v.shape)
+        else:
+            want = torch.full_like(v, i)
+        assert torch.equal(v, want), k
 
 
 def test_saved_module_carries_no_trainer_gradient_views(tmp_path):
