@@ -23,16 +23,9 @@ typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 // the convolutions take their tiles (conv_gemm.hip xcd_chunked): the blocks that the hardware places on XCD k (block id
 // mod 8) work on the k-th EIGHTH of the rows, so the activation rows a convolution's XCD left in its 4 MB L2 are read by
 // blocks of the same XCD, and what they write waits in the L2 the next convolution's tiles of those rows run on.
-#ifndef DA_ROW_XCD
-#define DA_ROW_XCD 1
-#endif
 __device__ __forceinline__ int row_xcd_chunk(int id, int total) {
-#if DA_ROW_XCD
   if (total & 7) return id;
   return (id & 7) * (total >> 3) + (id >> 3);
-#else
-  return id;
-#endif
 }
 
 // Activation storage type.  Every RLC activation / activation-gradient tensor that crosses a kernel boundary is either
@@ -498,7 +491,6 @@ int wino4_wgrad_launch(const da_wgrad_job* jobs, int n, hipStream_t stream, Wgra
 bool bf16_wgrad_eligible(const da_wgrad_job& j);
 void bf16_wgrad_plan(int rows, int L, int* splits, int* pchunk);
 int bf16_wgrad_launch(const da_wgrad_job* jobs, int n, int code, hipStream_t stream);   // code 16 (bf16) or 49 (x3 operands)
-void bf16_wgrad_set_pchunk(int pchunk);
 
 // One problem of da_conv_gemm_multi: the arguments of da_conv_gemm (include/deepards_hip.h).
 typedef struct {

@@ -199,10 +199,6 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs a) {
   conv_gemm_body<TM, TN, WGM, WGN>(a, xcd_linear_tile(blockIdx.x, gridDim.x), lds);
 }
 
-// tuning knobs (benchmark use): 0 = automatic
-static int g_force_conv_tile = 0;
-static int g_wgrad_target_blocks = 0;
-
 template <int TM, int TN, int WGM, int WGN>
 static int launch_conv_gemm(const ConvGemmArgs& a, hipStream_t s) {
   constexpr int BM = TM * WGM * 32, BN = TN * WGN * 32;
@@ -458,7 +454,6 @@ __global__ __launch_bounds__(256) void conv_gemm_tailed_kernel(ConvGemmArgs a, i
   else conv_gemm_body<1, 1, 2, 2>(a, xcd_linear_tile(blockIdx.x - nmini_pad, full), lds);
 }
 
-static int g_use_halo = 128;   // smallest channel count that takes the shared-panel kernel (0: never)
 static int g_use_tail = 1;
 
 // launch T = tiles 64x64 tiles, the partly filled last round of 256 as half tiles when that pays (see above)
@@ -541,9 +536,9 @@ static int conv_gemm_dispatch(const ConvGemmArgs& a, hipStream_t s) {
   if ((uint64_t)a.M * (uint64_t)a.divLm.d >= 0xffffffffull) return DA_EINVAL;
   // k3 stride-1 (forward / data gradient): shared-panel kernel (+2 % on C >= 128; its 37 KB of LDS cap a CU at 4
   // blocks, which costs more than it gains on the 2-chunk C = 64 layer).  Needs src and dst on the same flattened axis.
-  if (g_use_halo && a.C >= g_use_halo && a.ntaps == 3 && a.src_stride == 1 && a.dst_stride == 1 && a.dst_off == 0 && a.N % 64 == 0 &&
+  if (a.C >= 128 && a.ntaps == 3 && a.src_stride == 1 && a.dst_stride == 1 && a.dst_off == 0 && a.N % 64 == 0 &&
       a.Lsrc == (int)a.divLm.d && a.Ldst == (int)a.divLm.d && a.so0 >= -1 && a.so0 <= 1 && a.so1 >= -1 && a.so1 <= 1 &&
-      a.so2 >= -1 && a.so2 <= 1 && !g_force_conv_tile) {
+      a.so2 >= -1 && a.so2 <= 1) {
     return launch_conv64<true>(a, s);
   }
   // candidates: id, BM, BN, relative per-block efficiency
@@ -554,7 +549,6 @@ static int conv_gemm_dispatch(const ConvGemmArgs& a, hipStream_t s) {
   double best_score = -1.0;
   for (const Cand& c : cands) {
     if (a.N % c.bn) continue;
-    if (g_force_conv_tile && g_force_conv_tile != c.id) continue;
     long blocks = (long)((a.M + c.bm - 1) / c.bm) * (a.N / c.bn);
     double score = c.eff * balance(blocks);
     if (score > best_score) {
@@ -1159,7 +1153,7 @@ static WgradPlan wgrad_plan(int M, int N, int C, int ntaps, int batch_target = 0
     if (N % tn) continue;
     for (int tc : opts) {
       if (C % tc) continue;
-      int target = g_wgrad_target_blocks > 0 ? g_wgrad_target_blocks : (batch_target > 0 ? batch_target : target0);
+      int target = batch_target > 0 ? batch_target : target0;
       // kernels exist for these pairs only
       bool ok = (tn == 128 && tc == 128) || (tn == 128 && tc == 64) || (tn == 64 && tc == 128) ||
                 (tn == 64 && tc == 64) || (tn == 128 && tc == 32) || (tn == 32 && tc == 128);
@@ -1300,14 +1294,11 @@ static int launch_wgrad_any(const da_wgrad_job* jobs, int n, hipStream_t s, Wgra
 
 extern "C" {
 
-// Benchmark-only tuning knobs.  key 0: force the conv GEMM tile (0 auto, 1 128x128, 2 64x128, 3 128x64,
-// 4 64x64, 5 128x32, 6 32x128).  key 1: wgrad target block count (0 = 1024).  key 7: 0 = the dense-block weight gradients as
-// one launch per tile shape instead of one launch for all shapes (conv_wgrad_any_kernel).
+// Comparison forms the tests flip.  key 3: 0 = no half-tile tail round in the 64x64 conv launches.  key 7: 0 = the
+// dense-block weight gradients as one launch per tile shape instead of one launch for all shapes (conv_wgrad_any_kernel).
+// Any other key: DA_EINVAL.
 int da_debug_set(int key, int value) {
-  if (key == 0) g_force_conv_tile = value;
-  else if (key == 1) g_wgrad_target_blocks = value;
-  else if (key == 2) g_use_halo = value;
-  else if (key == 3) g_use_tail = value;
+  if (key == 3) g_use_tail = value;
   else if (key == 7) g_wgrad_any = value;
   else return DA_EINVAL;
   return DA_OK;

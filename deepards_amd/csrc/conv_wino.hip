@@ -50,7 +50,6 @@ struct WinoArgs {
   const float* in_beta;
   int in_tiles, in_Wu;
   float in_eps;
-  int tapmod;      // timing experiment only (da_wino_debug_tapmod): F(4,3) K-16 kernel reads its taps modulo this many channels
 };
 
 __device__ __forceinline__ uint32_t wino_mix32(uint32_t a, uint32_t b) {      // head_optim.hip mix32
@@ -72,9 +71,6 @@ __device__ __forceinline__ int wino_row(int i) {
   return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9);
 }
 
-#ifndef WINO_SPLIT_GLOAD
-#define WINO_SPLIT_GLOAD 1   // tap loads in the first half of the MFMAs, activation loads in the second (+2..5 %)
-#endif
 #define WINO_PITCH 36
 #define WINO_AROWS 66
 #define WINO_LDS_FLOATS (2 * WINO_AROWS * WINO_PITCH + 4 * 32 * WINO_PITCH)
@@ -211,20 +207,13 @@ __device__ __forceinline__ void conv3_wino_body(const WinoArgs& a, const int til
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int col = (2 * g + half) * 4;
-#if WINO_SPLIT_GLOAD
+      // next chunk's loads: taps in the first half of the MFMAs, activations in the second (+2..5 %)
       __builtin_amdgcn_sched_barrier(0);
       if (ks + 1 < kc) {
         if (half == 0) gload_b(ks + 1);
         else gload_a(ks + 1);
       }
       __builtin_amdgcn_sched_barrier(0);
-#else
-      if (half == 1) {                    // next chunk's loads late in the MFMA sequence (see GLOAD_AT in conv_gemm.hip)
-        __builtin_amdgcn_sched_barrier(0);
-        if (ks + 1 < kc) gload(ks + 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
       if (MINI && half != khalf) continue;
       f32x4 d0 = *reinterpret_cast<const f32x4*>(&Os[(pr - 1) * PITCH + col]);
       const f32x4 d1 = *reinterpret_cast<const f32x4*>(&Es[pr * PITCH + col]);
@@ -664,7 +653,7 @@ __device__ __forceinline__ void conv3_wino4k_body(const WinoArgs& a, const int t
   for (int p = 0; p < 3; ++p) {
     const int idx = p * 64 + lr;
     const int nrow = n_blk + (idx & 31);
-    ub[p] = a.u + (size_t)(idx >> 5) * a.N * a.C + (size_t)(a.tapmod ? nrow % a.tapmod : nrow) * a.C + lq * 4;
+    ub[p] = a.u + (size_t)(idx >> 5) * a.N * a.C + (size_t)nrow * a.C + lq * 4;
   }
 
   f32x4 ra[NA], rb[3];
@@ -810,8 +799,6 @@ __global__ __launch_bounds__(256) void conv3_wino4_kernel(WinoArgs a, int nmini,
 
 static int g_wino_tail = 1;
 static int g_wino4_k16 = 1;
-static int g_wino4_tapmod = 0;   // TIMING EXPERIMENT ONLY (da_wino_debug_tapmod): F(4,3) taps read modulo this many output
-                                 // channels, so that the tap tensor fits one XCD's L2 -- results are then wrong by design
 
 // ---------------------------------------------------------------------------------------------
 // Weight gradient of the same convolution, Winograd form.  With dm = A dy = (dy0, dy0 + dy1, dy0 - dy1, -dy1) per
@@ -974,13 +961,12 @@ bool wino_wgrad_eligible(const da_wgrad_job& j) {
 #ifndef WW_PCHUNK
 #define WW_PCHUNK 640      // (whole fp32 step at B = 64, ms, rows = pairs per split 416 / 512 / 640 / 768 / 1024 with 320 quads: 2.927 / 2.944 / 2.912 / 2.955 / 2.970)
 #endif
-static int g_ww_pchunk = WW_PCHUNK;
 
 // pairs per split: every block of every job carries the same work (20 K steps), slab traffic 48 KB per block.  f = 2: half the
 // pairs per split (the launcher's choice for the jobs of the launch's last, partly filled round -- see wino_wgrad_launch)
 void wino_wgrad_plan(int rows, int L, int* splits, int* pchunk, int f) {
   const int MP = rows * ((L + 1) / 2);
-  const int base = g_ww_pchunk / (f > 1 ? f : 1) >= 32 ? g_ww_pchunk / (f > 1 ? f : 1) : 32;
+  const int base = WW_PCHUNK / (f > 1 ? f : 1) >= 32 ? WW_PCHUNK / (f > 1 ? f : 1) : 32;
   int sp = (MP + base - 1) / base;
   if (sp < 1) sp = 1;
   int pc = ((MP + sp - 1) / sp + 31) / 32 * 32;
@@ -1196,12 +1182,11 @@ __global__ __launch_bounds__(256, WW4_MIN_WAVES) void wino4_wgrad_multi_kernel(W
 #ifndef WW4_QCHUNK
 #define WW4_QCHUNK 320     // (quads per split 192 / 256 / 320 / 384 / 448 with 640 pairs: 2.959 / 2.934 / 2.912 / 2.990 (768 pairs) / 2.987: block counts that fill whole rounds)
 #endif
-static int g_ww4_qchunk = WW4_QCHUNK;
 
 // quads per split (a multiple of the K step)
 void wino4_wgrad_plan(int rows, int L, int* splits, int* qchunk) {
   const int MQ = rows * ((L + 3) / 4);
-  int sp = (MQ + g_ww4_qchunk - 1) / g_ww4_qchunk;
+  int sp = (MQ + WW4_QCHUNK - 1) / WW4_QCHUNK;
   if (sp < 1) sp = 1;
   int qc = ((MQ + sp - 1) / sp + WW4_KQ - 1) / WW4_KQ * WW4_KQ;
   if (qc < WW4_KQ) qc = WW4_KQ;
@@ -1293,7 +1278,6 @@ int da_conv3_winograd4(const float* x, const float* u, float* y, int rows, int L
   a.drop_seed = nullptr; a.drop_salt = 0u; a.drop_p = 0.f;
   a.stat_part = nullptr; a.stat_Wu = 1;
   a.in_pend = nullptr; a.in_mean = a.in_invstd = nullptr; a.in_gamma = a.in_beta = nullptr; a.in_tiles = 0; a.in_Wu = 1; a.in_eps = 0.f;
-  a.tapmod = g_wino4_tapmod;
   a.divPL = make_fastdiv((uint32_t)a.PL);
   if ((uint64_t)a.MP * (uint64_t)a.PL >= 0xffffffffull) return DA_EINVAL;
   const int tiles = ((a.MP + 63) / 64) * (N / 32);
@@ -1345,7 +1329,6 @@ static int conv3_winograd_impl(const float* x, const float* u, float* y, int row
   a.stat_part = stat_part; a.stat_Wu = (stat_part || bn) ? stat_R * a.PL : 1;
   if ((stat_part || bn) && (stat_R < 1 || rows % stat_R || a.stat_Wu < 64 || accumulate)) return DA_EINVAL;
   a.in_pend = nullptr; a.in_mean = a.in_invstd = nullptr; a.in_gamma = a.in_beta = nullptr; a.in_tiles = 0; a.in_Wu = 1; a.in_eps = 0.f;
-  a.tapmod = 0;
   if (bn) {
     if (!bn->pend || !bn->mean || !bn->invstd || !bn->gamma || !bn->beta || C > 128 || ldx != C) return DA_EINVAL;
     a.in_pend = bn->pend; a.in_mean = bn->mean; a.in_invstd = bn->invstd; a.in_gamma = bn->gamma; a.in_beta = bn->beta;
@@ -1409,25 +1392,13 @@ size_t da_stat_records_floats(long units, int N) {
   return tiles * 4 * (size_t)N + tiles * 2;
 }
 
-// tuning / tests: 0 = no half tiles for the last round; pchunk > 0: pairs per weight-gradient split
+// tests: 0 = no half tiles for the last round; 2 / 3: F(4,3) K step 32 / 16
 int da_wino_debug_tail(int on) {
   if (on & ~1) {                 // 2 / 3: F(4,3) K step 32 / 16
     g_wino4_k16 = on & 1;
     return DA_OK;
   }
   g_wino_tail = on;
-  return DA_OK;
-}
-// TIMING EXPERIMENT ONLY: the F(4,3) kernel reads its transformed taps modulo `mod` output channels (0: off) -- the tap
-// tensor then fits one XCD's L2 and the launch shows what its re-reads through the fabric cost; results are wrong by design
-int da_wino_debug_tapmod(int mod) {
-  if (mod < 0 || mod % 32) return DA_EINVAL;
-  g_wino4_tapmod = mod;
-  return DA_OK;
-}
-int da_wino_debug_pchunk(int pchunk) {
-  if (pchunk > 0) g_ww_pchunk = pchunk;
-  if (pchunk < 0) bf16_wgrad_set_pchunk(-pchunk);          // negative: padded positions per split of the bf16 kernels
   return DA_OK;
 }
 

@@ -16,25 +16,19 @@
 // x3 activation format (common.h): per position C/16 groups of [h 16 ch | m 16 ch | l 16 ch] bf16 = 96 bytes per group,
 // 6 C bytes per position: one K step (16 channels) of one panel row is ONE contiguous 96-byte run.
 //
-// Two forms of the same tiles, same MFMA order, bit-identical results: LDS-DMA staging into a 3-slot ring (the default,
-// conv3_x3p_dma_kernel below) and register staging (conv3_x3p_kernel, build with -DXP_DEFAULT_KERNEL=1: the form of round 3's first
-// ablations; kept for A/B).
-//
 // Block = (64 MT) positions x 64 output channels, 4 waves of (32 MT) x 32 (v_mfma_f32_32x32x16_bf16, MT accumulators);
 // MT = 2 for the full tiles, MT = 1 for the tiles of the partly filled last round (see da_conv3_x3p).  K step = 16
 // channels x 3 taps = 18 MT MFMAs per wave.  LDS per K step: the activation panel [64 MT + 2 rows + a zero row][112 B]
 // (96 data + 16 pad: the 16 rows a ds_read_b128 lane group touches fall on 16 different 16-byte slots) and the weight
 // chunk [3 taps][2 n halves][3 terms][64 lanes][16 B] = 18 KB exactly as the repack lays it out in HBM (fragment-major:
-// a wave's B fragment is one conflict-free 1 KB read) -- both double-buffered, ONE barrier per K step; the loads of step
-// k + 2 are in flight while step k multiplies.  Sequence edges: a tap that would cross one reads the zero row.
+// a wave's B fragment is one conflict-free 1 KB read) -- both staged into a ring of three slots (conv3_x3p_dma_body), ONE
+// barrier per K step; the loads of step k + 2 are in flight while step k multiplies.  Sequence edges: a tap that would
+// cross one reads zeros.
 #include "common.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef XP_DEFAULT_KERNEL
-#define XP_DEFAULT_KERNEL 4
-#endif
 #define XP_TN 64
 #define XP_PITCH 112
 #define XP_BCHUNK (18 * 1024)                       // bytes of one (64-channel tile, K step) weight chunk
@@ -70,194 +64,11 @@ struct ConvX3pArgs {
   FastDiv divL;
 };
 
-// One tile of (32 MT WM) positions x 64 output channels by the calling block's NT threads: waves 0 .. 2 WM - 1 compute
-// (wave = (wm, wn): rows wm * 32 MT .., channels wn * 32 ..), every thread of the block stages.
-template <int MT, int WM, int NT>
-__device__ __forceinline__ void conv3_x3p_body(const ConvX3pArgs& a, const int P0, const int n_blk, unsigned char* lds, const bool early) {
-  constexpr int TM = 32 * MT * WM, XROWS = TM + 2, PROWS = XROWS + 1;     // + the zero row
-  constexpr int XBYTES = PROWS * XP_PITCH;
-  constexpr int NXP = (XROWS * 6 + NT - 1) / NT;                     // 16-byte pieces of the panel per thread
-  constexpr int NBP = (1152 + NT - 1) / NT;                          // ... of the 18 KB weight chunk
-  unsigned char* Xs = lds;                          // 2 x [PROWS][112]
-  unsigned char* Bs = lds + 2 * XBYTES;             // 2 x 18 KB
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kch = a.C >> 4;
-  const size_t xrow_bytes = (size_t)a.C * 6;
-
-  // panel loader: piece q of the panel = (row q / 6, 16-byte slot q % 6).  Rows outside [0, M) are read from a clamped
-  // (valid) address: no output that is stored ever uses them (a tap that would reads the zero row).
-  const unsigned char* xsrc[NXP];
-  int xdst[NXP];
-  bool xon[NXP];
-#pragma unroll
-  for (int p = 0; p < NXP; ++p) {
-    const int q = tid + NT * p;
-    xon[p] = q < XROWS * 6;
-    const int r = xon[p] ? q / 6 : 0, s = xon[p] ? q - r * 6 : 0;
-    long P = (long)P0 - 1 + r;
-    P = P < 0 ? 0 : (P >= a.M ? a.M - 1 : P);
-    xsrc[p] = reinterpret_cast<const unsigned char*>(a.x) + (size_t)P * xrow_bytes + s * 16;
-    xdst[p] = r * XP_PITCH + s * 16;
-  }
-  // weight chunk loader: 1152 pieces of 16 bytes, linear
-  const unsigned char* bsrc = reinterpret_cast<const unsigned char*>(a.w) + (size_t)(n_blk >> 6) * kch * XP_BCHUNK + tid * 16;
-  bool bon[NBP];
-#pragma unroll
-  for (int i = 0; i < NBP; ++i) bon[i] = tid + NT * i < 1152;
-
-  f32x4 rx[NXP], rb[NBP];
-  auto gload = [&](int ks) {
-#pragma unroll
-    for (int p = 0; p < NXP; ++p)
-      if (xon[p]) rx[p] = *reinterpret_cast<const f32x4*>(xsrc[p] + ks * 96);
-    const unsigned char* b = bsrc + (size_t)ks * XP_BCHUNK;
-#pragma unroll
-    for (int i = 0; i < NBP; ++i)
-      if (bon[i]) rb[i] = *reinterpret_cast<const f32x4*>(b + i * NT * 16);
-  };
-  auto stage = [&](int buf) {
-    unsigned char* xs = Xs + buf * XBYTES;
-    unsigned char* bs = Bs + buf * XP_BCHUNK + tid * 16;
-#pragma unroll
-    for (int p = 0; p < NXP; ++p)
-      if (xon[p]) *reinterpret_cast<f32x4*>(xs + xdst[p]) = rx[p];
-#pragma unroll
-    for (int i = 0; i < NBP; ++i)
-      if (bon[i]) *reinterpret_cast<f32x4*>(bs + i * NT * 16) = rb[i];
-  };
-
-  const bool computes = wave < 2 * WM;              // (the tail tiles of a 512-thread block: waves 4 .. 7 only stage)
-  const int frow = lane & 31, kg = lane >> 5;
-  const int wm = computes ? wave >> 1 : 0, wn = wave & 1;
-  // LDS offset of the A fragment of (row tile mt, tap t): the panel row of position + t - 1, or the zero row when that
-  // position lies across a sequence edge
-  int aoff[MT][3];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const long P = (long)P0 + (wm * MT + mt) * 32 + frow;
-    const uint32_t Pc = (uint32_t)(P < a.M ? P : 0);
-    const int l = (int)(Pc - fdiv(Pc, a.divL) * (uint32_t)a.L);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const bool edge = (t == 0 && l == 0) || (t == 2 && l == a.L - 1);
-      aoff[mt][t] = (edge ? XROWS : (wm * MT + mt) * 32 + t + frow) * XP_PITCH + kg * 16;
-    }
-  }
-  const int boff = wn * 3 * 1024 + lane * 16;       // + tap * 6 KB + term * 1 KB
-
-  f32x16 acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-
-  if (tid < 14) {                                   // the zero rows of both panel buffers (7 16-byte slots each)
-    const int bsel = tid >= 7, piece = tid - 7 * bsel;
-    *reinterpret_cast<f32x4*>(Xs + bsel * XBYTES + XROWS * XP_PITCH + piece * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  gload(0);
-  stage(0);
-  gload(kch > 1 ? 1 : 0);
-  __syncthreads();
-  for (int ks = 0; ks < kch; ++ks) {
-    const int cur = ks & 1;
-    const unsigned char* xs = Xs + cur * XBYTES;
-    const unsigned char* bs = Bs + cur * XP_BCHUNK + boff;
-    // One K step = 3 taps x MT row tiles = 3 MT groups of 6 MFMAs.  The fragments of group g + 1 are read from LDS BEFORE the
-    // MFMAs of group g issue (register double buffer: an LDS round trip hides behind 192 MFMA cycles instead of stalling
-    // both waves of a SIMD at the same moment), and the staging of step ks + 1 / the loads of step ks + 2 sit between the
-    // first groups instead of in front of them, where the matrix pipe would idle.
-    constexpr int G = 3 * MT;
-    f32x4 av[2][3], bv[2][3];
-    auto ld_frags = [&](int g) {
-      const int t = g / MT, mt = g % MT;
-      if (mt == 0) {
-#pragma unroll
-        for (int s_ = 0; s_ < 3; ++s_) bv[t & 1][s_] = lds_read16(bs + t * 6144 + s_ * 1024);
-      }
-#pragma unroll
-      for (int s_ = 0; s_ < 3; ++s_) av[g & 1][s_] = lds_read16(xs + aoff[mt][t] + s_ * 32);
-    };
-    // The two waves that share a SIMD (waves w and w + 4) must not do the same thing at the same time, or the matrix pipe
-    // idles while both stage and both queue for it afterwards (measured: MFMA, staging and load time simply ADDED UP):
-    // waves 0-3 stage step ks + 1 and load step ks + 2 BEFORE their MFMAs, waves 4-7 AFTER theirs -- within one barrier
-    // interval one half computes while the other moves bytes.
-    if (early) {
-      stage(cur ^ 1);                               // step ks + 1 (already in registers); its buffer was released by the last barrier
-      gload(ks + 2 < kch ? ks + 2 : kch - 1);
-    }
-    if (computes) ld_frags(0);
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      if (computes && g + 1 < G) ld_frags(g + 1);
-      if (computes) {
-        const int mt = g % MT, tb = (g / MT) & 1, sl = g & 1;
-        // the reads of group g are older than everything issued since: the next group's 3 (+ 3 with a new tap's weights)
-        if (g + 1 >= G) lds_wait<0>(av[sl], bv[tb]);
-        else if ((g + 1) % MT == 0) lds_wait<6>(av[sl], bv[tb]);
-        else lds_wait<3>(av[sl], bv[tb]);
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, bv[tb][0]), bm = __builtin_bit_cast(bf16x8, bv[tb][1]),
-                     bl = __builtin_bit_cast(bf16x8, bv[tb][2]);
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, av[sl][0]), am = __builtin_bit_cast(bf16x8, av[sl][1]),
-                     al = __builtin_bit_cast(bf16x8, av[sl][2]);
-        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mt], 0, 0, 0);      // small terms first
-        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mt], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (!early) {
-      stage(cur ^ 1);
-      gload(ks + 2 < kch ? ks + 2 : kch - 1);
-    }
-    __syncthreads();
-  }
-
-  // lane holds output channel n_blk + wn*32 + l%32 of the positions (r & 3) + 8 (r >> 2) + 4 (l / 32) of each 32-row tile
-  if (computes) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const long P = (long)P0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-        if (P < a.M) {
-          float* o = a.y + P * a.ldy + n_blk + wn * 32 + frow;
-          float v = acc[mt][r];
-          if (a.accumulate) v += *o;
-          *o = v;
-        }
-      }
-  }
-}
-
 #define XP_TM 256                                    // full tile: 8 waves = 4 (rows) x 2 (channels), 2 accumulators each
-#define XP_LDS_BYTES (2 * (XP_TM + 3) * XP_PITCH + 2 * XP_BCHUNK)
-
-// Work items: full_m * (N / 64) tiles of 256 x 64 (8 waves; ONE resident block per CU: 95 KB of LDS -- a tile this tall
-// is what brings the operand traffic down to what the L2 -> LDS path sustains: 18.7 bytes per clock and CU against 26.7
-// for 128 x 64 tiles, of ~35 achievable) and, for the partly filled last round of a launch, 64 x 64 tiles (a quarter of
-// the MFMA time on 4 of the block's 8 waves, the others help staging): the FIRST blocks of the launch.
-__global__ __launch_bounds__(512, 1) void conv3_x3p_kernel(ConvX3pArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];       // XP_LDS_BYTES (> 64 KB: dynamic)
-  const int ntn = a.N / XP_TN;
-  const int tail_blocks = 4 * a.tail_m * ntn;
-  if ((int)blockIdx.x < tail_blocks) {
-    const int id = xcd_chunked_xp(blockIdx.x, tail_blocks);        // channel tile fastest: the tiles of one panel share an L2
-    conv3_x3p_body<1, 2, 512>(a, a.full_m * XP_TM + (id / ntn) * 64, (id % ntn) * XP_TN, lds, threadIdx.x < 256);
-  } else {
-    const int tile = xcd_chunked_xp(blockIdx.x - tail_blocks, a.full_m * ntn);
-    conv3_x3p_body<2, 4, 512>(a, (tile / ntn) * XP_TM, (tile % ntn) * XP_TN, lds, threadIdx.x < 256);
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
-// LDS-DMA form (variant 4): the same tiles and the same MFMA order, but the operands go global -> LDS by
-// global_load_lds_dwordx4 (no VGPR round trip, no ds_write) into a ring of THREE slots: the pieces of K step k + 2 are
-// issued while step k multiplies and have a whole step to land (a counted vmcnt in front of the barrier leaves the newest
+// LDS-DMA staging: the operands go global -> LDS by global_load_lds_dwordx4 (no VGPR round trip, no ds_write) into a
+// ring of THREE slots: the pieces of K step k + 2 are issued while step k multiplies and have a whole step to land (a counted vmcnt in front of the barrier leaves the newest
 // ones in flight).  A slot = [activation panel: 258 rows x 7 16-byte granules (6 data + 1 pad), padded to whole 1 KB
 // pieces][512 zero bytes][weight chunk 18 KB]; one wave instruction writes 64 consecutive granules from per-lane sources
 // (the lanes that fall on a pad granule fetch their left neighbour again).  A tap across a sequence edge reads zeros at
@@ -445,6 +256,10 @@ __device__ __forceinline__ void conv3_x3p_dma_body(const ConvX3pArgs& a, const i
   }
 }
 
+// Work items: full_m * (N / 64) tiles of 256 x 64 (8 waves; ONE resident block per CU -- a tile this tall is what brings
+// the operand traffic down to what the L2 -> LDS path sustains: 18.7 bytes per clock and CU against 26.7 for 128 x 64
+// tiles, of ~35 achievable) and, for the partly filled last round of a launch, 64 x 64 tiles (a quarter of the MFMA time
+// on 4 of the block's 8 waves): the FIRST blocks of the launch.
 __global__ __launch_bounds__(512, 1) void conv3_x3p_dma_kernel(ConvX3pArgs a) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];      // XD_LDS_BYTES
   const int ntn = a.N / XP_TN;
@@ -772,37 +587,22 @@ int da_conv3_x3p(const void* x, const void* wpk, float* y, int rows, int L, int 
   a.M = (int)M; a.L = L; a.C = C; a.ldy = ldy; a.N = N; a.accumulate = accumulate;
   a.divL = make_fastdiv((uint32_t)L);
   const int ntn = N / XP_TN;
-  const int g_kernel = XP_DEFAULT_KERNEL;
   const long mtiles = (M + XP_TM - 1) / XP_TM;
   const long tiles = mtiles * ntn;
   if (tiles > 0x3fffffffl) return DA_EINVAL;
   // the partly filled last round (256 resident blocks: 1 per CU) runs as 64 x 64 tiles -- whole M-tile rows of them
-  long tail_m = 0;
-  const int g_tail = 1;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_x3p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            XP_LDS_BYTES) != hipSuccess)
-      return DA_EINVAL;
-    attr_set = true;
-  }
-  if (g_tail) tail_m = tiles < 256 ? mtiles : (tiles % 256) / ntn;
+  const long tail_m = tiles < 256 ? mtiles : (tiles % 256) / ntn;
   a.tail_m = (int)tail_m;
   a.full_m = (int)(mtiles - tail_m);
   const long blocks = (long)a.full_m * ntn + 4l * tail_m * ntn;
-  if (g_kernel == 4) {
-    static bool attr4 = false;
-    if (!attr4) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_x3p_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              XD_LDS_BYTES) != hipSuccess)
-        return DA_EINVAL;
-      attr4 = true;
-    }
-    hipLaunchKernelGGL(conv3_x3p_dma_kernel, dim3((unsigned)blocks), dim3(512), XD_LDS_BYTES, stream, a);
-    DA_CHECK_LAUNCH();
-    return DA_OK;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_x3p_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            XD_LDS_BYTES) != hipSuccess)
+      return DA_EINVAL;
+    attr_set = true;
   }
-  hipLaunchKernelGGL(conv3_x3p_kernel, dim3((unsigned)blocks), dim3(512), XP_LDS_BYTES, stream, a);
+  hipLaunchKernelGGL(conv3_x3p_dma_kernel, dim3((unsigned)blocks), dim3(512), XD_LDS_BYTES, stream, a);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

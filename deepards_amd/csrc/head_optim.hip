@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256) void repack_multi_kernel(RepackTable t) {
   }
 }
 
-// one weight into the CHUNKED split-bf16 pack of conv3_x3p_kernel (conv_x3p.hip): the 18 KB a block stages per (64-channel tile, 16-channel
+// one weight into the CHUNKED split-bf16 pack of conv3_x3p_dma_kernel (conv_x3p.hip): the 18 KB a block stages per (64-channel tile, 16-channel
 // K step) are contiguous and already in LDS order -- element (tap t, n, c), term s at
 //     (((n/64) * (C/16) + c/16) * 18 + (t * 2 + (n%64)/32) * 3 + s) * 512 + ((c%16 / 8) * 32 + n%32) * 8 + c%8
 __device__ __forceinline__ void x3p_pack_put(__bf16* pk, int t, int n, int c, int N, int C, float v) {

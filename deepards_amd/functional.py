@@ -100,7 +100,6 @@ def _launch_wgrads():
 
 
 _WGRAD_CHAIN = True       # (tests switch it off to compare with the one reduction launch behind all weight gradients)
-_WINOGRAD = os.environ.get('DA_WINOGRAD', '1') != '0'   # 0: the direct fp32 kernels (the second fp32 implementation the tests compare)
 _WINO4_MIN_C = 512        # channels from which F(4,3) beats F(2,3) (scripts/bench_wino.py; DESIGN appendix)
 
 
@@ -181,7 +180,7 @@ def _step_pack_code(m):
 
 def _fp32_code(w):
     """The fp32 kernel of a k3 s1 p1 conv whose operand is a float tensor: Winograd F(2,3) / F(4,3) or direct."""
-    if not _WINOGRAD:
+    if not H.WINOGRAD_WGRAD:
         return 0
     return 6 if min(w.shape[0], w.shape[1]) >= _WINO4_MIN_C else 4
 
@@ -744,7 +743,7 @@ def dense_block_ok(rows, R, l, c0, growth, n_layers, mid, tail_out, use_drop):
         return False
     if tail_out and (l % 2 or tail_out % 64 or R * (l // 2) < 64):
         return False
-    if use_drop and not _WINOGRAD:
+    if use_drop and not H.WINOGRAD_WGRAD:
         return False
     return H.dense_fused_ok(rows, R, l, sorted(set([c0 + k * growth for k in range(n_layers + 1)] + [mid, growth])))
 

@@ -572,7 +572,9 @@ def _conv_wgrad_taps(dy, x, src_off, stride):
     return out
 
 
-WINOGRAD_WGRAD = os.environ.get('DA_WINOGRAD', '1') != '0'     # 0: the direct fp32 kernels (as functional._WINOGRAD)
+# DA_WINOGRAD=0: the direct fp32 kernels (the second fp32 implementation the tests compare).  The one switch of every fp32 k3 s1
+# conv path -- forward, data and weight gradients (functional reads it here too) -- under its historical name.
+WINOGRAD_WGRAD = os.environ.get('DA_WINOGRAD', '1') != '0'
 WGRAD_BF16 = False        # set by functional.set_conv_dtype('bf16'): k3 s1 weight gradients on the bf16 matrix cores
 WINO4_WGRAD_MIN_C = 512  # channels from which the F(4,3) weight-gradient form replaces F(2,3) (the 512-channel stage, as the forward)
 

@@ -65,7 +65,8 @@ int da_conv_wgrad(const float* dy, const float* x, float* dw, float* workspace, 
                   int lddy, int N, int Lx, int ldx, int C, int dy_stride, int dy_off, int src_stride, int ntaps,
                   const int* src_off, int accumulate, da_stream_t stream);
 
-/* benchmark-only tuning knobs: key 0 = force conv tile id, key 1 = wgrad target blocks (0 = automatic) */
+/* comparison forms for tests: key 3 = 0: no half-tile tail round in the 64x64 conv launches; key 7 = 0: the dense-block
+   weight gradients as one launch per tile shape.  Any other key returns DA_EINVAL. */
 int da_debug_set(int key, int value);
 
 /* n <= 4 independent da_conv_gemm problems (jobs: HOST array, N % 64 == 0, disjoint outputs) in ONE launch: the
@@ -86,10 +87,6 @@ int da_conv3_winograd(const float* x, const float* u, float* y, int rows, int L,
 /* tuning / tests: 0 = the partly filled last round of tiles is NOT cut into split-K half tiles (1 = default);
    2 / 3 = da_conv3_winograd4 with a K step of 32 / 16 (default) channels */
 int da_wino_debug_tail(int on);
-/* tuning: pchunk > 0 = output pairs per split of the Winograd weight gradient (default 512); pchunk < 0 = -pchunk padded
-   positions per split of the bf16 weight gradient (default 2048) */
-int da_wino_debug_tapmod(int mod);   /* timing experiment only: F(4,3) taps read modulo `mod` output channels (0: off) */
-int da_wino_debug_pchunk(int pchunk);
 /* u[4][co][ci] (transpose = 0, forward) or u[4][ci][co] (transpose = 1, data gradient) from w[co][ci][3] */
 int da_wino_weights(const float* w, float* u, int co, int ci, int transpose, da_stream_t stream);
 /* Winograd F(4,3) variants (half the direct conv's MFMAs): u = 6 * N * C floats. */

@@ -1,5 +1,5 @@
 """Per-layer timing of the pre-split split-bf16 kernels (conv arithmetic 'f32x3p') against the fp32 Winograd kernels at the
-bench batch, hipGraph timed: the k3 s1 conv (conv3_x3p_kernel), the 15 k3 s1 weight gradients in one call
+bench batch, hipGraph timed: the k3 s1 conv (conv3_x3p_dma_kernel), the 15 k3 s1 weight gradients in one call
 (wgrad_x3p_multi_kernel vs wino_wgrad_multi_kernel), and the BatchNorm kernels with float / x3 stores.
 usage: python scripts/bench_x3p.py"""
 import os, sys

@@ -1,4 +1,4 @@
-"""Launches for counter collection: the k3 s1 conv on x3 operands (conv3_x3p_kernel) and the x3 weight gradient at the
+"""Launches for counter collection: the k3 s1 conv on x3 operands (conv3_x3p_dma_kernel) and the x3 weight gradient at the
 bench shapes.  usage (own rocprofv3 run per counter group):
 rocprofv3 --pmc <counters> --kernel-trace --output-format csv -d out -- python3 scripts/pmc_probe_x3p.py"""
 import os, sys

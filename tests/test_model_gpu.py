@@ -1244,10 +1244,10 @@ def test_cli_main_holdout_with_test_pickle_and_foreign_base_network(tmp_path):
 
 # ---- the bench shape (BASELINE configs[1]: B = 64 windows of (20, 1, 224)) --------------------------------------------
 def _set_fast_paths(on):
-    """Toggle every fast path at once: Winograd forward / data / weight gradients, split-K tail tiles, paired stride-2
-    launches, ReLU bit masks -- off = the plain direct kernels."""
-    from deepards_amd import _lib, functional as F_, hip_ops as H_
-    F_._WINOGRAD, F_._PAIR_S2, F_._BN_MASK, H_.WINOGRAD_WGRAD = on, on, on, on
+    """Toggle every fast path at once: Winograd forward / data / weight gradients and split-K tail tiles -- off = the
+    plain direct kernels."""
+    from deepards_amd import _lib, hip_ops as H_
+    H_.WINOGRAD_WGRAD = on
     _lib.lib().da_debug_set(3, 1 if on else 0)
     _lib.lib().da_wino_debug_tail(1 if on else 0)
 
