@@ -120,7 +120,6 @@ SIGNATURES = {
     'da_stat_records_floats': (_Z, [ctypes.c_long, _I]),
     'da_conv3_winograd_bn': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _U, _F, _P, _P]),
     'da_conv_wgrad_splits': (_I, [_I] * 5),
-    'da_conv_wgrad_plan': (_I, [_I] * 6 + [ctypes.POINTER(_I)]),
     'da_conv_gemm_multi': (_I, [ctypes.POINTER(ConvJob), _I, _P]),
     'da_conv3_winograd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'da_conv3_winograd4': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
@@ -137,7 +136,8 @@ SIGNATURES = {
     'da_wino_weights': (_I, [_P, _P, _I, _I, _I, _P]),
     'da_wino4_weights': (_I, [_P, _P, _I, _I, _I, _P]),
     'da_conv_wgrad_multi': (_I, [ctypes.POINTER(WgradJob), _I, _P]),
-    'da_conv_wgrad_multi_reduce': (_I, [ctypes.POINTER(WgradJob), _I, ctypes.POINTER(ctypes.c_void_p), _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _P]),
+    'da_conv_wgrad_multi_reduce': (_I, [ctypes.POINTER(WgradJob), _I, ctypes.POINTER(ctypes.c_void_p), _I, _IP, _P]),
+    'da_conv_wgrad_plan': (_I, [ctypes.POINTER(WgradJob), _I, _I, _IP]),
     'da_wgrad_reduce_multi': (_I, [ctypes.POINTER(WgradReduceDesc), _I, _I, _P]),
     'da_step_tail_multi': (_I, [ctypes.POINTER(WgradReduceDesc), _I, ctypes.POINTER(BnPgradDesc), _I, ctypes.POINTER(BnRunningDesc), _I, _P, _I, _I, _P, _I, _P]),
     'da_stem_bwd_partials': (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_I)]),

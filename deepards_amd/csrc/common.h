@@ -341,7 +341,7 @@ typedef struct {
   int src_off[3];
   int winograd;          // k3 s1 p1, N and C multiples of 64 -- 1: Winograd F(2,3) form (fp32), 6: F(4,3) form (fp32), 16: bf16 operands /
                          // fp32 sums, 49: split-bf16 fp32-equivalent products on x3 operands (both conv_bf16.hip; also
-                         // the stride-2 jobs); the matching da_conv_wgrad_plan(winograd = 1 / 16 / 49) sizes the workspace
+                         // the stride-2 jobs); da_conv_wgrad_plan sizes the workspace
   // dense-block operand forms of stride-1 jobs on the direct kernels (winograd == 0; conv_gemm.hip WgradArgs): xform = 1: X is
   // relu(BatchNorm(x)) recomputed while staged from the statistics tables [rows * Lm / Wn][ldstat]; dy_half = 1: dY has
   // Ldy = Lm / 2 positions per row and position j reads dy[j / 2] / 2 (a transition's pooling in front of its conv)
@@ -480,17 +480,30 @@ static inline WgradPreTable wgrad_chain_take(WgradChain* c) {
   return t;
 }
 
+// What one job of a da_conv_wgrad_multi / da_conv_wgrad_multi_reduce call runs as.  The kernel family is the job's own
+// `winograd` code (0: the direct kernels, with the xform / dy_half operand forms apart); this adds the output tile, the
+// slabs the job writes and its K extent per split.
+struct WgradPlan {
+  int tn, tc;      // output tile (co x ci): the direct kernels have six, every other family 64 x 64; tn == 0: no kernel fits
+  int splits;      // slabs the job writes into its workspace
+  int kchunk;      // per split -- direct: positions, F(2,3): output pairs, F(4,3): quads, bf16 / x3: padded positions
+};
+// The ONE planning pass of a call (conv_gemm.hip; host only, no HIP call, reads no `workspace`): validates every job's shape
+// and fills plan[0 .. n).  chained = 1 is da_conv_wgrad_multi_reduce, 0 da_conv_wgrad_multi -- unchained, a job's plan
+// depends on that job alone.  The launchers below read this array and plan nothing themselves.
+int wgrad_plan_jobs(const da_wgrad_job* jobs, int n, int chained, WgradPlan* plan);
+
 // conv_wino.hip
 bool wino_wgrad_eligible(const da_wgrad_job& j);
-void wino_wgrad_plan(int rows, int L, int* splits, int* pchunk, int f = 1);
-int wino_wgrad_launch(const da_wgrad_job* jobs, int n, hipStream_t stream, WgradChain* chain = nullptr, int* factors = nullptr);
+void wino_wgrad_plan_jobs(const da_wgrad_job* jobs, int n, int chained, WgradPlan* plan);       // the winograd == 1 jobs of a call
+int wino_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hipStream_t stream, WgradChain* chain);
 void wino4_wgrad_plan(int rows, int L, int* splits, int* qchunk);               // winograd == 6: the F(4,3) form (quads)
-int wino4_wgrad_launch(const da_wgrad_job* jobs, int n, hipStream_t stream, WgradChain* chain = nullptr);
+int wino4_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hipStream_t stream, WgradChain* chain);
 
 // conv_bf16.hip: jobs with winograd == 16 (the same eligibility; bf16 operands, padded-position K)
 bool bf16_wgrad_eligible(const da_wgrad_job& j);
 void bf16_wgrad_plan(int rows, int L, int* splits, int* pchunk);
-int bf16_wgrad_launch(const da_wgrad_job* jobs, int n, int code, hipStream_t stream);   // code 16 (bf16) or 49 (x3 operands)
+int bf16_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, int code, hipStream_t stream);   // code 16 (bf16) or 49 (x3 operands)
 
 // One problem of da_conv_gemm_multi: the arguments of da_conv_gemm (include/deepards_hip.h).
 typedef struct {

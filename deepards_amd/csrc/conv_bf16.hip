@@ -904,7 +904,7 @@ void bf16_wgrad_plan(int rows, int L, int* splits, int* pchunk) {
 }
 
 // jobs flagged `code` (16: bf16 operands; 49: fp32-equivalent split-bf16 products on x3 operands, fp32 activations only)
-int bf16_wgrad_launch(const da_wgrad_job* jobs, int n, int code, hipStream_t s) {
+int bf16_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, int code, hipStream_t s) {
   WgradBf16Table t;
   int cnt = 0, blocks = 0;
   auto flush = [&]() -> int {
@@ -922,17 +922,15 @@ int bf16_wgrad_launch(const da_wgrad_job* jobs, int n, int code, hipStream_t s) 
     const da_wgrad_job& j = jobs[i];
     if (j.winograd != code) continue;
     if (code == 49 && g_act_bf16) return DA_EINVAL;      // the split kernels belong to float activations
-    int splits, pchunk;
-    bf16_wgrad_plan(j.rows, j.Lm, &splits, &pchunk);
     WgradBf16Args& a = t.d[cnt];
     a.dy = j.dy; a.x = j.x; a.slab = j.workspace;
     a.rows = j.rows; a.L = j.Lm; a.Kpad = j.rows * (j.Lm + 1);
-    a.lddy = j.lddy; a.N = j.N; a.ldx = j.ldx; a.C = j.C; a.pchunk = pchunk;
+    a.lddy = j.lddy; a.N = j.N; a.ldx = j.ldx; a.C = j.C; a.pchunk = plan[i].kchunk;
     a.divL1 = make_fastdiv((uint32_t)(j.Lm + 1));
     a.mode = j.src_stride == 1 ? 0 : (j.ntaps == 3 ? 1 : 2);
     a.divLx2 = make_fastdiv((uint32_t)(2 * j.Lm + 2));
     t.first_block[cnt] = blocks;
-    blocks += (j.N / 64) * (j.C / 64) * splits;
+    blocks += (j.N / 64) * (j.C / 64) * plan[i].splits;
     if (++cnt == 24) {
       int rc = flush();
       if (rc) return rc;

@@ -1136,11 +1136,7 @@ static int launch_wgrad(const WgradArgs& a, int splits, hipStream_t s) {
 // wgrad plan: output tile (tn x tc) and number of position splits.  Cost model (MI355X measurements):
 // MFMA time at ~120 TF/s scaled by CU balance and a per-tile efficiency, plus the slab round trip
 // (written once, read once by the reduce) at ~4 TB/s.  Small outputs (layer1/2) prefer small tiles and
-// few splits; large outputs (layer3/4) prefer 128x128 tiles.
-struct WgradPlan {
-  int tn, tc, splits, kchunk;
-};
-
+// few splits; large outputs (layer3/4) prefer 128x128 tiles.  (WgradPlan: common.h)
 // batch_target > 0: the job shares its launch with many others (launch_wgrad_any): that many blocks per job instead of a grid
 // that fills the chip by itself
 static WgradPlan wgrad_plan(int M, int N, int C, int ntaps, int batch_target = 0) {
@@ -1182,8 +1178,24 @@ static WgradPlan wgrad_plan(int M, int N, int C, int ntaps, int batch_target = 0
 // C ABI
 // =============================================================================================
 
+static void wgrad_fill_args(WgradArgs& a, const da_wgrad_job& j, const WgradPlan& pl) {
+  a.dy = j.dy; a.x = j.x; a.slab = j.workspace;
+  a.M = j.rows * j.Lm; a.Ldy = j.Ldy; a.lddy = j.lddy; a.N = j.N;
+  a.Lx = j.Lx; a.ldx = j.ldx; a.C = j.C;
+  a.dy_stride = j.dy_stride; a.dy_off = j.dy_off; a.src_stride = j.src_stride;
+  a.ntaps = j.ntaps;
+  a.so0 = j.src_off[0]; a.so1 = j.ntaps > 1 ? j.src_off[1] : 0; a.so2 = j.ntaps > 2 ? j.src_off[2] : 0;
+  a.kchunk = pl.kchunk;
+  a.divLm = make_fastdiv((uint32_t)j.Lm);
+  a.xform = j.xform; a.dy_half = j.dy_half; a.ldstat = j.ldstat;
+  a.kind = 0;
+  a.mean = j.mean; a.invstd = j.invstd; a.gamma = j.gamma; a.beta = j.beta;
+  a.divWn = make_fastdiv((uint32_t)(j.Wn > 0 ? j.Wn : 1));
+}
+
+// the direct jobs of the operand kind XF that are planned on the tn x tc tile
 template <int TM, int TN, int WGM, int WGN, int XF = 0>
-static int launch_wgrad_group(const da_wgrad_job* jobs, int n, int tn, int tc, hipStream_t s, WgradChain* chain = nullptr, int tgt = 0) {
+static int launch_wgrad_group(const da_wgrad_job* jobs, const WgradPlan* plan, int n, int tn, int tc, hipStream_t s, WgradChain* chain) {
   constexpr int BM = TM * WGM * 32, BN = TN * WGN * 32;
   WgradTable t;
   int cnt = 0, blocks = 0;
@@ -1203,25 +1215,13 @@ static int launch_wgrad_group(const da_wgrad_job* jobs, int n, int tn, int tc, h
   for (int i = 0; i < n; ++i) {
     if (jobs[i].winograd) continue;                       // conv_wino.hip
     if ((XF != 0) != (jobs[i].xform != 0 || jobs[i].dy_half != 0)) continue;      // the operand forms have kernels of their own
-    WgradPlan pl = wgrad_plan(jobs[i].rows * jobs[i].Lm, jobs[i].N, jobs[i].C, jobs[i].ntaps, tgt);
-    if (pl.tn == tn && pl.tc == tc) order.push_back({-pl.kchunk, i});
+    if (plan[i].tn == tn && plan[i].tc == tc) order.push_back({-plan[i].kchunk, i});
   }
   std::stable_sort(order.begin(), order.end());
   for (const auto& o : order) {
     const da_wgrad_job& j = jobs[o.second];
-    WgradPlan pl = wgrad_plan(j.rows * j.Lm, j.N, j.C, j.ntaps, tgt);
-    WgradArgs& a = t.d[cnt];
-    a.dy = j.dy; a.x = j.x; a.slab = j.workspace;
-    a.M = j.rows * j.Lm; a.Ldy = j.Ldy; a.lddy = j.lddy; a.N = j.N;
-    a.Lx = j.Lx; a.ldx = j.ldx; a.C = j.C;
-    a.dy_stride = j.dy_stride; a.dy_off = j.dy_off; a.src_stride = j.src_stride;
-    a.ntaps = j.ntaps;
-    a.so0 = j.src_off[0]; a.so1 = j.ntaps > 1 ? j.src_off[1] : 0; a.so2 = j.ntaps > 2 ? j.src_off[2] : 0;
-    a.kchunk = pl.kchunk;
-    a.divLm = make_fastdiv((uint32_t)j.Lm);
-    a.xform = j.xform; a.dy_half = j.dy_half; a.ldstat = j.ldstat;
-    a.mean = j.mean; a.invstd = j.invstd; a.gamma = j.gamma; a.beta = j.beta;
-    a.divWn = make_fastdiv((uint32_t)(j.Wn > 0 ? j.Wn : 1));
+    const WgradPlan& pl = plan[o.second];
+    wgrad_fill_args(t.d[cnt], j, pl);
     t.first_block[cnt] = blocks;
     blocks += (j.N / BM) * (j.C / BN) * j.ntaps * pl.splits;
     wgrad_chain_offer(chain, o.second, j, pl.splits);
@@ -1233,26 +1233,11 @@ static int launch_wgrad_group(const da_wgrad_job* jobs, int n, int tn, int tc, h
   return flush();
 }
 
-static void wgrad_fill_args(WgradArgs& a, const da_wgrad_job& j, const WgradPlan& pl) {
-  a.dy = j.dy; a.x = j.x; a.slab = j.workspace;
-  a.M = j.rows * j.Lm; a.Ldy = j.Ldy; a.lddy = j.lddy; a.N = j.N;
-  a.Lx = j.Lx; a.ldx = j.ldx; a.C = j.C;
-  a.dy_stride = j.dy_stride; a.dy_off = j.dy_off; a.src_stride = j.src_stride;
-  a.ntaps = j.ntaps;
-  a.so0 = j.src_off[0]; a.so1 = j.ntaps > 1 ? j.src_off[1] : 0; a.so2 = j.ntaps > 2 ? j.src_off[2] : 0;
-  a.kchunk = pl.kchunk;
-  a.divLm = make_fastdiv((uint32_t)j.Lm);
-  a.xform = j.xform; a.dy_half = j.dy_half; a.ldstat = j.ldstat;
-  a.kind = 0;
-  a.mean = j.mean; a.invstd = j.invstd; a.gamma = j.gamma; a.beta = j.beta;
-  a.divWn = make_fastdiv((uint32_t)(j.Wn > 0 ? j.Wn : 1));
-}
-
 static int g_wgrad_any = 1;     // da_debug_set(key 7): 0 = one launch per tile shape (the form the tests compare with)
 
 // every direct job of the operand kind XF whose plan is not the 128 x 128 tile, in one launch (conv_wgrad_any_kernel)
 template <int XF>
-static int launch_wgrad_any(const da_wgrad_job* jobs, int n, hipStream_t s, WgradChain* chain, int tgt) {
+static int launch_wgrad_any(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hipStream_t s, WgradChain* chain) {
   WgradAnyTable t;
   int cnt = 0, blocks = 0;
   auto flush = [&]() -> int {
@@ -1271,14 +1256,14 @@ static int launch_wgrad_any(const da_wgrad_job* jobs, int n, hipStream_t s, Wgra
   for (int i = 0; i < n; ++i) {
     if (jobs[i].winograd) continue;
     if ((XF != 0) != (jobs[i].xform != 0 || jobs[i].dy_half != 0)) continue;
-    const WgradPlan pl = wgrad_plan(jobs[i].rows * jobs[i].Lm, jobs[i].N, jobs[i].C, jobs[i].ntaps, tgt);
+    const WgradPlan& pl = plan[i];
     if (pl.tn == 128 && pl.tc == 128) continue;
     order.push_back({-(long)pl.kchunk * (pl.tn * pl.tc / 4096), i});
   }
   std::stable_sort(order.begin(), order.end());
   for (const auto& o : order) {
     const da_wgrad_job& j = jobs[o.second];
-    const WgradPlan pl = wgrad_plan(j.rows * j.Lm, j.N, j.C, j.ntaps, tgt);
+    const WgradPlan& pl = plan[o.second];
     wgrad_fill_args(t.d[cnt], j, pl);
     t.d[cnt].kind = pl.tn == 128 ? (pl.tc == 64 ? 0 : 3) : (pl.tn == 64 ? (pl.tc == 128 ? 1 : 2) : 4);
     t.first_block[cnt] = blocks;
@@ -1290,6 +1275,49 @@ static int launch_wgrad_any(const da_wgrad_job* jobs, int n, hipStream_t s, Wgra
     }
   }
   return flush();
+}
+
+// The planning pass of da_conv_wgrad_multi / da_conv_wgrad_multi_reduce (common.h): everything that decides how many slabs a
+// job writes is here or in the per-family plans it calls.  chained, the dense-block jobs (xform / dy_half) of a call that
+// has 8 or more of them share ONE launch (conv_wgrad_any_kernel) and are planned as a batch: ~2 560 blocks over all of them
+// instead of 512 ... 1 024 per job -- for some shapes more slabs than the job's plan alone, for most fewer.
+// densenet18 at B = 64, per-job target 0 (the plan alone) / 64 / 128 / 192 / 256 / 384 / 512: 1.215 / 1.249 / 1.187 / 1.194 /
+// 1.199 / 1.206 / 1.213 ms a step.
+int wgrad_plan_jobs(const da_wgrad_job* jobs, int n, int chained, WgradPlan* plan) {
+  if (n < 0 || (n && (!jobs || !plan))) return DA_EINVAL;
+  int n_xf = 0;
+  for (int i = 0; i < n; ++i) {
+    const da_wgrad_job& j = jobs[i];
+    if (!j.dy || !j.x || j.ntaps < 1 || j.ntaps > 3 || j.C % 32 || j.N % 32 || j.lddy % 4 || j.ldx % 4 ||
+        (j.winograd == 49 && (j.lddy != j.N || j.ldx != j.C)))
+      return DA_EINVAL;
+    if ((uint64_t)j.rows * j.Lm * (uint64_t)j.Lm >= 0xffffffffull) return DA_EINVAL;
+    if (j.winograd != 0 && j.winograd != 1 && j.winograd != 6 && j.winograd != 16 && j.winograd != 49) return DA_EINVAL;
+    if ((j.xform || j.dy_half) && (j.winograd || j.src_stride != 1 || j.dy_stride != 1 || j.dy_off || j.Lm != j.Lx ||
+                                   (j.dy_half && j.ntaps != 1)))
+      return DA_EINVAL;                                       // the dense-block operand forms: stride-1 jobs on the direct kernels
+    if (j.dy_half && !j.xform) return DA_EINVAL;              // (the half-resolution dY only comes with the recomputed X)
+    if (j.xform && (j.xform != 1 || !j.mean || !j.invstd || !j.gamma || !j.beta || j.Wn < 1 || j.ldstat < j.C || j.ldstat % 4 ||
+                    j.Wn < 32 || (uint64_t)j.rows * j.Lm * (uint64_t)j.Wn >= 0xffffffffull))
+      return DA_EINVAL;
+    if (j.dy_half && (j.Lm & 1 || j.Ldy * 2 != j.Lm)) return DA_EINVAL;
+    if (g_act_bf16 && j.winograd != 16) return DA_EINVAL;     // bf16 activations: only the bf16-operand kernels read them
+    if (j.winograd == 16 || j.winograd == 49 ? !bf16_wgrad_eligible(j) : (j.winograd && !wino_wgrad_eligible(j))) return DA_EINVAL;
+    n_xf += (j.xform || j.dy_half) ? 1 : 0;
+  }
+  const int tgt = (chained && g_wgrad_any && n_xf >= 8) ? (2560 / n_xf < 96 ? 96 : 2560 / n_xf) : 0;
+  for (int i = 0; i < n; ++i) {
+    const da_wgrad_job& j = jobs[i];
+    plan[i].tn = plan[i].tc = 64;
+    if (j.winograd == 16 || j.winograd == 49) bf16_wgrad_plan(j.rows, j.Lm, &plan[i].splits, &plan[i].kchunk);
+    else if (j.winograd == 6) wino4_wgrad_plan(j.rows, j.Lm, &plan[i].splits, &plan[i].kchunk);
+    else if (j.winograd == 0) {
+      plan[i] = wgrad_plan(j.rows * j.Lm, j.N, j.C, j.ntaps, (j.xform || j.dy_half) ? tgt : 0);
+      if (!plan[i].tn) return DA_EINVAL;
+    }
+  }
+  wino_wgrad_plan_jobs(jobs, n, chained, plan);
+  return DA_OK;
 }
 
 extern "C" {
@@ -1407,41 +1435,20 @@ size_t da_conv_wgrad_workspace(int rows, int Lm, int N, int C, int ntaps) {
 }
 
 // Slabs of n weight gradients (jobs: HOST array) with one launch per tile shape; reduce them afterwards with
-// da_wgrad_reduce_multi (da_conv_wgrad_splits() slabs per job).
+// da_wgrad_reduce_multi.  Job i writes the da_conv_wgrad_plan(jobs, n, chained) figure of slabs into its workspace: the call
+// plans once (wgrad_plan_jobs) and every launcher reads that plan.
 // dws != NULL: dws[i] is job i's gradient destination (or NULL); the slab reduction dws[i] (+)= sum of job i's slabs then rides
 // in front of the NEXT launch of this call (common.h WgradPreTable) where there is one, and reduced[i] says whether it did
 // (1) or the caller still owes it (0: da_wgrad_reduce_multi / da_step_tail_multi) -- the jobs of the call's last launch always.
-// splits_out != NULL: the number of slabs every job wrote (what its reduction must be told) -- with it the dense-block jobs
-// of a call that has 8 or more of them are planned as a batch (one launch, conv_wgrad_any_kernel: ~2 560 blocks over all of
-// them instead of 512 ... 1 024 per job; never more slabs than da_conv_wgrad_plan's figure, which sizes the workspace).
-// densenet18 at B = 64, per-job target 0 (the plan alone) / 64 / 128 / 192 / 256 / 384 / 512: 1.215 / 1.249 / 1.187 / 1.194 /
-// 1.199 / 1.206 / 1.213 ms a step.
-static int conv_wgrad_multi_impl(const da_wgrad_job* jobs, int n, float* const* dws, int accumulate, int* reduced,
-                                 int* splits_out, hipStream_t stream) {
+static int conv_wgrad_multi_impl(const da_wgrad_job* jobs, int n, int chained, float* const* dws, int accumulate, int* reduced,
+                                 hipStream_t stream) {
   DA_ENTER();
-  if (n < 0 || (n && !jobs)) return DA_EINVAL;
-  for (int i = 0; i < n; ++i) {
-    const da_wgrad_job& j = jobs[i];
-    if (!j.dy || !j.x || !j.workspace || j.ntaps < 1 || j.ntaps > 3 || j.C % 32 || j.N % 32 || j.lddy % 4 || j.ldx % 4 ||
-        (j.winograd == 49 && (j.lddy != j.N || j.ldx != j.C)))
-      return DA_EINVAL;
-    if ((uint64_t)j.rows * j.Lm * (uint64_t)j.Lm >= 0xffffffffull) return DA_EINVAL;
-    if (j.winograd != 0 && j.winograd != 1 && j.winograd != 6 && j.winograd != 16 && j.winograd != 49) return DA_EINVAL;
-    if ((j.xform || j.dy_half) && (j.winograd || j.src_stride != 1 || j.dy_stride != 1 || j.dy_off || j.Lm != j.Lx ||
-                                   (j.dy_half && j.ntaps != 1)))
-      return DA_EINVAL;                                       // the dense-block operand forms: stride-1 jobs on the direct kernels
-    if (j.dy_half && !j.xform) return DA_EINVAL;              // (the half-resolution dY only comes with the recomputed X)
-    if (j.xform && (j.xform != 1 || !j.mean || !j.invstd || !j.gamma || !j.beta || j.Wn < 1 || j.ldstat < j.C || j.ldstat % 4 ||
-                    j.Wn < 32 || (uint64_t)j.rows * j.Lm * (uint64_t)j.Wn >= 0xffffffffull))
-      return DA_EINVAL;
-    if (j.dy_half && (j.Lm & 1 || j.Ldy * 2 != j.Lm)) return DA_EINVAL;
-    if (g_act_bf16 && j.winograd != 16) return DA_EINVAL;     // bf16 activations: only the bf16-operand kernels read them
-    if (j.winograd == 16 || j.winograd == 49
-            ? !bf16_wgrad_eligible(j)
-            : (j.winograd ? !wino_wgrad_eligible(j) : !wgrad_plan(j.rows * j.Lm, j.N, j.C, j.ntaps).tn))
-      return DA_EINVAL;
-  }
-  int rc;
+  std::vector<WgradPlan> plan_(n > 0 ? n : 0);
+  WgradPlan* const plan = plan_.data();
+  int rc = wgrad_plan_jobs(jobs, n, chained, plan);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!jobs[i].workspace) return DA_EINVAL;
   WgradChain chain_, *chain = nullptr;
   if (dws) {
     if (!reduced) return DA_EINVAL;
@@ -1449,73 +1456,48 @@ static int conv_wgrad_multi_impl(const da_wgrad_job* jobs, int n, float* const* 
     wgrad_chain_init(&chain_, dws, accumulate, reduced);
     chain = &chain_;
   }
-  if ((rc = wino4_wgrad_launch(jobs, n, stream, chain))) return rc;  // the heaviest blocks first
-  std::vector<int> wino_f(n > 0 ? n : 1, 1);
-  if ((rc = wino_wgrad_launch(jobs, n, stream, chain, splits_out ? wino_f.data() : nullptr))) return rc;
-  if ((rc = bf16_wgrad_launch(jobs, n, 49, stream))) return rc;      // x3 operands (dy / x are x3 tensors; ld* = channel counts)
-  if ((rc = bf16_wgrad_launch(jobs, n, 16, stream))) return rc;
-  if ((rc = launch_wgrad_group<2, 2, 2, 2>(jobs, n, 128, 128, stream, chain))) return rc;
-  if ((rc = launch_wgrad_group<2, 1, 2, 2>(jobs, n, 128, 64, stream, chain))) return rc;
-  if ((rc = launch_wgrad_group<1, 2, 2, 2>(jobs, n, 64, 128, stream, chain))) return rc;
-  if ((rc = launch_wgrad_group<1, 1, 2, 2>(jobs, n, 64, 64, stream, chain))) return rc;
-  if ((rc = launch_wgrad_group<1, 1, 4, 1>(jobs, n, 128, 32, stream, chain))) return rc;
-  if ((rc = launch_wgrad_group<1, 1, 1, 4>(jobs, n, 32, 128, stream, chain))) return rc;
-  int n_xf = 0;
-  for (int i = 0; i < n; ++i) n_xf += (jobs[i].xform || jobs[i].dy_half) ? 1 : 0;
-  const int tgt = (splits_out && g_wgrad_any && n_xf >= 8) ? (2560 / n_xf < 96 ? 96 : 2560 / n_xf) : 0;
-  if (splits_out)
-    for (int i = 0; i < n; ++i) {
-      const da_wgrad_job& j = jobs[i];
-      int sp = 0, kc = 0;
-      if (j.winograd == 16 || j.winograd == 49) bf16_wgrad_plan(j.rows, j.Lm, &sp, &kc);
-      else if (j.winograd == 6) wino4_wgrad_plan(j.rows, j.Lm, &sp, &kc);
-      else if (j.winograd) wino_wgrad_plan(j.rows, j.Lm, &sp, &kc, wino_f[i]);
-      else sp = wgrad_plan(j.rows * j.Lm, j.N, j.C, j.ntaps, (j.xform || j.dy_half) ? tgt : 0).splits;
-      splits_out[i] = sp;
-    }
-  if (n_xf) {                                             // dense-block operand forms (conv1x1_bn_kernel's weight gradients)
-    if ((rc = launch_wgrad_group<2, 2, 2, 2, 1>(jobs, n, 128, 128, stream, chain, tgt))) return rc;
-    if (g_wgrad_any) return launch_wgrad_any<1>(jobs, n, stream, chain, tgt);
-    if ((rc = launch_wgrad_group<2, 1, 2, 2, 1>(jobs, n, 128, 64, stream, chain))) return rc;
-    if ((rc = launch_wgrad_group<1, 2, 2, 2, 1>(jobs, n, 64, 128, stream, chain))) return rc;
-    if ((rc = launch_wgrad_group<1, 1, 2, 2, 1>(jobs, n, 64, 64, stream, chain))) return rc;
-    if ((rc = launch_wgrad_group<1, 1, 4, 1, 1>(jobs, n, 128, 32, stream, chain))) return rc;
-    if ((rc = launch_wgrad_group<1, 1, 1, 4, 1>(jobs, n, 32, 128, stream, chain))) return rc;
-  }
-  return DA_OK;
+  if ((rc = wino4_wgrad_launch(jobs, plan, n, stream, chain))) return rc;  // the heaviest blocks first
+  if ((rc = wino_wgrad_launch(jobs, plan, n, stream, chain))) return rc;
+  if ((rc = bf16_wgrad_launch(jobs, plan, n, 49, stream))) return rc;      // x3 operands (dy / x are x3 tensors; ld* = channel counts)
+  if ((rc = bf16_wgrad_launch(jobs, plan, n, 16, stream))) return rc;
+  if ((rc = launch_wgrad_group<2, 2, 2, 2>(jobs, plan, n, 128, 128, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<2, 1, 2, 2>(jobs, plan, n, 128, 64, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 2, 2, 2>(jobs, plan, n, 64, 128, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 1, 2, 2>(jobs, plan, n, 64, 64, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 1, 4, 1>(jobs, plan, n, 128, 32, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 1, 1, 4>(jobs, plan, n, 32, 128, stream, chain))) return rc;
+  // dense-block operand forms (conv1x1_bn_kernel's weight gradients)
+  if ((rc = launch_wgrad_group<2, 2, 2, 2, 1>(jobs, plan, n, 128, 128, stream, chain))) return rc;
+  if (g_wgrad_any) return launch_wgrad_any<1>(jobs, plan, n, stream, chain);
+  if ((rc = launch_wgrad_group<2, 1, 2, 2, 1>(jobs, plan, n, 128, 64, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 2, 2, 2, 1>(jobs, plan, n, 64, 128, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 1, 2, 2, 1>(jobs, plan, n, 64, 64, stream, chain))) return rc;
+  if ((rc = launch_wgrad_group<1, 1, 4, 1, 1>(jobs, plan, n, 128, 32, stream, chain))) return rc;
+  return launch_wgrad_group<1, 1, 1, 4, 1>(jobs, plan, n, 32, 128, stream, chain);
 }
 
 int da_conv_wgrad_multi(const da_wgrad_job* jobs, int n, hipStream_t stream) {
-  return conv_wgrad_multi_impl(jobs, n, nullptr, 0, nullptr, nullptr, stream);
+  return conv_wgrad_multi_impl(jobs, n, 0, nullptr, 0, nullptr, stream);
 }
 
 int da_conv_wgrad_multi_reduce(const da_wgrad_job* jobs, int n, float* const* dws, int accumulate, int* reduced,
-                               int* splits, hipStream_t stream) {
-  if (n && (!dws || !reduced || !splits)) return DA_EINVAL;
-  return conv_wgrad_multi_impl(jobs, n, dws, accumulate, reduced, splits, stream);
+                               hipStream_t stream) {
+  if (n && (!dws || !reduced)) return DA_EINVAL;
+  return conv_wgrad_multi_impl(jobs, n, 1, dws, accumulate, reduced, stream);
+}
+
+// The planning pass as a query (include/deepards_hip.h): slabs[i] = the slabs the matching launch writes into job i's workspace.
+int da_conv_wgrad_plan(const da_wgrad_job* jobs, int n, int chained, int* slabs) {
+  if (n > 0 && !slabs) return DA_EINVAL;
+  std::vector<WgradPlan> plan(n > 0 ? n : 0);
+  const int rc = wgrad_plan_jobs(jobs, n, chained, plan.data());
+  for (int i = 0; !rc && i < n; ++i) slabs[i] = plan[i].splits;
+  return rc;
 }
 
 // number of slabs da_conv_wgrad writes for this shape (workspace = splits * ntaps*N*C floats)
 int da_conv_wgrad_splits(int rows, int Lm, int N, int C, int ntaps) {
   return wgrad_plan(rows * Lm, N, C, ntaps).splits;
-}
-
-// the plan da_conv_wgrad / da_conv_wgrad_multi use for this shape: out = {tile_n, tile_c, splits, kchunk};
-// a job's workspace is splits * ntaps*N*C floats.  winograd != 0: the plan of a job with that flag set (k3 s1 p1;
-// kchunk counts output PAIRS).
-int da_conv_wgrad_plan(int rows, int Lm, int N, int C, int ntaps, int winograd, int* out) {
-  if (!out || ntaps < 1 || ntaps > 3 || N % 32 || C % 32) return DA_EINVAL;
-  if (winograd) {
-    if ((ntaps != 3 && winograd != 16 && winograd != 49) || N % 64 || C % 64) return DA_EINVAL;
-    out[0] = 64; out[1] = 64;
-    if (winograd == 16 || winograd == 49) bf16_wgrad_plan(rows, Lm, &out[2], &out[3]);     // kchunk counts padded positions
-    else if (winograd == 6) wino4_wgrad_plan(rows, Lm, &out[2], &out[3]);                  // ... quads
-    else wino_wgrad_plan(rows, Lm, &out[2], &out[3]);
-    return DA_OK;
-  }
-  WgradPlan p = wgrad_plan(rows * Lm, N, C, ntaps);
-  out[0] = p.tn; out[1] = p.tc; out[2] = p.splits; out[3] = p.kchunk;
-  return p.tn ? DA_OK : DA_EINVAL;
 }
 
 typedef struct {

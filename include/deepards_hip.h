@@ -142,7 +142,7 @@ int da_conv_bf16_multi(const da_conv_job* jobs, int n, da_stream_t stream);   /*
 typedef struct {
   const float* dy; const float* x; float* workspace;
   int rows, Lm, Ldy, lddy, N, Lx, ldx, C, dy_stride, dy_off, src_stride, ntaps; int src_off[3];
-  int winograd;   /* != 0: k3 s1 p1 job (N, C multiples of 64) in Winograd F(2,3) form; plan with winograd = 1;
+  int winograd;   /* != 0: k3 s1 p1 job (N, C multiples of 64) in Winograd F(2,3) form (6: F(4,3) form);
                      16: bf16 operands; 49: split-bf16 (fp32-equivalent) products with dy AND x in the x3
                      format (see da_conv3_x3p; lddy == N, ldx == C), k3 s1 p1 only */
   /* dense-block operand forms of stride-1 jobs on the direct kernels (winograd == 0; see da_conv1x1_bn): xform = 1: X is
@@ -157,16 +157,17 @@ int da_conv_wgrad_multi(const da_wgrad_job* jobs, int n, da_stream_t stream);  /
    owes it (the jobs of the call's last launch, always) -- da_wgrad_reduce_multi / da_step_tail_multi.  The sums are the
    ones da_wgrad_reduce_multi forms, bit for bit.  (replaces nothing of its own in the reference: the reduction of
    loss.backward()'s conv weight gradients, train_ards_detector.py:161-173) */
-int da_conv_wgrad_multi_reduce(const da_wgrad_job* jobs, int n, float* const* dws, int accumulate, int* reduced, int* splits, da_stream_t stream);
-/* splits[i] (out): the slabs job i wrote -- what its reduction must be given.  A job's workspace here must hold TWICE
-   da_conv_wgrad_plan's slabs: the winograd == 1 jobs of the launch's last, partly filled round run with half the pairs per
-   split (twice the slabs); the dense-block jobs of a call with 8 or more of them share ONE launch, are planned as a batch
-   and write fewer. */
+int da_conv_wgrad_multi_reduce(const da_wgrad_job* jobs, int n, float* const* dws, int accumulate, int* reduced, da_stream_t stream);
+/* host only (no HIP call): slabs[i] = the number of slabs (ntaps*N*C floats each) the matching launch will write into job
+   i's workspace -- chained = 0: da_conv_wgrad_multi, chained = 1: da_conv_wgrad_multi_reduce.  It is the launch's own
+   planning pass: the same shape validation (DA_EINVAL for the same jobs), the jobs' `workspace` pointers ignored (may be
+   NULL).  Size every workspace from it and give the same figure to the job's reduction.  Unchained, slabs[i] depends on
+   job i alone, so any subset of the array may be launched with the workspaces sized for the whole array; chained, it
+   depends on the whole array (the dense-block jobs of a call with 8 or more of them share one launch and are planned as
+   a batch; the winograd == 1 jobs of the launch's last, partly filled round run with half the pairs per split). */
+int da_conv_wgrad_plan(const da_wgrad_job* jobs, int n, int chained, int* slabs);
 /* deferred slab reduction: da_conv_wgrad with dw == NULL leaves da_conv_wgrad_splits() slabs in the workspace */
 int da_conv_wgrad_splits(int rows, int Lm, int N, int C, int ntaps);
-/* host only: out[4] = {tile_n, tile_c, splits, positions per split} the plan of da_conv_wgrad and
-   da_conv_wgrad_multi for this shape; a job's workspace is splits * ntaps*N*C floats */
-int da_conv_wgrad_plan(int rows, int Lm, int N, int C, int ntaps, int winograd, int* out);
 typedef struct { const float* slab; float* dw; int splits, ntaps, N, C; } da_wgrad_reduce_desc;
 int da_wgrad_reduce_multi(const da_wgrad_reduce_desc* descs, int n, int accumulate, da_stream_t stream);
 /* The tail of a training step in ONE launch: the slab reductions, every BatchNorm's dgamma / dbeta fold

@@ -232,6 +232,33 @@ def test_one_launch_for_all_tile_shapes_and_the_batch_plan(H):
         close(x.cpu().numpy(), r, tol=2e-5, name='batched dW %d' % n)
 
 
+def test_batch_plan_with_more_slabs_than_the_job_alone(H):
+    """8 chained dense-block jobs of M = 20 x 56 positions, 512 -> 256 channels, k3: the batch plan (target 320 blocks a job)
+    takes the 128 x 128 tile with 9 slabs where the job alone runs 128 x 32 with 5 -- the workspace comes from the call's
+    plan (da_conv_wgrad_plan), so the 9 slabs have their room; gradients == the oracle."""
+    rng = np.random.RandomState(5)
+    R, rows, L, C, N, k, cb = 20, 20, 56, 512, 256, 3, 544
+    jobs, refs = [], []
+    for _ in range(8):
+        x = rng.randn(rows, C, L) + rng.randn(1, C, 1)
+        gamma, beta = rng.rand(C) + 0.5, rng.randn(C) * 0.3
+        h_ref = np_ref.relu(np_ref.bn_window_fwd(x, gamma, beta, R)[0])
+        dy = rng.randn(rows, N, L)
+        refs.append(np_ref.conv1d_bwd(h_ref, np.zeros((N, C, k)), dy, 1, k // 2, need_dx=False)[1])
+        _, xv = pitched(x, cb)
+        mean_t, invstd_t = stat_tables(rows // R, cb)
+        H.bn_stats_fused(xv, R, mean_t[:, :C], invstd_t[:, :C])
+        _, dyv = pitched(dy, N + 32)
+        jobs.append((dyv, xv, k, 1, k // 2, {'xform': (mean_t[:, :C], invstd_t[:, :C], cu(gamma), cu(beta), R)}))
+    dws = [torch.zeros(r.shape, device='cuda') for r in refs]
+    slabs, reduced = H.conv_wgrad_multi(jobs, dws=dws, accumulate=False)
+    assert [sl[1] for sl in slabs] == [9] * 8
+    assert all(sl[0].numel() == 9 * k * N * C for sl in slabs)
+    H.wgrad_reduce_multi([(sl, dw) for sl, dw, r in zip(slabs, dws, reduced) if not r], accumulate=False)
+    for n, (x, r) in enumerate(zip(dws, refs)):
+        close(x.cpu().numpy(), r, tol=2e-5, name='batched dW %d' % n)
+
+
 @pytest.mark.parametrize('rows,L', [(40, 56), (40, 7), (300, 28), (1280, 14)])
 def test_winograd_growth_conv_with_dropout_in_the_epilogue(H, rows, L):
     """The growth conv (128 -> 32, k3) writing at a channel offset of a pitched buffer with F.dropout applied in its

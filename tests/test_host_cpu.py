@@ -89,6 +89,96 @@ def test_model_surface_matches_reference_inventory():
     assert float(r.bn1.weight.min()) == 1.0 and float(r.bn1.bias.abs().max()) == 0.0
 
 
+def _wgrad_job(rows, L, N, C, k, code=0, stride=1, xform=False, dy_half=False):
+    """A da_wgrad_job descriptor of Conv1d(C, N, k, stride, pad = k // 2) on rows x L outputs; the plan query dereferences
+    nothing, so every operand is one dummy non-null address (the launch's pointer checks) and the workspace stays NULL."""
+    from deepards_amd import _lib
+    j = _lib.WgradJob()
+    j.dy = j.x = 64
+    j.rows, j.Lm, j.Ldy, j.lddy, j.N, j.Lx, j.ldx, j.C = rows, L, L // 2 if dy_half else L, N, N, L * stride, C, C
+    j.dy_stride, j.dy_off, j.src_stride, j.ntaps = 1, 0, stride, k
+    for t in range(k):
+        j.src_off[t] = t - k // 2
+    j.winograd = code
+    if xform or dy_half:
+        j.xform, j.dy_half, j.Wn, j.ldstat = 1, 1 if dy_half else 0, 20 * L, C
+        j.mean = j.invstd = j.gamma = j.beta = 64
+    return j
+
+
+def _wgrad_slabs(jobs, chained):
+    """-> (rc, [slabs per job]) of da_conv_wgrad_plan."""
+    import ctypes
+    from deepards_amd import _lib
+    arr = (_lib.WgradJob * len(jobs))(*jobs)
+    out = (ctypes.c_int * len(jobs))()
+    rc = _lib.lib().da_conv_wgrad_plan(arr, len(jobs), chained, out)
+    return rc, list(out)
+
+
+def test_wgrad_plan_query_reports_what_the_launch_writes():
+    """da_conv_wgrad_plan over job arrays (host only): the slab counts of the launch's own planning pass.
+    Unchained, and chained below 8 dense-block jobs, a job's count is that job's alone (a direct job's = da_conv_wgrad_splits)
+    whatever else the array holds; chained, 8 or more dense-block jobs are planned as a batch and the F(2,3) jobs behind the
+    launch's last whole round of 1 024 slots write twice the slabs."""
+    from deepards_amd import _lib
+    _lib.build()
+    lib = _lib.lib()
+
+    def alone(j):
+        return lib.da_conv_wgrad_splits(j.rows, j.Lm, j.N, j.C, j.ntaps)
+
+    rows = 1280                                                  # B = 64 windows of 20 rows
+    direct = [_wgrad_job(rows, 28, 128, 64, 3, stride=2), _wgrad_job(rows, 28, 128, 64, 1, stride=2),
+              _wgrad_job(rows, 56, 64, 64, 3), _wgrad_job(rows, 7, 512, 256, 3, stride=2)]
+    dense = [_wgrad_job(rows, 56, 128, 32 * (i + 1), 1, xform=True) for i in range(6)] + \
+            [_wgrad_job(rows, 56, 32, 128, 3, xform=True), _wgrad_job(rows, 56, 128, 128, 1, dy_half=True)] * 3
+    coded = [_wgrad_job(rows, 56, 64, 64, 3, code=1), _wgrad_job(rows, 7, 512, 512, 3, code=6),
+             _wgrad_job(rows, 28, 128, 128, 3, code=16), _wgrad_job(rows, 14, 256, 128, 3, code=16, stride=2),
+             _wgrad_job(rows, 14, 256, 256, 3, code=49), _wgrad_job(rows, 14, 256, 128, 1, code=49, stride=2)]
+    # unchained: every job as if alone -- 12 dense-block jobs and all five winograd codes in one array, in two orders
+    mixed = direct + dense + coded
+    assert len(dense) == 12 and {j.winograd for j in mixed} == {0, 1, 6, 16, 49}
+    # ... and chained with 7 dense-block jobs (one F(2,3) job: less than a round)
+    for jobs, chained in ((mixed, 0), (mixed[::-1], 0), (coded + direct + dense[:7], 0), (coded + direct + dense[:7], 1)):
+        rc, slabs = _wgrad_slabs(jobs, chained)
+        assert rc == 0
+        for j, s in zip(jobs, slabs):
+            assert s >= 1 and _wgrad_slabs([j], 0) == (0, [s])
+            if j.winograd == 0:
+                assert s == alone(j)
+    # chained, 8 or more dense-block jobs: the batch plan (per-job target 2560 // n blocks), not the job's plan alone
+    big = _wgrad_job(2040, 56, 128, 64, 1, xform=True)           # M = 114 240 (B = 102)
+    small = _wgrad_job(20, 56, 256, 512, 3, xform=True)          # M = 1 120
+    assert (alone(big), alone(small)) == (255, 5)
+    assert _wgrad_slabs([big] * 9, 1) == (0, [275] * 9)
+    assert _wgrad_slabs([small] * 8, 1) == (0, [9] * 8)
+    assert _wgrad_slabs([big] * 9, 0) == (0, [255] * 9) and _wgrad_slabs([small] * 7, 1) == (0, [5] * 7)
+    assert lib.da_debug_set(7, 0) == 0                            # one launch per tile shape: no batch plan, here as in the launch
+    try:
+        assert _wgrad_slabs([big] * 9, 1) == (0, [255] * 9)
+    finally:
+        assert lib.da_debug_set(7, 1) == 0
+    # chained F(2,3): resnet18 at B = 64, in the backward's order -- layer 3, layer 2 (1 008 blocks), layer 1 (224 blocks,
+    # behind the last whole round of 1 024 slots: 448 half blocks, twice the slabs); the F(4,3) jobs are another launch
+    wino = [_wgrad_job(rows, 7, 512, 512, 3, code=6)] * 3 + [_wgrad_job(rows, 14, 256, 256, 3, code=1)] * 3 + \
+           [_wgrad_job(rows, 28, 128, 128, 3, code=1)] * 3 + [_wgrad_job(rows, 56, 64, 64, 3, code=1)] * 4
+    rc, plain = _wgrad_slabs(wino, 0)
+    assert rc == 0 and plain[3:] == [14] * 3 + [28] * 3 + [56] * 4
+    blocks = [(j.N // 64) * (j.C // 64) * s for j, s in zip(wino, plain)]
+    assert sum(blocks[3:9]) == 1008 and sum(blocks[9:]) == 224
+    rc, chained = _wgrad_slabs(wino, 1)
+    assert rc == 0 and chained == plain[:9] + [112] * 4
+    assert sum((j.N // 64) * (j.C // 64) * s for j, s in zip(wino[9:], chained[9:])) == 448
+    assert _wgrad_slabs(wino[:9], 1) == (0, plain[:9])          # 1 008 blocks: less than one round, as planned
+    # jobs no kernel takes: DA_EINVAL from the query as from the launch
+    for bad in (_wgrad_job(rows, 56, 32, 32, 3), _wgrad_job(rows, 56, 64, 64, 1, code=1), _wgrad_job(rows, 56, 96, 64, 3, code=6),
+                _wgrad_job(rows, 56, 64, 64, 3, code=2), _wgrad_job(rows, 56, 64, 48, 1)):
+        for chained in (0, 1):
+            assert _wgrad_slabs([direct[0], bad], chained)[0] == -1
+    assert _wgrad_slabs([], 0) == (0, [])
+
+
 def test_host_helpers():
     from deepards_amd.train import clip_odd_batch_sizes, shard_windows
     idx, seq, meta, tgt = torch.arange(5), torch.zeros(5, 20, 1, 224), torch.zeros(5), torch.zeros(5, 2)
