@@ -47,8 +47,8 @@ def training_step(model=None):
                   if isinstance(m, torch.nn.Conv1d) and m.kernel_size[0] <= 3 and m.in_channels % 32 == 0
                   and m.weight.is_cuda]
             ws = [m.weight for m in ms]
-            wino = [_step_pack_code(m) for m in ms]
-            for w, c, e in zip(ws, wino, H.repack_multi(ws, wino)):
+            forms = [H.step_pack_form(*m.weight.shape, m.stride[0], m.padding[0]) for m in ms]
+            for w, c, e in zip(ws, forms, H.repack_multi(ws, forms)):
                 _STEP['pack'][(w.data_ptr(), int(c))] = e
         yield
     finally:
@@ -100,32 +100,27 @@ def _launch_wgrads():
 
 
 _WGRAD_CHAIN = True       # (tests switch it off to compare with the one reduction launch behind all weight gradients)
-_WINO4_MIN_C = 512        # channels from which F(4,3) beats F(2,3) (scripts/bench_wino.py; DESIGN appendix)
 
 
-# Arithmetic of the k3 s1 p1 convs' forward / data gradient: 'f32' (Winograd on the fp32 matrix cores), 'bf16' (BASELINE
-# config C3: operands rounded to bf16, fp32 sums, conv_bf16.hip; also the k3 s1 weight gradients) or 'f32x3p'
-# (fp32-equivalent products from exact three-term bf16 splits on the bf16 matrix cores, the split done by the PRODUCERS:
-# the BatchNorm / pool kernels in front of a k3 s1 conv store the x3 format, conv_x3p.hip and the x3 weight-gradient
-# kernel read it; forward, data gradient and weight gradient; opt-in, frozen since round 3).
-_CONV_DTYPE = os.environ.get('DA_CONV_DTYPE', 'f32')
+# Arithmetic of the convs (H.CONV_DTYPE, beside the kernel choice it drives): 'f32', 'bf16' (BASELINE config C3) or 'f32x3p'
+# (the split into x3 operands is done by the PRODUCERS: the BatchNorm / pool kernels in front of a k3 s1 conv or a stride-2
+# block entry store the x3 format; opt-in, frozen since round 3).
 _STEM_FUSED = os.environ.get('DA_STEM_FUSED', '1') != '0'   # the default stem recomputes its conv output instead of storing it
 CONV_DTYPES = ('f32', 'bf16', 'f32x3p')
 
 
 def set_conv_dtype(name):
-    """One of CONV_DTYPES (see _CONV_DTYPE); captured steps keep the arithmetic they were captured with."""
-    global _CONV_DTYPE
+    """One of CONV_DTYPES (above); captured steps keep the arithmetic they were captured with."""
     if name not in CONV_DTYPES:
         raise ValueError('conv dtype must be one of %s' % (CONV_DTYPES,))
     if name != 'bf16' and H.act_dtype() == 'bf16':
         H.set_act_dtype('f32')                     # fp32 convs read fp32 activations
-    _CONV_DTYPE = name
+    H.CONV_DTYPE = name
     H.WGRAD_BF16 = name == 'bf16'
 
 
 def conv_dtype():
-    return _CONV_DTYPE
+    return H.CONV_DTYPE
 
 
 def set_storage_dtype(name):
@@ -133,7 +128,7 @@ def set_storage_dtype(name):
     configs C3 / C5: bf16 storage with fp32 statistics and accumulators).  bf16 storage needs conv dtype 'bf16' and a
     network whose convs all have bf16 kernels (the ResNets: channel counts multiples of 64, even lengths at the
     stride-2 heads); captured steps keep the storage they were captured with."""
-    if name == 'bf16' and _CONV_DTYPE != 'bf16':
+    if name == 'bf16' and H.CONV_DTYPE != 'bf16':
         raise ValueError("bf16 storage needs conv dtype 'bf16' (set_conv_dtype('bf16') first)")
     H.set_act_dtype(name)
 
@@ -142,52 +137,11 @@ def storage_dtype():
     return H.act_dtype()
 
 
-set_conv_dtype(_CONV_DTYPE)
-
-
-def _is_wino(w, stride, pad):
-    """How a conv's forward / data gradient runs: 0 = direct fp32 kernel; k3 s1 p1 convs: 4 = Winograd F(2,3) (2/3 of
-    the direct conv's MFMAs, fp32 throughout), 6 = F(4,3) (1/2 of them; pays once both channel counts reach
-    _WINO4_MIN_C), 16 = bf16 products with fp32 sums (conv dtype 'bf16', channel counts multiples of 64; also the
-    k3 s2 p1 and k1 s2 p0 convs)."""
-    if _CONV_DTYPE == 'bf16' and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0 and (
-            (w.shape[2] == 3 and pad == 1 and stride in (1, 2)) or (w.shape[2] == 1 and pad == 0 and stride == 2)):
-        return 16                                   # also the stride-2 block heads and 1x1 downsamples (even lengths)
-    if not (w.shape[2] == 3 and stride == 1 and pad == 1 and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0):
-        return 0
-    if _CONV_DTYPE == 'f32x3p' and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0:
-        return 49                                   # the same on x3 (pre-split) operands (conv_x3p.hip); float operands: _fp32_code
-    return _fp32_code(w)
-
-
-def s2_x3_ok(w1, wd, l_in):
-    """Whether a stride-2 block entry (k3 s2 p1 conv + 1x1 s2 downsample) runs on x3 operands (conv arithmetic 'f32x3p':
-    H.conv_x3p_s2_fwd / _dgrad and the x3 weight-gradient jobs): even input length, channel counts multiples of 64."""
-    return _CONV_DTYPE == 'f32x3p' and H.act_dtype() == 'f32' and wd is not None and l_in % 2 == 0 and \
-        tuple(w1.shape[2:]) == (3,) and tuple(wd.shape[2:]) == (1,) and tuple(wd.shape[:2]) == tuple(w1.shape[:2]) and \
-        w1.shape[0] % 64 == 0 and w1.shape[1] % 64 == 0
-
-
-def _step_pack_code(m):
-    """The pack form the step's batched repack prepares for a conv module (a consumer that needs another form packs it
-    itself, once: _pack)."""
-    w, stride, pad = m.weight, m.stride[0], m.padding[0]
-    if _CONV_DTYPE == 'f32x3p' and H.act_dtype() == 'f32' and stride == 2 and w.shape[0] % 64 == 0 and \
-            w.shape[1] % 64 == 0 and (w.shape[2], pad) in ((3, 1), (1, 0)):
-        return 49                                   # the stride-2 block entries on x3 operands (s2_x3_ok)
-    return _is_wino(w, stride, pad)
-
-
-def _fp32_code(w):
-    """The fp32 kernel of a k3 s1 p1 conv whose operand is a float tensor: Winograd F(2,3) / F(4,3) or direct."""
-    if not H.WINOGRAD_WGRAD:
-        return 0
-    return 6 if min(w.shape[0], w.shape[1]) >= _WINO4_MIN_C else 4
+set_conv_dtype(os.environ.get('DA_CONV_DTYPE', 'f32'))
 
 
 def _pack(w, code):
-    """(wf, wd, uf, ud) of a conv weight: direct packs (code 0), Winograd taps or bf16 tap packs (in the uf / ud
-    places), repacked once per step."""
+    """(wf, wd, uf, ud) of a conv weight in the form of kernel ``code`` (H.repack_multi), repacked once per step."""
     key = (w.data_ptr(), int(code))                 # a weight may be packed in two forms in one step (x3 and fp32 consumers)
     e = _STEP['pack'].get(key) if _STEP['on'] else None
     if e is None:
@@ -197,44 +151,26 @@ def _pack(w, code):
     return e
 
 
-def _need_bf16_kernel(code, w, stride, pad):
-    if code != 16 and H.act_dtype() == 'bf16':
-        raise NotImplementedError('bf16 activation storage: the conv %s stride %d pad %d has no bf16 kernel (channel counts '
-                                  'must be multiples of 64, stride-2 inputs of even length)' % (tuple(w.shape), stride, pad))
-
-
 def _conv_fwd(x, w, stride, pad):
-    code = _is_wino(w, stride, pad)
-    if code == 49:
-        if H.is_x3(x):
-            return H.conv3_x3p(x, _pack(w, 49)[2])
-        code = _fp32_code(w)                        # a float operand (a shape without x3 producers): the fp32 kernels
-    if code == 16 and stride == 2 and x.shape[1] % 2:
-        code = 0                                    # odd length: the fp32 kernel
-    _need_bf16_kernel(code, w, stride, pad)
-    if code == 16:
-        return H.conv3_bf16(x, _pack(w, code)[2]) if stride == 1 else H.conv_fwd_bf16_s2(x, _pack(w, code)[2])
-    if code:
-        return H.conv3_winograd(x, _pack(w, code)[2])
-    return H.conv_fwd(x, _pack(w, 0)[0], stride, pad)
+    kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(x), x.shape[1])
+    if kern == H.DIRECT:
+        return H.conv_fwd(x, _pack(w, kern)[0], stride, pad)
+    pk = _pack(w, kern)[2]
+    if kern == H.BF16 and stride == 2:
+        return H.conv_fwd_bf16_s2(x, pk)
+    fn = H.conv3_x3p if kern == H.X3 else H.conv3_bf16 if kern == H.BF16 else H.conv3_winograd
+    return fn(x, pk)
 
 
 def _conv_dgrad(dy, w, stride, pad, l_in, out=None, accumulate=False):
-    code = _is_wino(w, stride, pad)
-    if code == 49:
-        if H.is_x3(dy):
-            return H.conv3_x3p(dy, _pack(w, 49)[3], out=out, accumulate=accumulate)
-        code = _fp32_code(w)
-    if code == 16 and stride == 2 and l_in % 2:
-        code = 0
-    _need_bf16_kernel(code, w, stride, pad)
-    if code == 16:
-        if stride == 2:
-            return H.conv_dgrad_bf16_s2(dy, _pack(w, code)[3], l_in, out=out, accumulate=accumulate)
-        return H.conv3_bf16(dy, _pack(w, code)[3], out=out, accumulate=accumulate)
-    if code:
-        return H.conv3_winograd(dy, _pack(w, code)[3], out=out, accumulate=accumulate)
-    return H.conv_dgrad(dy, _pack(w, 0)[1], stride, pad, l_in, out=out, accumulate=accumulate)
+    kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(dy), l_in)
+    if kern == H.DIRECT:
+        return H.conv_dgrad(dy, _pack(w, kern)[1], stride, pad, l_in, out=out, accumulate=accumulate)
+    pk = _pack(w, kern)[3]
+    if kern == H.BF16 and stride == 2:
+        return H.conv_dgrad_bf16_s2(dy, pk, l_in, out=out, accumulate=accumulate)
+    fn = H.conv3_x3p if kern == H.X3 else H.conv3_bf16 if kern == H.BF16 else H.conv3_winograd
+    return fn(dy, pk, out=out, accumulate=accumulate)
 
 
 # A captured training step may run WITHOUT the zero-fill of the gradient bucket: every gradient destination is then written
@@ -281,12 +217,6 @@ def x3_handle(x3):
     if z is None:
         z = _HANDLES[x3.device] = torch.zeros(1, device=x3.device, dtype=torch.float32)
     return z.expand(rows, l, g * 16)
-
-
-def x3_block_ok(rows, l, c, R):
-    """Whether a block whose activations are (rows, L, C) in windows of R rows can run its k3 s1 convs on x3 operands:
-    conv arithmetic 'f32x3p', float storage, 64-multiple channels and the single-pass BatchNorm geometry (its store forms)."""
-    return _CONV_DTYPE == 'f32x3p' and H.act_dtype() == 'f32' and c % 64 == 0 and H.bn_x3_ok(rows, l, c, R)
 
 
 def _bn_apply_x(x, R, s, st, gamma, beta, relu, res=None, want_mask=False, out_x3=True):
@@ -555,33 +485,30 @@ class BasicBlockFunction(Function):
         # is never stored -- bn2 + residual + ReLU hand over the pooled features (rows, C) float (H.bn_fwd_pool), and the
         # backward takes their gradient (H.bn_bwd_pool): two 18 MB passes and the pooling launch less at B = 64
         in3 = x3 is not None
-        bf16_pair = wd is not None and stride == 2 and x.shape[1] % 2 == 0 and \
-            _is_wino(w1, stride, 1) == 16 and _is_wino(wd, stride, 0) == 16
-        pair = bf16_pair or (wd is not None and stride == 2 and not _is_wino(w1, stride, 1))
-        s2x = in3 and stride == 2
+        # conv1 and the downsample conv of a stride-2 entry in one launch (H.X3 / BF16 / DIRECT), or None: separate convs
+        entry = H.s2_entry_kernel(w1.shape, None if wd is None else wd.shape, stride, x.shape[1], in3)
+        if in3 and stride == 2 and entry != H.X3:
+            raise ValueError('x3 input handed to a stride-2 block whose shape has no x3 kernels')
+        pair = entry is not None
+        want1, want2 = H.conv_kernel_wanted(*w1.shape, stride, 1), H.conv_kernel_wanted(*w2.shape, 1, 1)
         # conv dtype bf16, a stride-1 block: bn1 has no pass of its own (H.conv3_bf16_bn at both ends); a window must cover a
         # 128-position tile and its halo
         fuse1 = _BN1_FUSED and not in3 and stride == 1 and R * x.shape[1] >= 130 and x.shape[0] % R == 0 and \
-            _is_wino(w1, 1, 1) == 16 and _is_wino(w2, 1, 1) == 16 and \
-            H.bn_single_pass(x.shape[0] // R, R * x.shape[1], w1.shape[0])
-        ctx.fuse1 = fuse1
-        ctx.bf16_pair = bf16_pair
-        if s2x:           # the stride-2 block entry on the pre-split input: conv1 and the downsample conv in one launch
-            if not s2_x3_ok(w1, wd, x3.shape[1]):
-                raise ValueError('x3 input handed to a stride-2 block whose shape has no x3 kernels')
-            y1, yd = H.conv_x3p_s2_fwd(x3, _pack(w1, 49)[2], _pack(wd, 49)[2])
-            pair = True
+            want1 == H.BF16 and want2 == H.BF16 and H.bn_single_pass(x.shape[0] // R, R * x.shape[1], w1.shape[0])
+        ctx.fuse1, ctx.entry = fuse1, entry
+        if entry == H.X3:  # the stride-2 block entry on the pre-split input: conv1 and the downsample conv in one launch
+            y1, yd = H.conv_x3p_s2_fwd(x3, _pack(w1, H.X3)[2], _pack(wd, H.X3)[2])
         elif in3:         # k3 s1 conv on the pre-split input
             y1 = _conv_fwd(x3, w1, 1, 1)
         elif fuse1:       # conv dtype bf16, stride 1: the statistics records of y1 come out of the conv's epilogue
-            y1, rec1 = H.conv3_bf16_bn(x, _pack(w1, 16)[2], R, want_records=True)
-        elif bf16_pair:   # conv dtype bf16: the same shared launch on the bf16 kernel
-            y1, yd = H.conv_fwd_bf16_s2(x, _pack(w1, 16)[2], _pack(wd, 16)[2])
-        elif pair:    # the stride-2 conv and the 1x1 downsample read the same input: one launch
-            y1, yd = H.conv_fwd_multi([(x, _pack(w1, False)[0], stride, 1), (x, _pack(wd, False)[0], stride, 0)])
+            y1, rec1 = H.conv3_bf16_bn(x, _pack(w1, H.BF16)[2], R, want_records=True)
+        elif entry == H.BF16:     # conv dtype bf16: the same shared launch on the bf16 kernel
+            y1, yd = H.conv_fwd_bf16_s2(x, _pack(w1, H.BF16)[2], _pack(wd, H.BF16)[2])
+        elif pair:        # the stride-2 conv and the 1x1 downsample read the same input: one launch
+            y1, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 1), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
         else:
             y1 = _conv_fwd(x, w1, stride, 1)
-        mid3 = x3_block_ok(y1.shape[0], y1.shape[1], y1.shape[2], R) and _is_wino(w2, 1, 1) == 49
+        mid3 = H.x3_block_ok(y1.shape[0], y1.shape[1], y1.shape[2], R) and want2 == H.X3
         if (in3 or want_out3) and not mid3:
             raise ValueError('x3 input / output asked of a block whose shape has no x3 store forms')
         s1 = _Stats()
@@ -603,7 +530,7 @@ class BasicBlockFunction(Function):
             wn_ = y1.shape[0] // R
             s1.mean = torch.empty((wn_, y1.shape[2]), device=y1.device, dtype=torch.float32)
             s1.invstd = torch.empty_like(s1.mean)
-            y2 = H.conv3_bf16_bn(y1, _pack(w2, 16)[2], R, rec=rec1, mean=s1.mean, invstd=s1.invstd, gamma=g1, beta=b1, eps=st1.eps)
+            y2 = H.conv3_bf16_bn(y1, _pack(w2, H.BF16)[2], R, rec=rec1, mean=s1.mean, invstd=s1.invstd, gamma=g1, beta=b1, eps=st1.eps)
             _running(y1, R, s1, st1)
             h1 = y1                                     # (placeholder in the saved list: the backward rebuilds h1 for the weight gradient)
             if DECISION_TAP is not None:
@@ -639,7 +566,7 @@ class BasicBlockFunction(Function):
             _tap(out)
         m1, i1, m2, i2 = s1.mean, s1.invstd, s2.mean, s2.invstd
         ctx.relu_mask = s2.mask     # 8 bytes per thread instead of re-reading `out` for its sign (None: two-stage geometry)
-        ctx.has_ds, ctx.in3, ctx.mid3, ctx.s2x = wd is not None, in3, mid3, s2x
+        ctx.has_ds, ctx.in3, ctx.mid3 = wd is not None, in3, mid3
         ctx.stride, ctx.R, ctx.lin = stride, R, x.shape[1]
         ctx.gt = _tgt(w1, g1, b1, w2, g2, b2, wd, gd, bd)
         # (the float block output is only kept when the backward reads it for its sign: no bit mask)
@@ -664,7 +591,7 @@ class BasicBlockFunction(Function):
         d2 = _STEP['dout2'].pop(dout.data_ptr(), None) if _STEP['on'] and _STEP.get('dout2') else None
         dout = dout.contiguous()
         # relu + residual add + bn2
-        bwd_pair = ctx.has_ds and ctx.bn_pair and ctx.relu_mask is not None and not mid3 and not ctx.s2x
+        bwd_pair = ctx.has_ds and ctx.bn_pair and ctx.relu_mask is not None and not mid3 and ctx.entry != H.X3
         two = d2 is not None and not ctx.pool_out and not mid3 and ctx.relu_mask is not None and H.bn_two_ok(y2, R)
         if d2 is not None and not two:      # (a shape without the two-term kernels: sum them here)
             dout = dout + d2
@@ -687,7 +614,7 @@ class BasicBlockFunction(Function):
             dy2, dg2, db2, g = _bn_bwd(dout, y2, R, m2, i2, g2, b2, 2, tg2, tb2, out=out, want_g=True, mask=ctx.relu_mask)
         if ctx.has_ds and not bwd_pair:    # the downsample BatchNorm's backward right away: g is still cache-resident
             wd, gd, bd, yd, md, idd = s[15:]
-            if ctx.s2x:       # x3: it feeds the stride-2 data-gradient and weight-gradient kernels
+            if ctx.entry == H.X3:     # x3: it feeds the stride-2 data-gradient and weight-gradient kernels
                 dyd, dgd, dbd = _bn_bwd_x(g, yd, R, md, idd, gd, bd, 0, tgd, tbd)
             else:
                 dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, tgd, tbd, dx=g)
@@ -708,12 +635,12 @@ class BasicBlockFunction(Function):
         dw1 = _wgrad(dy1, x, 3, stride, 1, tw1)
         if ctx.has_ds:
             dwd = _wgrad(dyd, x, 1, stride, 0, twd)
-            if ctx.s2x:
-                dx = H.conv_x3p_s2_dgrad(dy1, _pack(w1, 49)[3], dyd, _pack(wd, 49)[3])
-            elif stride == 2 and not _is_wino(w1, stride, 1):
-                dx = H.conv_dgrad_s2_pair(dy1, _pack(w1, False)[1], dyd, _pack(wd, False)[1], lin)
-            elif ctx.bf16_pair and _BF16_DGRAD_PAIR:    # conv dtype bf16: the same shared launch (two sources in the even problem)
-                dx = H.conv_dgrad_bf16_s2_pair(dy1, _pack(w1, 16)[3], dyd, _pack(wd, 16)[3], lin)
+            if ctx.entry == H.X3:   # the entry form the forward chose
+                dx = H.conv_x3p_s2_dgrad(dy1, _pack(w1, H.X3)[3], dyd, _pack(wd, H.X3)[3])
+            elif ctx.entry == H.DIRECT:
+                dx = H.conv_dgrad_s2_pair(dy1, _pack(w1, H.DIRECT)[1], dyd, _pack(wd, H.DIRECT)[1], lin)
+            elif ctx.entry == H.BF16 and _BF16_DGRAD_PAIR:    # conv dtype bf16: the same shared launch (two sources in the even problem)
+                dx = H.conv_dgrad_bf16_s2_pair(dy1, _pack(w1, H.BF16)[3], dyd, _pack(wd, H.BF16)[3], lin)
             else:
                 dx = _conv_dgrad(dy1, w1, stride, 1, lin)
                 _conv_dgrad(dyd, wd, stride, 0, lin, out=dx, accumulate=True)
@@ -739,7 +666,7 @@ def dense_block_ok(rows, R, l, c0, growth, n_layers, mid, tail_out, use_drop):
     (0: by norm5), runs as ONE DenseBlockFunction: float storage, the single-pass BatchNorm geometry for every channel count
     of the block, an even length in front of a transition (its pooling is folded in front of its conv), channel counts the
     kernels tile (growth % 32, 1x1 outputs % 64), and -- with dropout on -- the Winograd growth conv (its epilogue drops)."""
-    if not (_DENSE_BLOCK and _CONV_DTYPE != 'bf16' and growth % 32 == 0 and c0 % 32 == 0 and mid % 64 == 0 and n_layers >= 1):
+    if not (_DENSE_BLOCK and H.CONV_DTYPE != 'bf16' and growth % 32 == 0 and c0 % 32 == 0 and mid % 64 == 0 and n_layers >= 1):
         return False
     if tail_out and (l % 2 or tail_out % 64 or R * (l // 2) < 64):
         return False
@@ -790,17 +717,17 @@ class DenseBlockFunction(Function):
         pl = (l + 1) // 2
         rec_ok = R * pl >= 64
         drop = drop_p > 0
-        keep, fused2 = [], []
+        keep, forms = [], []                            # forms: per layer (fuse2, the growth conv's kernel), for the backward
         for k in range(n_layers):
             g1, b1, w1, g2, b2, w2 = params[6 * k:6 * k + 6]
             ck = c0 + k * G
             xk = buf[:, :, :ck]
             mid = w1.shape[0]
             y1 = torch.empty((rows, l, mid), device=buf.device, dtype=torch.float32)
-            code = _is_wino(w2, 1, 1)
+            code = H.conv_kernel_wanted(*w2.shape, 1, 1)
             # norm2 -> relu2 -> conv2 as ONE kernel (the Winograd growth conv normalises while it stages, from the records
             # the 1x1 conv's epilogue hands over): h2 = relu(norm2(y1)) is then never stored either -- ``fuse2``
-            fuse2 = code == 4 and rec_ok and mid <= 128 and R * l >= 64
+            fuse2 = code == H.WINO2 and rec_ok and mid <= 128 and R * l >= 64
             r1 = H.conv1x1_bn(xk, w1, R, mean_t[:, :ck], invstd_t[:, :ck], g1, b1, y1, pend=pend, eps=eps, want_records=fuse2)
             pend = None
             if DECISION_TAP is not None:
@@ -821,18 +748,18 @@ class DenseBlockFunction(Function):
             else:
                 h2, m2, i2 = H.bn_fwd(y1, R, g2, b2, relu=True, eps=eps)
                 _tap(h2)
-                if code == 4:
+                if code == H.WINO2:
                     r_ = H.conv3_winograd(h2, _pack(w2, code)[2], out=new, drop=dr, stats_R=R if consumed and rec_ok else 0)
                     if consumed and rec_ok:
                         pend = (r_[1], ck, rows * pl, R * pl)
-                elif code == 6:
+                elif code == H.WINO4:
                     H.conv3_winograd(h2, _pack(w2, code)[2], out=new)
                 else:
-                    H.conv_fwd(h2, _pack(w2, 0)[0], 1, 1, out=new)
+                    H.conv_fwd(h2, _pack(w2, H.DIRECT)[0], 1, 1, out=new)
             if consumed and pend is None:
                 H.bn_stats_fused(new, R, mean_t[:, ck:ck + G], invstd_t[:, ck:ck + G], eps)
             keep += [y1, m2, i2, h2]
-            fused2.append(fuse2)
+            forms.append((fuse2, code))
         out_rec = None
         if tail_cb:
             gt, bt, wt = params[6 * n_layers:6 * n_layers + 3]
@@ -851,7 +778,7 @@ class DenseBlockFunction(Function):
             keep += [m5, i5]
             ctx.tail_out = out if tail_relu else None      # (its sign is the backward's ReLU decision)
         ctx.cfg = (R, c0, G, n_layers, drop_p, salt0, tail_cb, tail_relu)
-        ctx.fused2 = fused2
+        ctx.forms = forms
         ctx.gt = _tgt(*params)
         ctx.save_for_backward(buf, stats, seed if drop else stats, *keep, *params)
         if tail_cb:                                     # (next buffer, the records of its first channels)
@@ -893,7 +820,7 @@ class DenseBlockFunction(Function):
             dy = dout[:, :, :wt.shape[0]]
             grads[pt + 2] = _wgrad(dy, buf, 1, 1, 0, tg[pt + 2],
                                    {'xform': (mean_t, invstd_t, gt_, bt_, R), 'dy_half': True})
-            dpool = H.conv_dgrad(dy, _pack(wt, 0)[1], 1, 0, l // 2)
+            dpool = H.conv_dgrad(dy, _pack(wt, H.DIRECT)[1], 1, 0, l // 2)
             ds = H.bn_bwd_ss(dpool, buf, R, mean_t, invstd_t, gt_, bt_, 1, dbuf, half_dout=True, drop=last_drop)
         else:
             g5, b5 = params[pt:pt + 2]
@@ -906,13 +833,12 @@ class DenseBlockFunction(Function):
             y1, m2, i2, h2 = keep[4 * k:4 * k + 4]
             ck = c0 + k * G
             dnew = dbuf[:, :, ck:ck + G]                    # (its dropout mask was applied by the kernel that wrote it last)
-            f2 = ctx.fused2[k]
+            f2, kern = ctx.forms[k]
             grads[6 * k + 5] = _wgrad(dnew, y1 if f2 else h2, 3, 1, 1, tg[6 * k + 5], {'xform': (m2, i2, g2, b2, R)} if f2 else None)
-            code = _is_wino(w2, 1, 1)
-            if code in (4, 6):
-                dh2 = H.conv3_winograd(dnew, _pack(w2, code)[3])
+            if kern in (H.WINO2, H.WINO4):
+                dh2 = H.conv3_winograd(dnew, _pack(w2, kern)[3])
             else:
-                dh2 = H.conv_dgrad(dnew, _pack(w2, 0)[1], 1, 1, l)
+                dh2 = H.conv_dgrad(dnew, _pack(w2, H.DIRECT)[1], 1, 1, l)
             if f2:      # the ReLU decision of the form the forward applied (fused multiply-add), in place
                 ds2 = H.bn_bwd_ss(dh2, y1, R, m2, i2, g2, b2, 1, dh2)
                 fold(ds2, g2, b2, 6 * k + 3, 6 * k + 4)
@@ -921,7 +847,7 @@ class DenseBlockFunction(Function):
                 dy1, grads[6 * k + 3], grads[6 * k + 4] = _bn_bwd(dh2, y1, R, m2, i2, g2, b2, 1, tg[6 * k + 3], tg[6 * k + 4], dx=dh2)
             xk, mk, ik = buf[:, :, :ck], mean_t[:, :ck], invstd_t[:, :ck]
             grads[6 * k + 2] = _wgrad(dy1, xk, 1, 1, 0, tg[6 * k + 2], {'xform': (mk, ik, g1, b1, R)})
-            dh = H.conv_dgrad(dy1, _pack(w1, 0)[1], 1, 0, l)
+            dh = H.conv_dgrad(dy1, _pack(w1, H.DIRECT)[1], 1, 0, l)
             dxk = dbuf[:, :, :ck]
             ds = H.bn_bwd_ss(dh, xk, R, mk, ik, g1, b1, 1, dxk, add=dxk,
                              drop=(seed, salt0 + k - 1, drop_p, G) if drop and k > 0 else None)

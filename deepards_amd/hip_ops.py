@@ -291,7 +291,7 @@ def x3_merge(x3):
 
 def conv3_x3p(x3, wpk, out=None, accumulate=False):
     """k3 s1 p1 conv of an x3 activation (rows, L, C/16, 3, 16) with the chunked split-bf16 pack wpk (N/64, C/16, 18, 64, 8)
-    (repack_multi code 49): fp32-equivalent products on the bf16 matrix cores, fp32 sums -> (rows, L, N) fp32."""
+    (repack_multi form X3): fp32-equivalent products on the bf16 matrix cores, fp32 sums -> (rows, L, N) fp32."""
     if not (is_x3(x3) and x3.is_cuda and x3.is_contiguous()):
         raise ValueError('conv3_x3p: a contiguous x3 CUDA tensor expected, got %s %s' % (tuple(x3.shape), x3.dtype))
     rows, l, g = x3.shape[:3]
@@ -317,7 +317,7 @@ def _x3p_pack_ok(pk, nt, kc):
 
 def conv_x3p_s2_fwd(x3, w1pk, wdpk):
     """The stride-2 block entry on x3 operands: (y1, yd) = (conv k3 s2 p1, conv 1x1 s2) of the x3 activation
-    (rows, Lin, C/16, 3, 16), Lin even, from ONE read of it.  w1pk / wdpk: forward packs of repack_multi code 49
+    (rows, Lin, C/16, 3, 16), Lin even, from ONE read of it.  w1pk / wdpk: forward packs of repack_multi form X3
     (N/64, C/16, 18, 64, 8), the 1x1 weights packed with K = 1 (tap 1 of the chunks)."""
     if not (is_x3(x3) and x3.is_cuda and x3.is_contiguous()):
         raise ValueError('conv_x3p_s2_fwd: a contiguous x3 CUDA tensor expected')
@@ -333,7 +333,7 @@ def conv_x3p_s2_fwd(x3, w1pk, wdpk):
 
 def conv_x3p_s2_dgrad(dy1_3, w1pk, dyd_3, wdpk, out=None):
     """dx (rows, 2 Lout, C) fp32 = the data gradients of the two convs of conv_x3p_s2_fwd, summed; dy1_3 / dyd_3 x3
-    activations (rows, Lout, N/16, 3, 16), packs: the DATA-GRADIENT side of repack_multi code 49 (C/64, N/16, 18, 64, 8)."""
+    activations (rows, Lout, N/16, 3, 16), packs: the DATA-GRADIENT side of repack_multi form X3 (C/64, N/16, 18, 64, 8)."""
     for t in (dy1_3, dyd_3):
         if not (is_x3(t) and t.is_cuda and t.is_contiguous()):
             raise ValueError('conv_x3p_s2_dgrad: contiguous x3 CUDA tensors expected')
@@ -572,18 +572,101 @@ def _conv_wgrad_taps(dy, x, src_off, stride):
     return out
 
 
-# DA_WINOGRAD=0: the direct fp32 kernels (the second fp32 implementation the tests compare).  The one switch of every fp32 k3 s1
-# conv path -- forward, data and weight gradients (functional reads it here too) -- under its historical name.
+# ---- which kernel a conv runs on ---------------------------------------------------------------------------------------------
+# Decided HERE and nowhere else, by pure functions of shapes and the switches below.  The names are da_repack_desc.points.
+DIRECT = 0      # fp32 direct kernels (conv_gemm.hip): any shape
+WINO2 = 4       # Winograd F(2,3) of a k3 s1 p1 conv: 2/3 of the direct conv's MFMAs, fp32 throughout
+WINO4 = 6       # F(4,3): 1/2 of them; pays once both channel counts reach WINO4_WGRAD_MIN_C
+BF16 = 16       # operands rounded to bf16, fp32 sums (conv_bf16.hip): k3 s1 p1 convs and the stride-2 block entries
+X3 = 49         # fp32-equivalent products on x3 (pre-split) operands (conv_x3p.hip): the same shapes
+# DA_WINOGRAD=0: the direct kernels on every fp32 k3 s1 conv path (forward, data and weight gradients), under a historical name
 WINOGRAD_WGRAD = os.environ.get('DA_WINOGRAD', '1') != '0'
-WGRAD_BF16 = False        # set by functional.set_conv_dtype('bf16'): k3 s1 weight gradients on the bf16 matrix cores
-WINO4_WGRAD_MIN_C = 512  # channels from which the F(4,3) weight-gradient form replaces F(2,3) (the 512-channel stage, as the forward)
+CONV_DTYPE = 'f32'        # functional.set_conv_dtype: arithmetic of the forward / data gradient ('f32', 'bf16', 'f32x3p')
+WGRAD_BF16 = False        # set with it ('bf16'): the weight gradients on the bf16 matrix cores
+WINO4_WGRAD_MIN_C = 512   # channels from which F(4,3) replaces F(2,3), forward and gradients (scripts/bench_wino.py; DESIGN appendix)
+
+
+def _s2_entry(k, stride, pad):                      # the two convs of a stride-2 block entry: k3 s2 p1, 1x1 s2 downsample
+    return stride == 2 and (k, pad) in ((3, 1), (1, 0))
+
+
+def _mult(n, co, ci):
+    return co % n == 0 and ci % n == 0
+
+
+def _x3_flow():
+    return CONV_DTYPE == 'f32x3p' and ACT == torch.float32
+
+
+def _wino(co, ci):                                  # the fp32 kernel of a k3 s1 p1 conv on float operands
+    return DIRECT if not WINOGRAD_WGRAD else WINO4 if min(co, ci) >= WINO4_WGRAD_MIN_C else WINO2
+
+
+def conv_kernel_wanted(co, ci, k, stride, pad):
+    """The kernel a conv's forward / data gradient asks for from its shape alone: what the block Functions compare."""
+    if CONV_DTYPE == 'bf16' and _mult(64, co, ci) and ((k, stride, pad) == (3, 1, 1) or _s2_entry(k, stride, pad)):
+        return BF16
+    if not ((k, stride, pad) == (3, 1, 1) and _mult(32, co, ci)):
+        return DIRECT
+    return X3 if CONV_DTYPE == 'f32x3p' and _mult(64, co, ci) else _wino(co, ci)
+
+
+def conv_kernel(co, ci, k, stride, pad, x3, l_in):
+    """The kernel ONE forward / data-gradient conv runs on (``x3``: its operand is in the x3 format; ``l_in``: its input side)."""
+    kern = conv_kernel_wanted(co, ci, k, stride, pad)
+    if kern == X3 and not x3:
+        kern = _wino(co, ci)                        # a float operand (a shape without x3 producers): the fp32 kernels
+    if kern == BF16 and stride == 2 and l_in % 2:
+        kern = DIRECT                               # odd length: the fp32 kernel
+    if kern not in (BF16, X3) and ACT == torch.bfloat16:
+        raise NotImplementedError('bf16 activation storage: the conv %s stride %d pad %d has no bf16 kernel (channel counts '
+                                  'must be multiples of 64, stride-2 inputs of even length)' % ((co, ci, k), stride, pad))
+    return kern
+
+
+def step_pack_form(co, ci, k, stride, pad):
+    """The pack form the step's batched repack prepares for a conv module (another form: functional._pack, once a step)."""
+    if _x3_flow() and _s2_entry(k, stride, pad) and _mult(64, co, ci):
+        return X3                                   # the stride-2 block entries on x3 operands (s2_entry_kernel)
+    return conv_kernel_wanted(co, ci, k, stride, pad)
+
+
+def wgrad_kernel(co, ci, k, stride, pad, l, x3=False, operand_form=False):
+    """The kernel of one weight-gradient job on an input of length ``l`` (Winograd needs 64-multiple channel counts here, 32
+    in the forward).  ``operand_form``: the dense-block operand forms, which run on the direct kernels."""
+    fits = _mult(64, co, ci) and ((k, stride, pad) == (3, 1, 1) or (_s2_entry(k, stride, pad) and l % 2 == 0))
+    if x3 and not fits:
+        raise ValueError('conv_wgrad_multi: x3 operands belong to k3 s1 p1 / k3 s2 p1 / k1 s2 p0 (even length) jobs, channels % 64')
+    if operand_form:
+        return DIRECT
+    if x3:
+        return X3
+    if WGRAD_BF16 and fits:
+        return BF16
+    return _wino(co, ci) if fits and stride == 1 else DIRECT
+
+
+def s2_entry_kernel(w1, wd, stride, l_in, x3):
+    """How a block's conv1 (weight shape ``w1``) and downsample conv (``wd`` or None) run: in ONE launch on the X3 (``x3``: the
+    input is in the x3 format), BF16 or DIRECT kernels (a stride-2 entry: the two read the same input), or -- None -- apart."""
+    if wd is None or stride != 2:
+        return None
+    if x3:                                          # even input length, channel counts multiples of 64
+        fits = l_in % 2 == 0 and w1[2] == 3 and tuple(wd) == (w1[0], w1[1], 1) and _mult(64, w1[0], w1[1])
+        return X3 if _x3_flow() and fits else None
+    if conv_kernel_wanted(*w1, 2, 1) != BF16:
+        return DIRECT
+    return BF16 if l_in % 2 == 0 and conv_kernel_wanted(*wd, 2, 0) == BF16 else None
+
+
+def x3_block_ok(rows, l, c, R):
+    """Whether a block on (rows, L, C) activations in windows of R rows has the x3 store forms (single-pass BatchNorm geometry)."""
+    return _x3_flow() and c % 64 == 0 and bn_x3_ok(rows, l, c, R)
 
 
 def conv_wgrad_multi(jobs, dws=None, accumulate=True):
     """jobs: [(dy, x, k, stride, pad)] -> [(slab, splits, k, co, ci)]: every weight-gradient GEMM of the list in
-    one launch per tile shape (slabs only; reduce with wgrad_reduce_multi).  k3 s1 p1 jobs with 64-multiple
-    channel counts take the Winograd F(2,3) form (F(4,3) from WINO4_WGRAD_MIN_C channels), or the bf16-operand kernel
-    while WGRAD_BF16 is set.
+    one launch per tile shape (slabs only; reduce with wgrad_reduce_multi), each on its wgrad_kernel.
     dws (one (co, ci, k) gradient destination per job, or None entries): the slab reductions are chained
     (da_conv_wgrad_multi_reduce) -- every launch of the call carries, as its first blocks, the reduction of the slabs the
     launch before it wrote; -> (slabs, reduced) with reduced[i] False for the jobs whose reduction the caller still owes
@@ -597,11 +680,9 @@ def conv_wgrad_multi(jobs, dws=None, accumulate=True):
         dy, x, k, stride, pad = job[:5]
         extra = job[5] if len(job) > 5 and job[5] else {}         # dense-block operand forms (da_wgrad_job.xform / dy_half)
         both_x3 = is_x3(dy) and is_x3(x)
-        if both_x3:                                   # x3 operands (conv arithmetic 'f32x3p'): the split-bf16 kernels
-            if not (dy.is_cuda and dy.is_contiguous() and x.is_contiguous() and (
-                    (k == 3 and stride == 1 and pad == 1) or
-                    (stride == 2 and x.shape[1] % 2 == 0 and ((k == 3 and pad == 1) or (k == 1 and pad == 0))))):
-                raise ValueError('conv_wgrad_multi: x3 operands belong to k3 s1 p1 / k3 s2 p1 / k1 s2 p0 (even length) jobs')
+        if both_x3:                                   # x3 operands: (rows, L, C/16, 3, 16)
+            if not (dy.is_cuda and dy.is_contiguous() and x.is_contiguous()):
+                raise ValueError('conv_wgrad_multi: x3 operands must be contiguous CUDA tensors')
             rows, lo, co = dy.shape[0], dy.shape[1], dy.shape[2] * 16
             rows2, l, ci = x.shape[0], x.shape[1], x.shape[2] * 16
             lddy, ldx = co, ci
@@ -622,21 +703,11 @@ def conv_wgrad_multi(jobs, dws=None, accumulate=True):
             lo = l
         if rows != rows2 or lo != conv_out_len(l, k, stride, pad) or k > 3 or ci % 32 or co % 32:
             raise ValueError('conv_wgrad_multi: unsupported shape')
-        wino = 1 if (WINOGRAD_WGRAD and k == 3 and stride == 1 and pad == 1 and co % 64 == 0 and ci % 64 == 0) else 0
-        if wino and min(co, ci) >= WINO4_WGRAD_MIN_C:
-            wino = 6                                 # F(4,3) form: 6 contractions over quads instead of 8 over pairs
-        if WGRAD_BF16 and co % 64 == 0 and ci % 64 == 0 and (
-                (k == 3 and stride == 1 and pad == 1) or
-                (stride == 2 and l % 2 == 0 and ((k == 3 and pad == 1) or (k == 1 and pad == 0)))):
-            wino = 16                                # bf16 operands / fp32 sums (conv dtype bf16)
-        if both_x3:
-            if co % 64 or ci % 64:
-                raise ValueError('conv_wgrad_multi: x3 operands need channel counts that are multiples of 64')
-            wino = 49
+        kern = wgrad_kernel(co, ci, k, stride, pad, l, both_x3, bool(extra))
         d.dy, d.x = dy.data_ptr(), x.data_ptr()
         d.rows, d.Lm, d.Ldy, d.lddy, d.N, d.Lx, d.ldx, d.C = rows, lo, ldy_len, lddy, co, l, ldx, ci
         d.dy_stride, d.dy_off, d.src_stride, d.ntaps = 1, 0, stride, k
-        d.winograd = 0 if extra else wino                # (the operand forms run on the direct kernels)
+        d.winograd = 1 if kern == WINO2 else kern        # (da_wgrad_job.winograd: F(2,3) is 1 there)
         if extra:
             if stride != 1:
                 raise ValueError('conv_wgrad_multi: the dense-block operand forms belong to stride-1 jobs')
@@ -728,27 +799,26 @@ def step_tail_multi(items, pgrad, running, accumulate=True, stem=None):
 
 
 def repack_multi(weights, winograd=None):
-    """[(Co,Ci,K) weights] -> [(wf, wd, uf, ud)] with one launch per 32 weights.  winograd[i] (K == 3; True / 4:
-    F(2,3), 6: F(4,3)): emit the Winograd taps uf (points,Co,Ci) / ud (points,Ci,Co) INSTEAD of the direct packs
-    wf / wd (None in the tuple); 16: bf16 tap packs of conv3_bf16 in the uf / ud places; 49: the chunked split-bf16
-    packs of conv3_x3p there."""
+    """[(Co,Ci,K) weights] -> [(wf, wd, uf, ud)] with one launch per 32 weights.  winograd[i]: the kernel the pack is for
+    (DIRECT ... X3 above; True: WINO2).  DIRECT: the direct packs wf / wd; the others, INSTEAD (None in their places), uf / ud:
+    Winograd taps (points,Co,Ci) / (points,Ci,Co), bf16 tap packs of conv3_bf16, chunked split-bf16 packs of conv3_x3p."""
     outs, descs = [], []
     for n, w in enumerate(weights):
         _f32(w, 'w')
         co, ci, k = w.shape
-        code = winograd[n] if winograd is not None else 0
+        code = winograd[n] if winograd is not None else DIRECT
         wino = bool(code)
-        if wino and k != 3 and not (code in (16, 49) and k == 1):
+        if wino and k != 3 and not (code in (BF16, X3) and k == 1):
             raise ValueError('winograd taps need a 3-tap weight')
-        pts = code if wino and code in (6, 16, 49) else 4
+        pts = code if wino and code in (WINO4, BF16, X3) else WINO2
         mk = lambda *shape: torch.empty(shape, device=w.device, dtype=torch.float32)
         wf, wd = (None, None) if wino else (mk(k, co, ci), mk(k, ci, co))
-        if pts == 16:                                # bf16 tap packs (3, Co, Ci) / (3, Ci, Co)
+        if pts == BF16:                              # bf16 tap packs (3, Co, Ci) / (3, Ci, Co)
             if co % 32 or ci % 32:
                 raise ValueError('bf16 tap packs need channel counts that are multiples of 32')
             uf = torch.empty((k, co, ci), device=w.device, dtype=torch.bfloat16)
             ud = torch.empty((k, ci, co), device=w.device, dtype=torch.bfloat16)
-        elif pts == 49:                              # chunked split-bf16 packs of conv3_x3p (18 KB per 64 x 16 chunk)
+        elif pts == X3:                              # chunked split-bf16 packs of conv3_x3p (18 KB per 64 x 16 chunk)
             if co % 64 or ci % 64:
                 raise ValueError('chunked split-bf16 packs need channel counts that are multiples of 64')
             uf = torch.empty((co // 64, ci // 16, 18, 64, 8), device=w.device, dtype=torch.bfloat16)

@@ -89,6 +89,55 @@ def test_model_surface_matches_reference_inventory():
     assert float(r.bn1.weight.min()) == 1.0 and float(r.bn1.bias.abs().max()) == 0.0
 
 
+# Per Conv1d in module order, run-length coded ((wanted forward / data-gradient kernel, form of the step's batched repack,
+# weight-gradient kernel of the float job on an even length -- None: never a conv_wgrad_multi job, more than 3 taps or a
+# channel count off 32), repeat).  Recorded from the decision functions as they stood BEFORE they moved into one block
+# (functional._is_wino / _step_pack_code and the ladder inside hip_ops.conv_wgrad_multi), not from the code under test.
+_STEM3, _STEM1 = ((0, 0, None), 3), ((0, 0, None), 1)
+_RESNET18_F32 = [_STEM3, ((4, 4, 4), 4)] + [((0, 0, 0), 1), ((4, 4, 4), 1), ((0, 0, 0), 1), ((4, 4, 4), 2)] * 2 + \
+    [((0, 0, 0), 1), ((6, 6, 6), 1), ((0, 0, 0), 1), ((6, 6, 6), 2)]
+_RESNET18_X3 = [_STEM3, ((49, 49, 4), 4)] + [((0, 49, 0), 1), ((49, 49, 4), 1), ((0, 49, 0), 1), ((49, 49, 4), 2)] * 2 + \
+    [((0, 49, 0), 1), ((49, 49, 6), 1), ((0, 49, 0), 1), ((49, 49, 6), 2)]
+_DENSENET18_WINO = [_STEM1] + ([((0, 0, 0), 1), ((4, 4, 0), 1)] * 2 + [((0, 0, 0), 1)]) * 4
+_KERNEL_TABLE = {       # (backbone, conv dtype, storage dtype, DA_WINOGRAD)
+    ('resnet18', 'f32', 'f32', True): _RESNET18_F32,
+    ('resnet18', 'f32', 'f32', False): [_STEM3, ((0, 0, 0), 19)],
+    ('resnet18', 'bf16', 'f32', True): [_STEM3, ((16, 16, 16), 19)],
+    ('resnet18', 'bf16', 'bf16', True): [_STEM3, ((16, 16, 16), 19)],
+    ('resnet18', 'f32x3p', 'f32', True): _RESNET18_X3,
+    ('densenet18', 'f32', 'f32', True): _DENSENET18_WINO[:-1],
+    ('densenet18', 'f32', 'f32', False): [_STEM1, ((0, 0, 0), 19)],
+    ('densenet18', 'bf16', 'f32', True): _DENSENET18_WINO[:-1],
+    ('densenet18', 'f32x3p', 'f32', True): _DENSENET18_WINO[:-1],
+}
+
+
+def test_kernel_choice_per_conv_is_pinned():
+    """Which kernel every Conv1d of the two backbones runs on, under each arithmetic, equals the recorded table."""
+    import deepards_amd.models as M
+    from deepards_amd import functional as F, hip_ops as H
+    assert (H.DIRECT, H.WINO2, H.WINO4, H.BF16, H.X3) == (0, 4, 6, 16, 49)      # da_repack_desc.points
+    nets = {'resnet18': M.resnet18(), 'densenet18': M.densenet18()}
+    old = (F.conv_dtype(), H.ACT, H.WINOGRAD_WGRAD, H.WGRAD_BF16)
+    try:
+        for (backbone, dtype, storage, wino), rle in sorted(_KERNEL_TABLE.items()):
+            H.ACT = torch.float32
+            F.set_conv_dtype(dtype)
+            H.ACT = torch.bfloat16 if storage == 'bf16' else torch.float32     # (set_storage_dtype would call the library)
+            H.WINOGRAD_WGRAD = wino
+            got = []
+            for m in nets[backbone].modules():
+                if isinstance(m, torch.nn.Conv1d):
+                    shape = tuple(m.weight.shape) + (m.stride[0], m.padding[0])
+                    job = shape[2] <= 3 and shape[0] % 32 == 0 and shape[1] % 32 == 0
+                    got.append((H.conv_kernel_wanted(*shape), H.step_pack_form(*shape), H.wgrad_kernel(*shape, 56) if job else None))
+            assert got == [row for row, n in rle for _ in range(n)], (backbone, dtype, storage, wino)
+    finally:
+        H.ACT = torch.float32
+        F.set_conv_dtype(old[0])
+        H.ACT, H.WINOGRAD_WGRAD, H.WGRAD_BF16 = old[1:]
+
+
 def _wgrad_job(rows, L, N, C, k, code=0, stride=1, xform=False, dy_half=False):
     """A da_wgrad_job descriptor of Conv1d(C, N, k, stride, pad = k // 2) on rows x L outputs; the plan query dereferences
     nothing, so every operand is one dummy non-null address (the launch's pointer checks) and the workspace stays NULL."""
