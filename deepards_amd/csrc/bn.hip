@@ -11,6 +11,8 @@
 // (second pass L2-hot) -- no E[x^2]-E[x]^2 cancellation.
 #include "common.h"
 
+#include <type_traits>
+
 #define CG 32       // channels per block
 #define SLOTS 32    // position slots per block (256 threads / 8 quads)
 
@@ -837,7 +839,7 @@ __global__ __launch_bounds__(512) void bn_bwd_pair_d2_kernel(const AT* __restric
 // geometry of the single-pass kernels for W windows of Wn positions: channels per block (32, or 16 when 32 would
 // leave CUs without a block or the window too long for one block) and block size; 0: use the two-stage path
 static int g_bn_target_blocks = 256;   // blocks a launch should have before the channel group per block stops shrinking
-static int bn_fused_geometry(int W, int Wn, int C, int* cgb) {
+static int bn_fused_geometry(int W, int Wn, int C, int* cgb = nullptr) {
   if (Wn < 1 || g_bn_two_stage) return 0;
   int nq = 8;                                                  // channel quads per block: 32, 16 or 8 channels
   while (nq > 2 && (Wn > FUSED_NPOS * (1024 / nq) || (long)W * (C / (4 * nq)) < g_bn_target_blocks)) nq >>= 1;
@@ -846,8 +848,47 @@ static int bn_fused_geometry(int W, int Wn, int C, int* cgb) {
   const int mult = 64 / nq;                                  // whole waves
   int P = (Wn + FUSED_NPOS - 1) / FUSED_NPOS;
   P = (P + mult - 1) / mult * mult;
-  *cgb = 4 * nq;
+  if (cgb) *cgb = 4 * nq;
   return nq * P;
+}
+
+// The single-pass launch shape, chosen HERE for every entry point: calls fn(std::integral_constant<int, QB>{}, CH, threads)
+// with the block's channel group CH = 4 << QB (the kernels' compile-time QB) and its size; false: the shape takes the
+// two-stage kernels and nothing was called.  Grid: dim3(W, C / CH).
+template <class F>
+static bool bn_single_pass_launch(int W, int Wn, int C, F&& fn) {
+  int cgb = 0;
+  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
+  if (!threads) return false;
+  if (cgb == 32) fn(std::integral_constant<int, 3>{}, 32, threads);
+  else if (cgb == 16) fn(std::integral_constant<int, 2>{}, 16, threads);
+  else fn(std::integral_constant<int, 1>{}, 8, threads);
+  return true;
+}
+
+// what every forward / backward entry asks of its common arguments: pointers non-null, pitches multiples of 4 (float4 /
+// bf16x4 rows), whole channel groups.  A pitch that does not apply (an x3 operand, an absent gout) is passed as 0.
+static bool bn_fwd_args_ok(const void* x, int ldx, const void* res, int ldr, const float* mean, const float* invstd,
+                           const float* gamma, const float* beta, int C) {
+  return x && mean && invstd && gamma && beta && C % CG == 0 && ldx % 4 == 0 && !(res && ldr % 4);
+}
+static bool bn_bwd_one_ok(const void* x, int ldx, const void* dx, int lddx, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, const float* ds) {
+  return x && dx && mean && invstd && gamma && beta && ds && ldx % 4 == 0 && lddx % 4 == 0;
+}
+static bool bn_bwd_args_ok(const void* dout, int ldd, const void* x, int ldx, const void* dx, int lddx, const void* gout, int ldg,
+                           const float* mean, const float* invstd, const float* gamma, const float* beta, const float* ds, int C) {
+  return dout && ldd % 4 == 0 && !(gout && ldg % 4) && C % CG == 0 && bn_bwd_one_ok(x, ldx, dx, lddx, mean, invstd, gamma, beta, ds);
+}
+
+// ds is [2][W][C]: the window sums of g, then (here) of g * xhat
+static inline float* bn_s2(float* ds, int W, int C) { return ds + (size_t)W * C; }
+
+static BnBwdExt bn_ext_two(const void* dout2, int ldd2) {
+  BnBwdExt ext = {};
+  ext.dout2 = dout2;
+  ext.ldd2 = ldd2;
+  return ext;
 }
 
 // dbeta[c] (+)= sum_w s1[w][c];  dgamma[c] (+)= sum_w s2[w][c] for up to 32 BatchNorms in one launch
@@ -937,11 +978,8 @@ static void launch_bn_bwd_pair(const void* dout, int ldd, const da_bn_bwd_desc* 
   for (int i = 0; i < 2; ++i)
     s[i] = BnBwdOne<AT>{(const AT*)d[i].x, (AT*)d[i].dx, d[i].mean, d[i].invstd, d[i].gamma, d[i].beta, d[i].ds, d[i].ldx, d[i].lddx};
   if (dout2) {
-    BnBwdExt ext = {};
-    ext.dout2 = dout2;
-    ext.ldd2 = ldd2;
     hipLaunchKernelGGL((bn_bwd_pair_d2_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH, 2), dim3(threads), 0, stream, (const AT*)dout,
-                       ldd, s[0], s[1], W, Wn, C, mask, ext);
+                       ldd, s[0], s[1], W, Wn, C, mask, bn_ext_two(dout2, ldd2));
     return;
   }
   hipLaunchKernelGGL((bn_bwd_pair_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH, 2), dim3(threads), 0, stream, (const AT*)dout, ldd,
@@ -1072,8 +1110,7 @@ int da_bn_apply(const void* x, int ldx, const void* res, int ldr, void* out, int
                 float* mean, float* invstd, const float* gamma, const float* beta, int relu, const float* part,
                 float eps, hipStream_t stream) {
   DA_ENTER();
-  if (!x || !out || !mean || !invstd || !gamma || !beta || C % CG || ldx % 4 || ldo % 4 || (res && ldr % 4))
-    return DA_EINVAL;
+  if (!bn_fwd_args_ok(x, ldx, res, ldr, mean, invstd, gamma, beta, C) || !out || ldo % 4) return DA_EINVAL;
   if (W == 0) return DA_OK;
   int chunk = 256;
   int nz = (Wn + chunk - 1) / chunk;
@@ -1093,20 +1130,15 @@ static int bn_fwd_impl(const void* x, int ldx, const void* res, int ldr, void* o
                        float* mean, float* invstd, const float* gamma, const float* beta, int relu, float eps,
                        float* scratch, unsigned long long* mask, hipStream_t stream) {
   DA_ENTER();
-  if (!x || !out || !mean || !invstd || !gamma || !beta || !scratch || C % CG || ldx % 4 || ldo % 4 ||
-      (res && ldr % 4) || Wn < 1)
+  if (!bn_fwd_args_ok(x, ldx, res, ldr, mean, invstd, gamma, beta, C) || !out || ldo % 4 || !scratch || Wn < 1)
     return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  if (int threads = bn_fused_geometry(W, Wn, C, &cgb)) {
-#define BN_FWD_LAUNCH(QB, CH)                                                                                        \
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_fwd_fused_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream, \
-                                     (const AT*)x, ldx, (const AT*)res, ldr, (AT*)out, ldo, Wn, C, gamma, beta, relu, eps,   \
-                                     mean, invstd, mask, C))
-    if (cgb == 32) BN_FWD_LAUNCH(3, 32);
-    else if (cgb == 16) BN_FWD_LAUNCH(2, 16);
-    else BN_FWD_LAUNCH(1, 8);
-#undef BN_FWD_LAUNCH
+  if (bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+        constexpr int QB = decltype(qb)::value;
+        DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_fwd_fused_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,
+                                           (const AT*)x, ldx, (const AT*)res, ldr, (AT*)out, ldo, Wn, C, gamma, beta, relu, eps,
+                                           mean, invstd, mask, C));
+      })) {
     DA_CHECK_LAUNCH();
     return DA_OK;
   }
@@ -1130,28 +1162,25 @@ int da_bn_fwd_x(const float* x, int ldx, const void* res, int ldr, void* out, in
                 int res_x3, int out_x3, hipStream_t stream) {
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;
-  if (!x || !out || !mean || !invstd || !gamma || !beta || C % CG || ldx % 4 || Wn < 1) return DA_EINVAL;
-  if ((!out_x3 && ldo % 4) || (res && !res_x3 && ldr % 4) || ((res_x3 || out_x3) && C % 16)) return DA_EINVAL;
+  if (!bn_fwd_args_ok(x, ldx, res_x3 ? nullptr : res, ldr, mean, invstd, gamma, beta, C) || !out || Wn < 1) return DA_EINVAL;
+  if ((!out_x3 && ldo % 4) || ((res_x3 || out_x3) && C % 16)) return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  if (!threads) return DA_EINVAL;
-  const int rx = res && res_x3 ? 1 : 0, ox = out_x3 ? 1 : 0;
-#define BN_FWDX_LAUNCH(QB, CH, RX, OX)                                                                                  \
-  hipLaunchKernelGGL((bn_fwd_fused_kernel<float, FUSED_NPOS, QB, RX, OX>), dim3(W, C / CH), dim3(threads), 0, stream, x, ldx,   \
-                     (const float*)res, ldr, (float*)out, ldo, Wn, C, gamma, beta, relu, eps, mean, invstd, mask, C)
-#define BN_FWDX_QB(QB, CH)                                  \
-  do {                                                      \
-    if (rx && ox) BN_FWDX_LAUNCH(QB, CH, 1, 1);             \
-    else if (rx) BN_FWDX_LAUNCH(QB, CH, 1, 0);              \
-    else if (ox) BN_FWDX_LAUNCH(QB, CH, 0, 1);              \
-    else BN_FWDX_LAUNCH(QB, CH, 0, 0);                      \
-  } while (0)
-  if (cgb == 32) BN_FWDX_QB(3, 32);
-  else if (cgb == 16) BN_FWDX_QB(2, 16);
-  else BN_FWDX_QB(1, 8);
-#undef BN_FWDX_QB
-#undef BN_FWDX_LAUNCH
+  const bool rx = res && res_x3, ox = out_x3 != 0;
+  const bool single = bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    auto launch = [&](auto rxc, auto oxc) {
+      hipLaunchKernelGGL((bn_fwd_fused_kernel<float, FUSED_NPOS, QB, decltype(rxc)::value, decltype(oxc)::value>), dim3(W, C / CH),
+                         dim3(threads), 0, stream, x, ldx, (const float*)res, ldr, (float*)out, ldo, Wn, C, gamma, beta, relu, eps,
+                         mean, invstd, mask, C);
+    };
+    constexpr std::integral_constant<int, 0> no{};
+    constexpr std::integral_constant<int, 1> yes{};
+    if (rx && ox) launch(yes, yes);
+    else if (rx) launch(yes, no);
+    else if (ox) launch(no, yes);
+    else launch(no, no);
+  });
+  if (!single) return DA_EINVAL;
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -1164,29 +1193,21 @@ int da_bn_bwd_x(const float* dout, int ldd, const float* x, int ldx, void* dx, i
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;
   if (mask) mask_mode = 3;
-  if (!dout || !x || !dx || !mean || !invstd || !gamma || !beta || !ds) return DA_EINVAL;
-  if (C % CG || ldd % 4 || ldx % 4 || (!dx_x3 && lddx % 4) || (dx_x3 && C % 16) || (gout && ldg % 4)) return DA_EINVAL;
+  if (!bn_bwd_args_ok(dout, ldd, x, ldx, dx, dx_x3 ? 0 : lddx, gout, ldg, mean, invstd, gamma, beta, ds, C) || (dx_x3 && C % 16))
+    return DA_EINVAL;
   if (mask_mode != 0 && mask_mode != 1 && mask_mode != 3) return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  if (!threads) return DA_EINVAL;
-  float* s1 = ds;
-  float* s2 = ds + (size_t)W * C;
-#define BN_BWDX_LAUNCH(QB, CH, DX)                                                                                        \
-  hipLaunchKernelGGL((bn_bwd_fused_kernel<float, FUSED_NPOS, QB, DX>), dim3(W, C / CH), dim3(threads), 0, stream, dout, ldd, x,  \
-                     ldx, (const float*)nullptr, 0, (float*)dx, lddx, gout, ldg, Wn, C, mean, invstd, gamma, beta, mask_mode, s1, \
-                     s2, (const float*)nullptr, 0, mask, BnBwdExt{})
-#define BN_BWDX_QB(QB, CH)                       \
-  do {                                           \
-    if (dx_x3) BN_BWDX_LAUNCH(QB, CH, 1);        \
-    else BN_BWDX_LAUNCH(QB, CH, 0);              \
-  } while (0)
-  if (cgb == 32) BN_BWDX_QB(3, 32);
-  else if (cgb == 16) BN_BWDX_QB(2, 16);
-  else BN_BWDX_QB(1, 8);
-#undef BN_BWDX_QB
-#undef BN_BWDX_LAUNCH
+  const bool single = bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    auto launch = [&](auto dxc) {
+      hipLaunchKernelGGL((bn_bwd_fused_kernel<float, FUSED_NPOS, QB, decltype(dxc)::value>), dim3(W, C / CH), dim3(threads), 0, stream,
+                         dout, ldd, x, ldx, (const float*)nullptr, 0, (float*)dx, lddx, gout, ldg, Wn, C, mean, invstd, gamma, beta,
+                         mask_mode, ds, bn_s2(ds, W, C), (const float*)nullptr, 0, mask, BnBwdExt{});
+    };
+    if (dx_x3) launch(std::integral_constant<int, 1>{});
+    else launch(std::integral_constant<int, 0>{});
+  });
+  if (!single) return DA_EINVAL;
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -1214,30 +1235,25 @@ static int bn_bwd_impl(const void* dout, int ldd, const void* x, int ldx, const 
                        hipStream_t stream) {
   DA_ENTER();
   if (mask) mask_mode = 3;
-  if (!dout || !x || !dx || !mean || !invstd || !gamma || !beta || !scratch || !ds) return DA_EINVAL;
+  if (!bn_bwd_args_ok(dout, ldd, x, ldx, dx, lddx, gout, ldg, mean, invstd, gamma, beta, ds, C) || !scratch) return DA_EINVAL;
   if (add && ldadd % 4) return DA_EINVAL;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return DA_EINVAL;
-  if (C % CG || ldd % 4 || ldx % 4 || lddx % 4 || (gout && ldg % 4) || mask_mode < 0 || mask_mode > 3)
-    return DA_EINVAL;
-  if (mask_mode == 2 && (!out || ldo % 4)) return DA_EINVAL;
+  if (mask_mode < 0 || mask_mode > 3 || (mask_mode == 2 && (!out || ldo % 4))) return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int P, chunk;
-  bn_chunks(W, Wn, C, &P, &chunk);
   float* s1 = ds;
-  float* s2 = ds + (size_t)W * C;
-  int cgb = 0;
-  if (int threads = bn_fused_geometry(W, Wn, C, &cgb)) {
-#define BN_BWD_LAUNCH(QB, CH)                                                                                         \
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_fused_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,  \
-                                     (const AT*)dout, ldd, (const AT*)x, ldx, (const AT*)out, ldo, (AT*)dx, lddx, (AT*)gout,  \
-                                     ldg, Wn, C, mean, invstd, gamma, beta, mask_mode, s1, s2, (const AT*)add, ldadd, mask, BnBwdExt{}))
-    if (cgb == 32) BN_BWD_LAUNCH(3, 32);
-    else if (cgb == 16) BN_BWD_LAUNCH(2, 16);
-    else BN_BWD_LAUNCH(1, 8);
-#undef BN_BWD_LAUNCH
+  float* s2 = bn_s2(ds, W, C);
+  if (bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+        constexpr int QB = decltype(qb)::value;
+        DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_fused_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,
+                                           (const AT*)dout, ldd, (const AT*)x, ldx, (const AT*)out, ldo, (AT*)dx, lddx, (AT*)gout,
+                                           ldg, Wn, C, mean, invstd, gamma, beta, mask_mode, s1, s2, (const AT*)add, ldadd, mask,
+                                           BnBwdExt{}));
+      })) {
     DA_CHECK_LAUNCH();
   } else {
     if (mask) return DA_EINVAL;
+    int P, chunk;
+    bn_chunks(W, Wn, C, &P, &chunk);
     DA_ACT_DISPATCH(hipLaunchKernelGGL(bn_bwd_reduce_kernel<AT>, dim3(W, C / CG, P), dim3(256), 0, stream, (const AT*)dout, ldd,
                                        (const AT*)x, ldx, (const AT*)out, ldo, Wn, C, chunk, mean, invstd, gamma, beta,
                                        mask_mode, scratch));
@@ -1264,32 +1280,43 @@ int da_bn_bwd(const void* dout, int ldd, const void* x, int ldx, const void* out
                      scratch, ds, dgamma, dbeta, accumulate, nullptr, 0, nullptr, stream);
 }
 
+// ---- the geometry predicates: "single-pass" is bn_fused_geometry() != 0, each form adds its own clause ----
+// 64-bit words a ReLU mask of da_bn_fwd_mask / da_bn_bwd_mask has for this shape (one per thread of the single-pass
+// kernel); 0: the shape takes the two-stage kernels, no mask form.
+size_t da_bn_mask_words(int W, int Wn, int C) {
+  int cgb = 0;
+  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
+  return threads ? (size_t)W * (C / cgb) * threads : 0;
+}
+
+// the pooled forms below: L | Wn, Wn <= 160 (the block's LDS pool buffer)
+int da_bn_pool_ok(int W, int Wn, int C, int L) {
+  return L >= 1 && Wn % L == 0 && Wn <= BN_POOL_MAX_WN && C % CG == 0 && bn_fused_geometry(W, Wn, C) != 0;
+}
+
+// the two-term forms (da_bn_bwd_mask2 / da_bn_bwd_pair2): at most 512 threads
+int da_bn_two_ok(int W, int Wn, int C) {
+  const int threads = C % CG == 0 ? bn_fused_geometry(W, Wn, C) : 0;
+  return threads > 0 && threads <= 512;
+}
+
 // The block-output BatchNorm of the LAST residual block with the head's global average pool folded in (resnet.py:33-38 into
 // :112,159-160 AvgPool1d(7) + view): da_bn_fwd_mask(relu) whose output is not stored -- flat[W * Wn / L][C] (float) receives the
 // average over the L positions of every row, bit for bit what da_head_fwd pools from the stored map; and its backward,
 // da_bn_bwd_mask with dout = dflat[rows][ldd] (float), the gradient of those pooled features.  Single-pass geometry, L | Wn,
 // Wn <= 160 (da_bn_pool_ok); mask: da_bn_mask_words() words.
-int da_bn_pool_ok(int W, int Wn, int C, int L) {
-  int cgb = 0;
-  return L >= 1 && Wn % L == 0 && Wn <= BN_POOL_MAX_WN && C % CG == 0 && bn_fused_geometry(W, Wn, C, &cgb) != 0;
-}
-
 int da_bn_fwd_pool(const void* x, int ldx, const void* res, int ldr, float* flat, int W, int Wn, int C, int L, float* mean,
                    float* invstd, const float* gamma, const float* beta, float eps, unsigned long long* mask,
                    hipStream_t stream) {
   DA_ENTER();
-  if (!x || !flat || !mean || !invstd || !gamma || !beta || !mask || ldx % 4 || (res && ldr % 4)) return DA_EINVAL;
-  if (!da_bn_pool_ok(W, Wn, C, L)) return DA_EINVAL;
+  if (!bn_fwd_args_ok(x, ldx, res, ldr, mean, invstd, gamma, beta, C) || !flat || !mask || !da_bn_pool_ok(W, Wn, C, L))
+    return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-#define BN_FWDP_LAUNCH(QB, CH)                                                                                            \
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_fwd_pool_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,    \
-                                     (const AT*)x, ldx, (const AT*)res, ldr, Wn, C, gamma, beta, eps, mean, invstd, mask, flat, L))
-  if (cgb == 32) BN_FWDP_LAUNCH(3, 32);
-  else if (cgb == 16) BN_FWDP_LAUNCH(2, 16);
-  else BN_FWDP_LAUNCH(1, 8);
-#undef BN_FWDP_LAUNCH
+  bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_fwd_pool_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,
+                                       (const AT*)x, ldx, (const AT*)res, ldr, Wn, C, gamma, beta, eps, mean, invstd, mask, flat, L));
+  });
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -1298,36 +1325,21 @@ int da_bn_bwd_pool(const float* dflat, int ldd, const void* x, int ldx, void* dx
                    int C, int L, const float* mean, const float* invstd, const float* gamma, const float* beta, float* ds,
                    const unsigned long long* mask, hipStream_t stream) {
   DA_ENTER();
-  if (!dflat || !x || !dx || !mean || !invstd || !gamma || !beta || !ds || !mask || ldd % 4 || ldx % 4 || lddx % 4 ||
-      (gout && ldg % 4))
+  if (!bn_bwd_args_ok(dflat, ldd, x, ldx, dx, lddx, gout, ldg, mean, invstd, gamma, beta, ds, C) || !mask ||
+      !da_bn_pool_ok(W, Wn, C, L))
     return DA_EINVAL;
-  if (!da_bn_pool_ok(W, Wn, C, L)) return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
   BnBwdExt ext = {};
   ext.pool_L = L;
   ext.pool_div = make_fastdiv((uint32_t)L);
-  float* s1 = ds;
-  float* s2 = ds + (size_t)W * C;
-#define BN_BWDP_LAUNCH(QB, CH)                                                                                            \
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_pool_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,    \
-                                     dflat, ldd, (const AT*)x, ldx, (AT*)dx, lddx, (AT*)gout, ldg, Wn, C, mean, invstd, gamma,   \
-                                     beta, s1, s2, mask, ext))
-  if (cgb == 32) BN_BWDP_LAUNCH(3, 32);
-  else if (cgb == 16) BN_BWDP_LAUNCH(2, 16);
-  else BN_BWDP_LAUNCH(1, 8);
-#undef BN_BWDP_LAUNCH
+  bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_pool_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,
+                                       dflat, ldd, (const AT*)x, ldx, (AT*)dx, lddx, (AT*)gout, ldg, Wn, C, mean, invstd, gamma,
+                                       beta, ds, bn_s2(ds, W, C), mask, ext));
+  });
   DA_CHECK_LAUNCH();
   return DA_OK;
-}
-
-// 64-bit words a ReLU mask of da_bn_fwd_mask / da_bn_bwd_mask has for this shape (one per thread of the single-pass
-// kernel); 0: the shape takes the two-stage kernels, no mask form.
-size_t da_bn_mask_words(int W, int Wn, int C) {
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  return threads ? (size_t)W * (C / cgb) * threads : 0;
 }
 
 // da_bn_fwd (relu != 0) that also records the ReLU decisions, 1 bit per element (da_bn_mask_words() words).
@@ -1367,113 +1379,72 @@ int da_bn_fwd_pair(const da_bn_fwd_desc* d, int W, int Wn, int C, float eps, hip
   DA_ENTER();
   if (!d || C % CG || Wn < 1) return DA_EINVAL;
   for (int i = 0; i < 2; ++i)
-    if (!d[i].x || !d[i].out || !d[i].mean || !d[i].invstd || !d[i].gamma || !d[i].beta || d[i].ldx % 4 || d[i].ldo % 4 ||
-        (d[i].res && d[i].ldr % 4) || (d[i].mask && !d[i].relu))
+    if (!bn_fwd_args_ok(d[i].x, d[i].ldx, d[i].res, d[i].ldr, d[i].mean, d[i].invstd, d[i].gamma, d[i].beta, C) || !d[i].out ||
+        d[i].ldo % 4 || (d[i].mask && !d[i].relu))
       return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  if (!threads) return DA_EINVAL;
-#define BN_FWDP_LAUNCH(QB, CH)                                                          \
-  do {                                                                                  \
-    if (g_act_bf16) launch_bn_fwd_pair<__bf16, QB>(d, W, Wn, C, CH, threads, eps, stream); \
-    else launch_bn_fwd_pair<float, QB>(d, W, Wn, C, CH, threads, eps, stream);          \
-  } while (0)
-  if (cgb == 32) BN_FWDP_LAUNCH(3, 32);
-  else if (cgb == 16) BN_FWDP_LAUNCH(2, 16);
-  else BN_FWDP_LAUNCH(1, 8);
-#undef BN_FWDP_LAUNCH
+  const bool single = bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    DA_ACT_DISPATCH((launch_bn_fwd_pair<AT, QB>(d, W, Wn, C, CH, threads, eps, stream)));
+  });
+  if (!single) return DA_EINVAL;
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
 
 // ... and the two backwards that share one masked gradient (the block-output BatchNorm and the downsample's; the ReLU
 // decisions of the block output as the bit mask of da_bn_fwd_mask): dx_i = BatchNorm_i backward of dout * mask, ds_i
-// [2][W][C] the window sums for da_bn_param_grad_multi.  Single-pass geometry only.
-int da_bn_bwd_pair(const void* dout, int ldd, const da_bn_bwd_desc* d, int W, int Wn, int C, const unsigned long long* mask,
-                   hipStream_t stream) {
+// [2][W][C] the window sums for da_bn_param_grad_multi.  Single-pass geometry only.  dout2 != NULL: the two-term form below.
+static int bn_bwd_pair_impl(const void* dout, int ldd, const void* dout2, int ldd2, const da_bn_bwd_desc* d, int W, int Wn, int C,
+                            const unsigned long long* mask, hipStream_t stream) {
   DA_ENTER();
   if (!dout || !d || !mask || C % CG || Wn < 1 || ldd % 4) return DA_EINVAL;
+  if (dout2 && (ldd2 % 4 || !da_bn_two_ok(W, Wn, C))) return DA_EINVAL;
   for (int i = 0; i < 2; ++i)
-    if (!d[i].x || !d[i].dx || !d[i].mean || !d[i].invstd || !d[i].gamma || !d[i].beta || !d[i].ds || d[i].ldx % 4 ||
-        d[i].lddx % 4)
+    if (!bn_bwd_one_ok(d[i].x, d[i].ldx, d[i].dx, d[i].lddx, d[i].mean, d[i].invstd, d[i].gamma, d[i].beta, d[i].ds))
       return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  if (!threads) return DA_EINVAL;
-#define BN_BWDP_LAUNCH(QB, CH)                                                                 \
-  do {                                                                                         \
-    if (g_act_bf16) launch_bn_bwd_pair<__bf16, QB>(dout, ldd, d, W, Wn, C, CH, threads, mask, stream); \
-    else launch_bn_bwd_pair<float, QB>(dout, ldd, d, W, Wn, C, CH, threads, mask, stream);     \
-  } while (0)
-  if (cgb == 32) BN_BWDP_LAUNCH(3, 32);
-  else if (cgb == 16) BN_BWDP_LAUNCH(2, 16);
-  else BN_BWDP_LAUNCH(1, 8);
-#undef BN_BWDP_LAUNCH
+  const bool single = bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    DA_ACT_DISPATCH((launch_bn_bwd_pair<AT, QB>(dout, ldd, d, W, Wn, C, CH, threads, mask, stream, dout2, ldd2)));
+  });
+  if (!single) return DA_EINVAL;
   DA_CHECK_LAUNCH();
   return DA_OK;
+}
+
+int da_bn_bwd_pair(const void* dout, int ldd, const da_bn_bwd_desc* d, int W, int Wn, int C, const unsigned long long* mask,
+                   hipStream_t stream) {
+  return bn_bwd_pair_impl(dout, ldd, nullptr, 0, d, W, Wn, C, mask, stream);
 }
 
 // da_bn_bwd_mask / da_bn_bwd_pair with the upstream gradient given as TWO terms, dout + dout2 (resnet.py:33-38 backward: the
 // gradient of a block's output is the next block's data-gradient conv output plus its identity branch; summing them HERE
 // spares the conv an accumulating epilogue).  Single-pass geometry of at most 512 threads (da_bn_two_ok); ds only (fold
 // dgamma / dbeta with da_bn_param_grad_multi).
-int da_bn_two_ok(int W, int Wn, int C) {
-  int cgb = 0;
-  const int threads = C % CG == 0 ? bn_fused_geometry(W, Wn, C, &cgb) : 0;
-  return threads > 0 && threads <= 512;
-}
-
 int da_bn_bwd_mask2(const void* dout, int ldd, const void* dout2, int ldd2, const void* x, int ldx, void* dx, int lddx, void* gout,
                     int ldg, int W, int Wn, int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
                     float* ds, const unsigned long long* mask, hipStream_t stream) {
   DA_ENTER();
-  if (!dout || !dout2 || !x || !dx || !mean || !invstd || !gamma || !beta || !ds || !mask || ldd % 4 || ldd2 % 4 || ldx % 4 ||
-      lddx % 4 || (gout && ldg % 4) || !da_bn_two_ok(W, Wn, C))
+  if (!bn_bwd_args_ok(dout, ldd, x, ldx, dx, lddx, gout, ldg, mean, invstd, gamma, beta, ds, C) || !dout2 || ldd2 % 4 || !mask ||
+      !da_bn_two_ok(W, Wn, C))
     return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  BnBwdExt ext = {};
-  ext.dout2 = dout2;
-  ext.ldd2 = ldd2;
-  float* s1 = ds;
-  float* s2 = ds + (size_t)W * C;
-#define BN_BWD2_LAUNCH(QB, CH)                                                                                           \
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_d2_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,     \
-                                     (const AT*)dout, ldd, (const AT*)x, ldx, (AT*)dx, lddx, (AT*)gout, ldg, Wn, C, mean,     \
-                                     invstd, gamma, beta, s1, s2, mask, ext))
-  if (cgb == 32) BN_BWD2_LAUNCH(3, 32);
-  else if (cgb == 16) BN_BWD2_LAUNCH(2, 16);
-  else BN_BWD2_LAUNCH(1, 8);
-#undef BN_BWD2_LAUNCH
+  const BnBwdExt ext = bn_ext_two(dout2, ldd2);
+  bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_d2_kernel<AT, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream,
+                                       (const AT*)dout, ldd, (const AT*)x, ldx, (AT*)dx, lddx, (AT*)gout, ldg, Wn, C, mean,
+                                       invstd, gamma, beta, ds, bn_s2(ds, W, C), mask, ext));
+  });
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
 
 int da_bn_bwd_pair2(const void* dout, int ldd, const void* dout2, int ldd2, const da_bn_bwd_desc* d, int W, int Wn, int C,
                     const unsigned long long* mask, hipStream_t stream) {
-  DA_ENTER();
-  if (!dout || !dout2 || !d || !mask || Wn < 1 || ldd % 4 || ldd2 % 4 || !da_bn_two_ok(W, Wn, C)) return DA_EINVAL;
-  for (int i = 0; i < 2; ++i)
-    if (!d[i].x || !d[i].dx || !d[i].mean || !d[i].invstd || !d[i].gamma || !d[i].beta || !d[i].ds || d[i].ldx % 4 ||
-        d[i].lddx % 4)
-      return DA_EINVAL;
-  if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-#define BN_BWDP2_LAUNCH(QB, CH)                                                                              \
-  do {                                                                                                       \
-    if (g_act_bf16) launch_bn_bwd_pair<__bf16, QB>(dout, ldd, d, W, Wn, C, CH, threads, mask, stream, dout2, ldd2); \
-    else launch_bn_bwd_pair<float, QB>(dout, ldd, d, W, Wn, C, CH, threads, mask, stream, dout2, ldd2);      \
-  } while (0)
-  if (cgb == 32) BN_BWDP2_LAUNCH(3, 32);
-  else if (cgb == 16) BN_BWDP2_LAUNCH(2, 16);
-  else BN_BWDP2_LAUNCH(1, 8);
-#undef BN_BWDP2_LAUNCH
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  if (!dout2) return DA_EINVAL;
+  return bn_bwd_pair_impl(dout, ldd, dout2, ldd2, d, W, Wn, C, mask, stream);
 }
 
 // ---- dense-block forms (reference models/densenet.py:18-44,46-66,68-81; float activations, single-pass geometry only) ----
@@ -1484,17 +1455,13 @@ int da_bn_stats_fused(const float* x, int ldx, int W, int Wn, int C, float* mean
   if (g_act_bf16) return DA_EINVAL;
   if (!x || !mean || !invstd || C % CG || ldx % 4 || ldx < C || ldstat % 4 || ldstat < C || Wn < 1) return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  if (!threads) return DA_EINVAL;
-#define BN_STATS_LAUNCH(QB, CH)                                                                                         \
-  hipLaunchKernelGGL((bn_fwd_fused_kernel<float, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream, x, ldx,           \
-                     (const float*)nullptr, 0, (float*)nullptr, 0, Wn, C, (const float*)nullptr, (const float*)nullptr, 0, eps, \
-                     mean, invstd, (unsigned long long*)nullptr, ldstat)
-  if (cgb == 32) BN_STATS_LAUNCH(3, 32);
-  else if (cgb == 16) BN_STATS_LAUNCH(2, 16);
-  else BN_STATS_LAUNCH(1, 8);
-#undef BN_STATS_LAUNCH
+  const bool single = bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    hipLaunchKernelGGL((bn_fwd_fused_kernel<float, FUSED_NPOS, QB>), dim3(W, C / CH), dim3(threads), 0, stream, x, ldx,
+                       (const float*)nullptr, 0, (float*)nullptr, 0, Wn, C, (const float*)nullptr, (const float*)nullptr, 0, eps,
+                       mean, invstd, (unsigned long long*)nullptr, ldstat);
+  });
+  if (!single) return DA_EINVAL;
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -1529,38 +1496,29 @@ int da_bn_bwd_ss(const void* dout, int ldd, const void* x, int ldx, const void* 
                  const float* gamma, const float* beta, int relu, int half_dout, const long long* drop_seed, unsigned drop_salt, float drop_p, int drop_g, float* ds,
                  void* hout, int ldh, hipStream_t stream) {
   DA_ENTER();
-  if (!dout || !x || !dx || !mean || !invstd || !gamma || !beta || !ds) return DA_EINVAL;
+  if (!bn_bwd_args_ok(dout, ldd, x, ldx, dx, lddx, nullptr, 0, mean, invstd, gamma, beta, ds, C)) return DA_EINVAL;
   if (hout && (relu != 1 || ldh % 4 || ldh < C)) return DA_EINVAL;
-  if (C % CG || ldd % 4 || ldx % 4 || lddx % 4 || (add && ldadd % 4) || ldstat % 4 || ldstat < C || Wn < 1) return DA_EINVAL;
+  if ((add && ldadd % 4) || ldstat % 4 || ldstat < C || Wn < 1) return DA_EINVAL;
   if (half_dout && (Wn & 1)) return DA_EINVAL;
   if (relu < 0 || relu > 2 || (relu == 2 && (!out || ldo % 4))) return DA_EINVAL;
   if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && (!drop_seed || drop_g < 4 || drop_g % 4 || drop_g > C))) return DA_EINVAL;
   if (W == 0) return DA_OK;
-  int cgb = 0;
-  const int threads = bn_fused_geometry(W, Wn, C, &cgb);
-  if (!threads) return DA_EINVAL;
   BnBwdExt ext = {};
   ext.ldstat = ldstat; ext.half_dout = half_dout ? 1 : 0; ext.drop_c0 = C - drop_g; ext.drop_g = drop_g;
   ext.seed = drop_seed; ext.salt = drop_salt; ext.p = drop_p; ext.hout = hout; ext.ldh = ldh;
-  float* s1 = ds;
-  float* s2 = ds + (size_t)W * C;
-#define BN_BWDSS_LAUNCH(QB, CH)                                                                                              \
-  do {                                                                                                                              \
-    if (hout)                                                                                                                       \
-      DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_fused_kernel<AT, FUSED_NPOS, QB, 0, 2>), dim3(W, C / CH), dim3(threads), 0, stream, \
-                                         (const AT*)dout, ldd, (const AT*)x, ldx, (const AT*)out, ldo, (AT*)dx, lddx, (AT*)nullptr,  \
-                                         0, Wn, C, mean, invstd, gamma, beta, 4, s1, s2, (const AT*)add, ldadd,                      \
-                                         (const unsigned long long*)nullptr, ext));                                                  \
-    else                                                                                                                            \
-      DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_fused_kernel<AT, FUSED_NPOS, QB, 0, 1>), dim3(W, C / CH), dim3(threads), 0, stream, \
-                                         (const AT*)dout, ldd, (const AT*)x, ldx, (const AT*)out, ldo, (AT*)dx, lddx, (AT*)nullptr,  \
-                                         0, Wn, C, mean, invstd, gamma, beta, relu == 1 ? 4 : (relu == 2 ? 2 : 0), s1, s2,           \
-                                         (const AT*)add, ldadd, (const unsigned long long*)nullptr, ext));                           \
-  } while (0)
-  if (cgb == 32) BN_BWDSS_LAUNCH(3, 32);
-  else if (cgb == 16) BN_BWDSS_LAUNCH(2, 16);
-  else BN_BWDSS_LAUNCH(1, 8);
-#undef BN_BWDSS_LAUNCH
+  const int mask_mode = relu == 1 ? 4 : (relu == 2 ? 2 : 0);   // hout implies relu == 1
+  const bool single = bn_single_pass_launch(W, Wn, C, [&](auto qb, int CH, int threads) {
+    constexpr int QB = decltype(qb)::value;
+    auto launch = [&](auto ssc) {
+      DA_ACT_DISPATCH(hipLaunchKernelGGL((bn_bwd_fused_kernel<AT, FUSED_NPOS, QB, 0, decltype(ssc)::value>), dim3(W, C / CH),
+                                         dim3(threads), 0, stream, (const AT*)dout, ldd, (const AT*)x, ldx, (const AT*)out, ldo,
+                                         (AT*)dx, lddx, (AT*)nullptr, 0, Wn, C, mean, invstd, gamma, beta, mask_mode, ds,
+                                         bn_s2(ds, W, C), (const AT*)add, ldadd, (const unsigned long long*)nullptr, ext));
+    };
+    if (hout) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 1>{});
+  });
+  if (!single) return DA_EINVAL;
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

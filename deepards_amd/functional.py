@@ -231,16 +231,8 @@ def _bn_apply_x(x, R, s, st, gamma, beta, relu, res=None, want_mask=False, out_x
 def _bn_bwd_x(dout, x, R, mean, invstd, gamma, beta, mode, tg, tb, want_g=False, mask=None, dx_x3=True):
     """_bn_bwd through H.bn_bwd_x (dx in the x3 format); -> (dx, dgamma|None, dbeta|None[, g])."""
     dx, g, ds = H.bn_bwd_x(dout, x, R, mean, invstd, gamma, beta, mode, want_g=want_g, mask=mask, dx_x3=dx_x3)
-    direct = tg is not None and tb is not None
-    dg = db = None
-    if direct and _STEP['on']:
-        _STEP['pgrad'].append((ds, tg, tb))
-    elif direct:
-        H.bn_param_grad_multi([(ds, tg, tb)], accumulate=True)
-    else:
-        dg, db = torch.empty_like(gamma), torch.empty_like(beta)
-        H.bn_param_grad_multi([(ds, dg, db)], accumulate=False)
-    return (dx, dg, db, g) if want_g else (dx, dg, db)
+    res = (dx,) + _bn_pgrad(ds, gamma, beta, tg, tb)
+    return res + (g,) if want_g else res
 
 
 # Test instrumentation: with a list here, every block Function appends the post-ReLU activation it stores (float RLC or x3),
@@ -346,16 +338,7 @@ class StemFunction(Function):
                     _plain_writer()
                 dw, ds = H.stem_fused_bwd(dout, x2d, y0, ctx.R, mean, invstd, gamma, beta, ctx.pool_mode, dw=tw,
                                           accumulate=tw is not None)
-            dgamma = dbeta = None
-            if tg is not None and tb is not None:
-                if _STEP['on']:
-                    _STEP['pgrad'].append((ds, tg, tb))
-                else:
-                    _plain_writer()
-                    H.bn_param_grad_multi([(ds, tg, tb)], accumulate=True)
-            else:
-                dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-                H.bn_param_grad_multi([(ds, dgamma, dbeta)], accumulate=False)
+            dgamma, dbeta = _bn_pgrad(ds, gamma, beta, tg, tb)
             return None, None if tw is not None else dw, dgamma, dbeta, None, None, None, None, None
         dz = H.pool_bwd(dout, y0, ctx.R, mean, invstd, gamma, beta, ctx.pool_mode)
         dy0, dgamma, dbeta = _bn_bwd(dz, y0, ctx.R, mean, invstd, gamma, beta, 1, tg, tb, dx=dz)
@@ -415,22 +398,16 @@ class DoubleStemFunction(Function):
 def _bn_bwd(dout, x, R, mean, invstd, gamma, beta, mode, tg, tb, out=None, dx=None, want_g=False, add=None, mask=None):
     """bn_bwd with optional direct gradient destinations; returns (dx, dgamma|None, dbeta|None[, g]).
     add = (tensor, channel offset): that slice is added to dx in the same pass (a concatenation's pass-through)."""
-    direct = tg is not None and tb is not None
-    defer = direct and _STEP['on']
-    if direct and not defer:
-        _plain_writer()
-    dx, dg, db, g, ds = H.bn_bwd(dout, x, R, mean, invstd, gamma, beta, mode, out=out, want_g=want_g, dx=dx,
-                                 dgamma=tg if direct else None, dbeta=tb if direct else None, accumulate=direct,
-                                 defer_param_grads=defer, add=add, mask=mask)
-    if defer:
-        _STEP['pgrad'].append((ds, tg, tb))
-    res = (dx, None if direct else dg, None if direct else db)
+    dx, _, _, g, ds = H.bn_bwd(dout, x, R, mean, invstd, gamma, beta, mode, out=out, want_g=want_g, dx=dx,
+                               defer_param_grads=True, add=add, mask=mask)
+    res = (dx,) + _bn_pgrad(ds, gamma, beta, tg, tb)
     return res + (g,) if want_g else res
 
 
 def _bn_pgrad(ds, gamma, beta, tg, tb):
-    """dgamma / dbeta from a BatchNorm backward's window sums ``ds``: queued for (or run as) the batched fold into the trainer's
-    destinations (-> (None, None)), or returned."""
+    """dgamma / dbeta from a BatchNorm backward's window sums ``ds`` -- the one place that books them: with a trainer's
+    destinations (tg, tb) the fold is queued on the open step's tail launch, or outside a step accumulated into them now
+    (-> (None, None)); without, they are allocated, folded and returned."""
     if tg is not None and tb is not None:
         if _STEP['on']:
             _STEP['pgrad'].append((ds, tg, tb))
@@ -803,15 +780,7 @@ class DenseBlockFunction(Function):
         grads = [None] * len(params)
 
         def fold(ds, gamma, beta, ig, ib):                  # dgamma / dbeta from a BatchNorm backward's window sums
-            if tg[ig] is not None and tg[ib] is not None:
-                if _STEP['on']:
-                    _STEP['pgrad'].append((ds, tg[ig], tg[ib]))
-                else:
-                    _plain_writer()
-                    H.bn_param_grad_multi([(ds, tg[ig], tg[ib])], accumulate=True)
-            else:
-                grads[ig], grads[ib] = torch.empty_like(gamma), torch.empty_like(beta)
-                H.bn_param_grad_multi([(ds, grads[ig], grads[ib])], accumulate=False)
+            grads[ig], grads[ib] = _bn_pgrad(ds, gamma, beta, tg[ig], tg[ib])
 
         last_drop = (seed, salt0 + n_layers - 1, drop_p, G) if drop else None     # the last layer's new channels
         pt = 6 * n_layers

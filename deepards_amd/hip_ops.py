@@ -876,19 +876,87 @@ def stem_conv_wgrad(dy, x, out=None, accumulate=False, k=7, stride=2):
 # ------------------------------------------------------------------------------------------------
 # window-grouped batch norm
 # ------------------------------------------------------------------------------------------------
+def _bn_win(x, R):
+    """-> rows, L, C, W, Wn of a (rows, L, C) tensor in windows of R rows (W windows of Wn = R * L positions)."""
+    rows, l, c = x.shape
+    if R < 1 or rows % R:
+        raise ValueError('rows %d not a multiple of rows_per_window %d' % (rows, R))
+    return rows, l, c, rows // R, R * l
+
+
+def _bn_same(t, shape, what='residual'):
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError('%s shape mismatch' % what)
+
+
+def _bn_stats_pair(w, c, dev):
+    return (torch.empty((w, c), device=dev, dtype=torch.float32), torch.empty((w, c), device=dev, dtype=torch.float32))
+
+
+def _bn_sums(w, c, dev):
+    """ds (2, W, C): the window sums a backward leaves for bn_param_grad_multi."""
+    return torch.empty((2, w, c), device=dev, dtype=torch.float32)
+
+
+def _bn_mask(w, wn, c, dev, empty_ok=False):
+    """The ReLU bit mask of a single-pass forward; a shape on the two-stage kernels has none (None, or with empty_ok a
+    tensor of no words)."""
+    words = _lib.lib().da_bn_mask_words(w, wn, c)
+    return torch.empty((words,), device=dev, dtype=torch.int64) if words or empty_ok else None
+
+
 def _bn_ws(w, wn, c, dev):
     return torch.empty((_lib.lib().da_bn_workspace(w, wn, c) // 4,), device=dev, dtype=torch.float32)
+
+
+# ---- which form a BatchNorm has: every predicate is "single-pass geometry" (a window slab in one block's registers, decided
+# in bn.hip) plus its own clause ----
+def _bn_single(w, wn, c):
+    return _lib.lib().da_bn_mask_words(w, wn, c) > 0
+
+
+def bn_single_pass(w, wn, c):
+    """Whether a BatchNorm over W windows of wn positions x C channels has the single-pass geometry (a window slab in one
+    block's registers): what bn_bwd_ss and the block-fused forms need."""
+    return c % 32 == 0 and _bn_single(w, wn, c)
+
+
+def bn_x3_ok(rows, l, c, R):
+    """Whether the BatchNorm of a (rows, L, C) tensor in windows of R rows has the single-pass geometry the x3 store forms
+    exist for (a window slab fits one block's registers: R * L <= 1280 at the usual channel counts)."""
+    return c % 16 == 0 and rows % R == 0 and _bn_single(rows // R, R * l, c)
+
+
+def dense_fused_ok(rows, R, l, channels):
+    """Whether BatchNorms over (rows, l, C) for every C in ``channels`` have the single-pass geometry the dense-block
+    kernels need (float storage, a window slab in one block's registers, a conv tile within two windows)."""
+    if ACT != torch.float32 or rows % R or R * l < 64:
+        return False
+    return all(bn_single_pass(rows // R, R * l, c) for c in channels)
+
+
+def bn_two_ok(x, R):
+    """Whether bn_bwd_two / bn_bwd_pair(dout2=...) take this (rows, L, C) map (single-pass geometry of at most 512 threads)."""
+    rows, l, c = x.shape
+    return rows % R == 0 and rows > 0 and bool(_lib.lib().da_bn_two_ok(rows // R, R * l, c))
+
+
+def bn_pool_ok(x, R):
+    """Whether bn_fwd_pool / bn_bwd_pool take this (rows, L, C) map with windows of R rows."""
+    rows, l, c = x.shape
+    return rows % R == 0 and rows > 0 and bool(_lib.lib().da_bn_pool_ok(rows // R, R * l, c, l))
+
+
+def bn_debug_two_stage(on):
+    _chk(_lib.lib().da_bn_debug_two_stage(1 if on else 0), 'da_bn_debug_two_stage')
 
 
 def bn_stats_partial(x, R):
     """Stage 1 of the per-window statistics: chunk records part[w][p][{mean,M2}][C] (opaque tensor)."""
     _rlc(x, 'x')
-    rows, l, c = x.shape
-    if rows % R:
-        raise ValueError('rows %d not a multiple of rows_per_window %d' % (rows, R))
-    w = rows // R
-    part = _bn_ws(w, R * l, c, x.device)
-    _chk(_lib.lib().da_bn_stats_partial(_p(x), c, w, R * l, c, _p(part), _stream()), 'da_bn_stats_partial')
+    rows, l, c, w, wn = _bn_win(x, R)
+    part = _bn_ws(w, wn, c, x.device)
+    _chk(_lib.lib().da_bn_stats_partial(_p(x), c, w, wn, c, _p(part), _stream()), 'da_bn_stats_partial')
     return part
 
 
@@ -904,28 +972,24 @@ def bn_stats(x, R, eps=1e-5, running_mean=None, running_var=None, num_batches_tr
     """-> mean, invstd of shape (W, C); window = R rows (standalone form: partial + merge).  With running
     buffers the reference's per-window momentum updates are applied to them in place."""
     part = bn_stats_partial(x, R)
-    rows, l, c = x.shape
-    w = rows // R
-    mean = torch.empty((w, c), device=x.device, dtype=torch.float32)
-    invstd = torch.empty((w, c), device=x.device, dtype=torch.float32)
-    _chk(_lib.lib().da_bn_stats_merge(_p(part), w, R * l, c, eps, _p(mean), _p(invstd), _stream()), 'da_bn_stats_merge')
+    rows, l, c, w, wn = _bn_win(x, R)
+    mean, invstd = _bn_stats_pair(w, c, x.device)
+    _chk(_lib.lib().da_bn_stats_merge(_p(part), w, wn, c, eps, _p(mean), _p(invstd), _stream()), 'da_bn_stats_merge')
     if running_mean is not None:
-        bn_running_multi([(mean, invstd, R * l, running_mean, running_var, num_batches_tracked, momentum, eps)])
+        bn_running_multi([(mean, invstd, wn, running_mean, running_var, num_batches_tracked, momentum, eps)])
     return mean, invstd
 
 
 def bn_apply(x, R, mean, invstd, gamma, beta, relu=True, res=None, out=None, part=None, eps=1e-5):
     """out = act(bn(x) (+res)).  With `part` (bn_stats_partial) mean/invstd are OUTPUTS filled on the way."""
     _rlc(x, 'x')
-    rows, l, c = x.shape
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     if out is None:
         out = torch.empty_like(x)
-    if res is not None and tuple(res.shape) != tuple(x.shape):
-        raise ValueError('residual shape mismatch')
+    _bn_same(res, x.shape)
     if tuple(mean.shape) != (w, c) or tuple(invstd.shape) != (w, c):
         raise ValueError('mean/invstd must be (W, C)')
-    _chk(_lib.lib().da_bn_apply(_p(x), c, _p(res), c, _p(out), c, w, R * l, c, _p(mean), _p(invstd), _p(gamma),
+    _chk(_lib.lib().da_bn_apply(_p(x), c, _p(res), c, _p(out), c, w, wn, c, _p(mean), _p(invstd), _p(gamma),
                                 _p(beta), 1 if relu else 0, _p(part), eps, _stream()), 'da_bn_apply')
     return out
 
@@ -935,27 +999,18 @@ def bn_fwd(x, R, gamma, beta, relu=True, res=None, eps=1e-5, out=None, want_mask
     a window slab fits a block's registers).  want_mask (relu only): -> out, mean, invstd, mask with the ReLU decisions
     as a bit mask for bn_bwd(mask=...) (None when the shape takes the two-stage kernels)."""
     _rlc(x, 'x')
-    rows, l, c = x.shape
-    if rows % R:
-        raise ValueError('rows %d not a multiple of rows_per_window %d' % (rows, R))
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     if out is None:
         out = torch.empty_like(x)
-    if res is not None and tuple(res.shape) != tuple(x.shape):
-        raise ValueError('residual shape mismatch')
-    mean = torch.empty((w, c), device=x.device, dtype=torch.float32)
-    invstd = torch.empty((w, c), device=x.device, dtype=torch.float32)
-    scratch = _bn_ws(w, R * l, c, x.device)
-    mask = None
-    if want_mask and relu:
-        words = _lib.lib().da_bn_mask_words(w, R * l, c)
-        if words:
-            mask = torch.empty((words,), device=x.device, dtype=torch.int64)
+    _bn_same(res, x.shape)
+    mean, invstd = _bn_stats_pair(w, c, x.device)
+    scratch = _bn_ws(w, wn, c, x.device)
+    mask = _bn_mask(w, wn, c, x.device) if want_mask and relu else None
     if mask is not None:
-        _chk(_lib.lib().da_bn_fwd_mask(_p(x), c, _p(res), c, _p(out), c, w, R * l, c, _p(mean), _p(invstd), _p(gamma),
+        _chk(_lib.lib().da_bn_fwd_mask(_p(x), c, _p(res), c, _p(out), c, w, wn, c, _p(mean), _p(invstd), _p(gamma),
                                        _p(beta), eps, _p(scratch), _p(mask), _stream()), 'da_bn_fwd_mask')
     else:
-        _chk(_lib.lib().da_bn_fwd(_p(x), c, _p(res), c, _p(out), c, w, R * l, c, _p(mean), _p(invstd), _p(gamma), _p(beta),
+        _chk(_lib.lib().da_bn_fwd(_p(x), c, _p(res), c, _p(out), c, w, wn, c, _p(mean), _p(invstd), _p(gamma), _p(beta),
                                   1 if relu else 0, eps, _p(scratch), _stream()), 'da_bn_fwd')
     return (out, mean, invstd, mask) if want_mask else (out, mean, invstd)
 
@@ -967,33 +1022,22 @@ def bn_fwd_pair(items, R, eps=1e-5):
     (x0, x1) = items[0][0], items[1][0]
     _rlc(x0, 'x')
     _rlc(x1, 'x')
-    rows, l, c = x0.shape
-    if len(items) != 2 or tuple(x1.shape) != (rows, l, c) or rows % R:
-        raise ValueError('bn_fwd_pair: two tensors of one (rows, L, C) shape, rows a multiple of rows_per_window')
-    w = rows // R
-    L = _lib.lib()
-    words = L.da_bn_mask_words(w, R * l, c)
+    if len(items) != 2 or tuple(x1.shape) != tuple(x0.shape):
+        raise ValueError('bn_fwd_pair: two tensors of one (rows, L, C) shape')
+    rows, l, c, w, wn = _bn_win(x0, R)
     arr = (_lib.BnFwdDesc * 2)()
     outs = []
     for d, (x, gamma, beta, relu, res, want_mask) in zip(arr, items):
-        if res is not None and tuple(res.shape) != (rows, l, c):
-            raise ValueError('residual shape mismatch')
+        _bn_same(res, x0.shape)
         out = torch.empty_like(x)
-        mean = torch.empty((w, c), device=x.device, dtype=torch.float32)
-        invstd = torch.empty((w, c), device=x.device, dtype=torch.float32)
-        mask = torch.empty((words,), device=x.device, dtype=torch.int64) if (want_mask and relu and words) else None
+        mean, invstd = _bn_stats_pair(w, c, x.device)
+        mask = _bn_mask(w, wn, c, x.device) if want_mask and relu else None
         d.x, d.ldx, d.res, d.ldr, d.out, d.ldo = x.data_ptr(), c, (res.data_ptr() if res is not None else None), c, out.data_ptr(), c
         d.mean, d.invstd, d.gamma, d.beta = mean.data_ptr(), invstd.data_ptr(), _f32(gamma).data_ptr(), _f32(beta).data_ptr()
         d.relu, d.mask = (1 if relu else 0), (mask.data_ptr() if mask is not None else None)
         outs.append((out, mean, invstd, mask))
-    _chk(L.da_bn_fwd_pair(arr, w, R * l, c, eps, _stream()), 'da_bn_fwd_pair')
+    _chk(_lib.lib().da_bn_fwd_pair(arr, w, wn, c, eps, _stream()), 'da_bn_fwd_pair')
     return outs
-
-
-def bn_two_ok(x, R):
-    """Whether bn_bwd_two / bn_bwd_pair(dout2=...) take this (rows, L, C) map (single-pass geometry of at most 512 threads)."""
-    rows, l, c = x.shape
-    return rows % R == 0 and rows > 0 and bool(_lib.lib().da_bn_two_ok(rows // R, R * l, c))
 
 
 def bn_bwd_two(dout, dout2, x, R, mean, invstd, gamma, beta, mask, want_g=False, dx=None):
@@ -1002,15 +1046,14 @@ def bn_bwd_two(dout, dout2, x, R, mean, invstd, gamma, beta, mask, want_g=False,
     _rlc(dout, 'dout')
     _rlc(dout2, 'dout2')
     _rlc(x, 'x')
-    rows, l, c = x.shape
-    if tuple(dout.shape) != (rows, l, c) or tuple(dout2.shape) != (rows, l, c) or not bn_two_ok(x, R):
+    if tuple(dout.shape) != tuple(x.shape) or tuple(dout2.shape) != tuple(x.shape) or not bn_two_ok(x, R):
         raise ValueError('bn_bwd_two: shapes dout%s dout2%s x%s' % (tuple(dout.shape), tuple(dout2.shape), tuple(x.shape)))
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     if dx is None:
         dx = torch.empty_like(x)
     g = torch.empty_like(x) if want_g else None
-    ds = torch.empty((2, w, c), device=x.device, dtype=torch.float32)
-    _chk(_lib.lib().da_bn_bwd_mask2(_p(dout), c, _p(dout2), c, _p(x), c, _p(dx), c, _p(g), c, w, R * l, c, _p(mean), _p(invstd),
+    ds = _bn_sums(w, c, x.device)
+    _chk(_lib.lib().da_bn_bwd_mask2(_p(dout), c, _p(dout2), c, _p(x), c, _p(dx), c, _p(g), c, w, wn, c, _p(mean), _p(invstd),
                                     _p(_f32(gamma)), _p(_f32(beta)), _p(ds), _p(mask), _stream()), 'da_bn_bwd_mask2')
     return dx, g, ds
 
@@ -1020,56 +1063,42 @@ def bn_bwd_pair(dout, items, R, mask, dout2=None):
     BatchNorm; ``mask``: the ReLU bit mask of the block output's bn_fwd(want_mask=True)) in one launch: items = two
     (x, mean, invstd, gamma, beta, dx | None) -> [(dx, ds (2, W, C))].  dout2: the upstream gradient is dout + dout2."""
     _rlc(dout, 'dout')
-    rows, l, c = dout.shape
-    if len(items) != 2 or rows % R or mask is None:
-        raise ValueError('bn_bwd_pair: two items, rows a multiple of rows_per_window, a ReLU bit mask')
-    w = rows // R
+    if len(items) != 2 or mask is None:
+        raise ValueError('bn_bwd_pair: two items and a ReLU bit mask')
+    rows, l, c, w, wn = _bn_win(dout, R)
     arr = (_lib.BnBwdDesc * 2)()
     outs = []
     for d, (x, mean, invstd, gamma, beta, dx) in zip(arr, items):
         _rlc(x, 'x')
-        if tuple(x.shape) != (rows, l, c):
-            raise ValueError('bn_bwd_pair: shape mismatch')
+        _bn_same(x, dout.shape, 'bn_bwd_pair: x')
         if dx is None:
             dx = torch.empty_like(x)
-        ds = torch.empty((2, w, c), device=x.device, dtype=torch.float32)
+        ds = _bn_sums(w, c, x.device)
         d.x, d.ldx, d.dx, d.lddx = x.data_ptr(), c, dx.data_ptr(), c
         d.mean, d.invstd, d.gamma, d.beta, d.ds = mean.data_ptr(), invstd.data_ptr(), _f32(gamma).data_ptr(), _f32(beta).data_ptr(), ds.data_ptr()
         outs.append((dx, ds))
     if dout2 is not None:
         _rlc(dout2, 'dout2')
-        if tuple(dout2.shape) != (rows, l, c):
-            raise ValueError('bn_bwd_pair: dout2 shape mismatch')
-        _chk(_lib.lib().da_bn_bwd_pair2(_p(dout), c, _p(dout2), c, arr, w, R * l, c, _p(mask), _stream()), 'da_bn_bwd_pair2')
+        _bn_same(dout2, dout.shape, 'bn_bwd_pair: dout2')
+        _chk(_lib.lib().da_bn_bwd_pair2(_p(dout), c, _p(dout2), c, arr, w, wn, c, _p(mask), _stream()), 'da_bn_bwd_pair2')
     else:
-        _chk(_lib.lib().da_bn_bwd_pair(_p(dout), c, arr, w, R * l, c, _p(mask), _stream()), 'da_bn_bwd_pair')
+        _chk(_lib.lib().da_bn_bwd_pair(_p(dout), c, arr, w, wn, c, _p(mask), _stream()), 'da_bn_bwd_pair')
     return outs
-
-
-def bn_x3_ok(rows, l, c, R):
-    """Whether the BatchNorm of a (rows, L, C) tensor in windows of R rows has the single-pass geometry the x3 store forms
-    exist for (a window slab fits one block's registers: R * L <= 1280 at the usual channel counts)."""
-    return c % 16 == 0 and rows % R == 0 and _lib.lib().da_bn_mask_words(rows // R, R * l, c) > 0
 
 
 def bn_fwd_x(x, R, gamma, beta, relu=True, res=None, eps=1e-5, want_mask=False, out_x3=True):
     """bn_fwd on float activations whose output (out_x3) and / or residual (an x3 tensor) are in the x3 format: the
     producers of the k3 s1 convs' operands under conv arithmetic 'f32x3'.  -> out, mean, invstd[, mask]."""
     _rlc32(x, 'x')
-    rows, l, c = x.shape
-    if rows % R:
-        raise ValueError('rows %d not a multiple of rows_per_window %d' % (rows, R))
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     res_x3 = is_x3(res)
-    if res is not None and (tuple(res.shape) != ((rows, l, c // 16, 3, 16) if res_x3 else (rows, l, c)) or not res.is_contiguous()):
+    _bn_same(res, (rows, l, c // 16, 3, 16) if res_x3 else (rows, l, c))
+    if res is not None and not res.is_contiguous():
         raise ValueError('residual shape mismatch')
     out = x3_empty(rows, l, c, x.device) if out_x3 else torch.empty_like(x)
-    mean = torch.empty((w, c), device=x.device, dtype=torch.float32)
-    invstd = torch.empty((w, c), device=x.device, dtype=torch.float32)
-    mask = None
-    if want_mask and relu:
-        mask = torch.empty((_lib.lib().da_bn_mask_words(w, R * l, c),), device=x.device, dtype=torch.int64)
-    _chk(_lib.lib().da_bn_fwd_x(_p(x), c, _p(res), c, _p(out), c, w, R * l, c, _p(mean), _p(invstd), _p(gamma), _p(beta),
+    mean, invstd = _bn_stats_pair(w, c, x.device)
+    mask = _bn_mask(w, wn, c, x.device, empty_ok=True) if want_mask and relu else None
+    _chk(_lib.lib().da_bn_fwd_x(_p(x), c, _p(res), c, _p(out), c, w, wn, c, _p(mean), _p(invstd), _p(gamma), _p(beta),
                                 1 if relu else 0, eps, _p(mask), 1 if res_x3 else 0, 1 if out_x3 else 0, _stream()),
          'da_bn_fwd_x')
     return (out, mean, invstd, mask) if want_mask else (out, mean, invstd)
@@ -1080,18 +1109,13 @@ def bn_bwd_x(dout, x, R, mean, invstd, gamma, beta, mask_mode, want_g=False, mas
     (fold ds with bn_param_grad_multi).  -> dx, g (float, only when want_g), ds."""
     _rlc32(dout, 'dout')
     _rlc32(x, 'x')
-    rows, l, c = x.shape
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     dx = x3_empty(rows, l, c, x.device) if dx_x3 else torch.empty_like(x)
     g = torch.empty_like(x) if want_g else None
-    ds = torch.empty((2, w, c), device=x.device, dtype=torch.float32)
-    _chk(_lib.lib().da_bn_bwd_x(_p(dout), c, _p(x), c, _p(dx), c, _p(g), c, w, R * l, c, _p(mean), _p(invstd), _p(gamma),
+    ds = _bn_sums(w, c, x.device)
+    _chk(_lib.lib().da_bn_bwd_x(_p(dout), c, _p(x), c, _p(dx), c, _p(g), c, w, wn, c, _p(mean), _p(invstd), _p(gamma),
                                 _p(beta), mask_mode, _p(ds), _p(mask), 1 if dx_x3 else 0, _stream()), 'da_bn_bwd_x')
     return dx, g, ds
-
-
-def bn_debug_two_stage(on):
-    _chk(_lib.lib().da_bn_debug_two_stage(1 if on else 0), 'da_bn_debug_two_stage')
 
 
 def bn_bwd(dout, x, R, mean, invstd, gamma, beta, mask_mode, out=None, want_g=False, dx=None,
@@ -1101,43 +1125,33 @@ def bn_bwd(dout, x, R, mean, invstd, gamma, beta, mask_mode, out=None, want_g=Fa
     add = (tensor (rows, L, Ca >= C), channel offset): dx += tensor[:, :, off:off+C] in the same pass."""
     _rlc(dout, 'dout')
     _rlc(x, 'x')
-    rows, l, c = x.shape
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     if dx is None:
         dx = torch.empty_like(x)
     g = torch.empty_like(x) if want_g else None
     if not defer_param_grads and dgamma is None:
         dgamma = torch.empty((c,), device=x.device, dtype=torch.float32)
         dbeta = torch.empty((c,), device=x.device, dtype=torch.float32)
-    scratch = _bn_ws(w, R * l, c, x.device)
-    ds = torch.empty((2, w, c), device=x.device, dtype=torch.float32)
-    args = (_p(dout), c, _p(x), c, _p(out), c, _p(dx), c, _p(g), c, w, R * l, c, _p(mean),
-            _p(invstd), _p(gamma), _p(beta), mask_mode, _p(scratch), _p(ds),
-            None if defer_param_grads else _p(dgamma), None if defer_param_grads else _p(dbeta),
-            1 if accumulate else 0)
+    scratch = _bn_ws(w, wn, c, x.device)
+    ds = _bn_sums(w, c, x.device)
+    head = (_p(dout), c, _p(x), c)
+    tail = (_p(dx), c, _p(g), c, w, wn, c, _p(mean), _p(invstd), _p(gamma), _p(beta))
+    pgrad = (_p(scratch), _p(ds), None if defer_param_grads else _p(dgamma), None if defer_param_grads else _p(dbeta),
+             1 if accumulate else 0)
     if mask is not None:          # ReLU decisions from bn_fwd(want_mask=True) instead of reading `out`
         if add is not None:
             raise ValueError('bn_bwd: mask and add are exclusive')
-        _chk(_lib.lib().da_bn_bwd_mask(_p(dout), c, _p(x), c, _p(dx), c, _p(g), c, w, R * l, c, _p(mean), _p(invstd),
-                                       _p(gamma), _p(beta), _p(scratch), _p(ds),
-                                       None if defer_param_grads else _p(dgamma), None if defer_param_grads else _p(dbeta),
-                                       1 if accumulate else 0, _p(mask), _stream()), 'da_bn_bwd_mask')
+        _chk(_lib.lib().da_bn_bwd_mask(*head, *tail, *pgrad, _p(mask), _stream()), 'da_bn_bwd_mask')
     elif add is None:
-        _chk(_lib.lib().da_bn_bwd(*args, _stream()), 'da_bn_bwd')
+        _chk(_lib.lib().da_bn_bwd(*head, _p(out), c, *tail, mask_mode, *pgrad, _stream()), 'da_bn_bwd')
     else:
         at, off = add
         _rlc(at, 'add')
         if tuple(at.shape[:2]) != (rows, l) or off % 4 or off + c > at.shape[2]:
             raise ValueError('bn_bwd: bad add operand')
         ap = ctypes.c_void_p(at.data_ptr() + 4 * off)
-        _chk(_lib.lib().da_bn_bwd_add(*args, ap, at.shape[2], _stream()), 'da_bn_bwd_add')
+        _chk(_lib.lib().da_bn_bwd_add(*head, _p(out), c, *tail, mask_mode, *pgrad, ap, at.shape[2], _stream()), 'da_bn_bwd_add')
     return dx, dgamma, dbeta, g, ds
-
-
-def bn_pool_ok(x, R):
-    """Whether bn_fwd_pool / bn_bwd_pool take this (rows, L, C) map with windows of R rows."""
-    rows, l, c = x.shape
-    return rows % R == 0 and rows > 0 and bool(_lib.lib().da_bn_pool_ok(rows // R, R * l, c, l))
 
 
 def bn_fwd_pool(x, R, gamma, beta, res=None, eps=1e-5):
@@ -1145,16 +1159,14 @@ def bn_fwd_pool(x, R, gamma, beta, res=None, eps=1e-5):
     head_fwd / global_avgpool_fwd pool from the stored map, bit for bit), mean, invstd (W, C), mask (the ReLU decisions for
     bn_bwd_pool).  The block-output BatchNorm of the last residual block in front of the head."""
     _rlc(x, 'x')
-    rows, l, c = x.shape
     if not bn_pool_ok(x, R):
         raise ValueError('bn_fwd_pool: shape %s / R %d has no pooled form' % (tuple(x.shape), R))
-    if res is not None and tuple(res.shape) != tuple(x.shape):
-        raise ValueError('residual shape mismatch')
-    w = rows // R
-    mk = lambda *sh: torch.empty(sh, device=x.device, dtype=torch.float32)
-    flat, mean, invstd = mk(rows, c), mk(w, c), mk(w, c)
-    mask = torch.empty((_lib.lib().da_bn_mask_words(w, R * l, c),), device=x.device, dtype=torch.int64)
-    _chk(_lib.lib().da_bn_fwd_pool(_p(x), c, _p(res), c, _p(flat), w, R * l, c, l, _p(mean), _p(invstd), _p(_f32(gamma)),
+    rows, l, c, w, wn = _bn_win(x, R)
+    _bn_same(res, x.shape)
+    flat = torch.empty((rows, c), device=x.device, dtype=torch.float32)
+    mean, invstd = _bn_stats_pair(w, c, x.device)
+    mask = _bn_mask(w, wn, c, x.device)
+    _chk(_lib.lib().da_bn_fwd_pool(_p(x), c, _p(res), c, _p(flat), w, wn, c, l, _p(mean), _p(invstd), _p(_f32(gamma)),
                                    _p(_f32(beta)), eps, _p(mask), _stream()), 'da_bn_fwd_pool')
     return flat, mean, invstd, mask
 
@@ -1164,15 +1176,14 @@ def bn_bwd_pool(dflat, x, R, mean, invstd, gamma, beta, mask, want_g=False, dx=N
     gradient, activation storage type; only with want_g), ds (2, W, C)."""
     _rlc(x, 'x')
     _f32(dflat, 'dflat')
-    rows, l, c = x.shape
-    if tuple(dflat.shape) != (rows, c) or not bn_pool_ok(x, R):
+    if tuple(dflat.shape) != (x.shape[0], x.shape[2]) or not bn_pool_ok(x, R):
         raise ValueError('bn_bwd_pool: shapes dflat%s x%s' % (tuple(dflat.shape), tuple(x.shape)))
-    w = rows // R
+    rows, l, c, w, wn = _bn_win(x, R)
     if dx is None:
         dx = torch.empty_like(x)
     g = torch.empty_like(x) if want_g else None
-    ds = torch.empty((2, w, c), device=x.device, dtype=torch.float32)
-    _chk(_lib.lib().da_bn_bwd_pool(_p(dflat), c, _p(x), c, _p(dx), c, _p(g), c, w, R * l, c, l, _p(mean), _p(invstd),
+    ds = _bn_sums(w, c, x.device)
+    _chk(_lib.lib().da_bn_bwd_pool(_p(dflat), c, _p(x), c, _p(dx), c, _p(g), c, w, wn, c, l, _p(mean), _p(invstd),
                                    _p(_f32(gamma)), _p(_f32(beta)), _p(ds), _p(mask), _stream()), 'da_bn_bwd_pool')
     return dx, g, ds
 
@@ -1194,31 +1205,21 @@ def bn_param_grad_multi(items, accumulate=True):
 # the dense block as one design (include/deepards_hip.h "the dense block as one design"): a pitched buffer per block, one
 # pitched statistics table per block, relu(norm1(x)) never stored
 # ------------------------------------------------------------------------------------------------
-def bn_single_pass(w, wn, c):
-    """Whether a BatchNorm over W windows of wn positions x C channels has the single-pass geometry (a window slab in one
-    block's registers): what bn_bwd_ss and the block-fused forms need."""
-    return c % 32 == 0 and _lib.lib().da_bn_mask_words(w, wn, c) > 0
-
-
-def dense_fused_ok(rows, R, l, channels):
-    """Whether BatchNorms over (rows, l, C) for every C in ``channels`` have the single-pass geometry the dense-block
-    kernels need (float storage, a window slab in one block's registers, a conv tile within two windows)."""
-    if ACT != torch.float32 or rows % R or R * l < 64:
-        return False
-    L = _lib.lib()
-    return all(c % 32 == 0 and L.da_bn_mask_words(rows // R, R * l, c) > 0 for c in channels)
+def _bn_stat_slices(mean_v, invstd_v, w, c, who):
+    """-> the pitch of the (W, C) slices mean_v / invstd_v of a block's statistics tables (one pitch for both)."""
+    ldstat = _sv(mean_v, w, c, 'mean')
+    if _sv(invstd_v, w, c, 'invstd') != ldstat:
+        raise ValueError('%s: bad statistics slices' % who)
+    return ldstat
 
 
 def bn_stats_fused(xv, R, mean_v, invstd_v, eps=1e-5):
     """Per-window statistics of the channel slice xv (rows, L, C) of a pitched buffer, written into the (W, C) slices
     mean_v / invstd_v of the block's statistics tables."""
     ldx = _pv(xv, 'x')
-    rows, l, c = xv.shape
-    w = rows // R
-    ldstat = _sv(mean_v, w, c, 'mean')
-    if rows % R or _sv(invstd_v, w, c, 'invstd') != ldstat:
-        raise ValueError('bn_stats_fused: bad statistics slices')
-    _chk(_lib.lib().da_bn_stats_fused(_p(xv), ldx, w, R * l, c, _p(mean_v), _p(invstd_v), ldstat, eps, _stream()),
+    rows, l, c, w, wn = _bn_win(xv, R)
+    ldstat = _bn_stat_slices(mean_v, invstd_v, w, c, 'bn_stats_fused')
+    _chk(_lib.lib().da_bn_stats_fused(_p(xv), ldx, w, wn, c, _p(mean_v), _p(invstd_v), ldstat, eps, _stream()),
          'da_bn_stats_fused')
 
 
@@ -1226,13 +1227,10 @@ def bn_relu_ss(xv, R, mean_v, invstd_v, gamma, beta):
     """relu(norm(xv)) in the fused-multiply-add form the dense-block kernels apply on the fly -> contiguous (rows, L, C)
     (tests / explainers: the hot path never stores it)."""
     ldx = _pv(xv, 'x')
-    rows, l, c = xv.shape
-    w = rows // R
-    ldstat = _sv(mean_v, w, c, 'mean')
-    if rows % R or _sv(invstd_v, w, c, 'invstd') != ldstat:
-        raise ValueError('bn_relu_ss: bad statistics slices')
+    rows, l, c, w, wn = _bn_win(xv, R)
+    ldstat = _bn_stat_slices(mean_v, invstd_v, w, c, 'bn_relu_ss')
     out = torch.empty((rows, l, c), device=xv.device, dtype=torch.float32)
-    _chk(_lib.lib().da_bn_relu_ss(_p(xv), ldx, _p(out), c, w, R * l, c, _p(mean_v), _p(invstd_v), ldstat, _p(_f32(gamma)),
+    _chk(_lib.lib().da_bn_relu_ss(_p(xv), ldx, _p(out), c, w, wn, c, _p(mean_v), _p(invstd_v), ldstat, _p(_f32(gamma)),
                                   _p(_f32(beta)), _stream()), 'da_bn_relu_ss')
     return out
 
@@ -1247,18 +1245,13 @@ def bn_bwd_ss(dout, xv, R, mean_v, invstd_v, gamma, beta, relu, dx, add=None, ha
     (bf16: contiguous tensors)."""
     _ld = _pv if ACT == torch.float32 else (lambda t, name: _rlc(t, name).shape[2])
     ldd, ldx, lddx = _ld(dout, 'dout'), _ld(xv, 'x'), _ld(dx, 'dx')
-    rows, l, c = xv.shape
-    w = rows // R
-    if rows % R or tuple(dx.shape) != (rows, l, c) or tuple(dout.shape) != (rows, l // 2 if half_dout else l, c) or \
-            (half_dout and l % 2):
+    rows, l, c, w, wn = _bn_win(xv, R)
+    if tuple(dx.shape) != (rows, l, c) or tuple(dout.shape) != (rows, l // 2 if half_dout else l, c) or (half_dout and l % 2):
         raise ValueError('bn_bwd_ss: shape mismatch x%s dout%s dx%s' % (tuple(xv.shape), tuple(dout.shape), tuple(dx.shape)))
-    ldstat = _sv(mean_v, w, c, 'mean')
-    if _sv(invstd_v, w, c, 'invstd') != ldstat:
-        raise ValueError('bn_bwd_ss: bad statistics slices')
+    ldstat = _bn_stat_slices(mean_v, invstd_v, w, c, 'bn_bwd_ss')
     ldadd = 0
     if add is not None:
-        if tuple(add.shape) != (rows, l, c):
-            raise ValueError('bn_bwd_ss: bad add operand')
+        _bn_same(add, xv.shape, 'bn_bwd_ss: add')
         ldadd = _ld(add, 'add')
     seed, salt, p, g = drop if drop is not None else (None, 0, 0.0, 0)
     ldo = ldh = 0
@@ -1270,9 +1263,9 @@ def bn_bwd_ss(dout, xv, R, mean_v, invstd_v, gamma, beta, relu, dx, add=None, ha
         if relu != 1 or tuple(hout.shape) != (rows, l, c):
             raise ValueError('bn_bwd_ss: hout is the (rows, L, C) activation of the relu = 1 form')
         ldh = _ld(hout, 'hout')
-    ds = torch.empty((2, w, c), device=xv.device, dtype=torch.float32)
+    ds = _bn_sums(w, c, xv.device)
     _chk(_lib.lib().da_bn_bwd_ss(_p(dout), ldd, _p(xv), ldx, _p(out) if relu == 2 else None, ldo, _p(dx), lddx, _p(add), ldadd, w,
-                                 R * l, c, _p(mean_v), _p(invstd_v), ldstat, _p(_f32(gamma)), _p(_f32(beta)), int(relu), 1 if half_dout else 0,
+                                 wn, c, _p(mean_v), _p(invstd_v), ldstat, _p(_f32(gamma)), _p(_f32(beta)), int(relu), 1 if half_dout else 0,
                                  _p(seed) if p > 0 else None, salt, p, g, _p(ds), _p(hout), ldh, _stream()), 'da_bn_bwd_ss')
     return ds
 

@@ -138,6 +138,114 @@ def test_kernel_choice_per_conv_is_pinned():
         H.ACT, H.WINOGRAD_WGRAD, H.WGRAD_BF16 = old[1:]
 
 
+# The BatchNorm host queries on the (L, C) maps of the two backbones (windows of 20 rows: Wn = 20 L), per batch size
+# W = 16, 64, 128.  _BN_GEOMETRY[target blocks][shape][batch] = (da_bn_mask_words / W -- the single-pass kernel's threads per
+# window, da_bn_two_ok, da_bn_pool_ok(L)); _BN_CHUNKS[shape][batch] = (P, chunk) of da_bn_chunks.  Recorded from the library
+# as it stood BEFORE the entry points' launch shapes moved into bn_single_pass_launch, not from the code under test.
+_BN_SHAPES = [(112, 64), (56, 64), (56, 96), (56, 128), (28, 64), (28, 96), (28, 128), (14, 64), (14, 96), (14, 128), (14, 256),
+              (7, 64), (7, 96), (7, 128), (7, 512)]
+_BN_GEOMETRY = {
+    256: [
+        [(3584, 0, 0), (3584, 0, 0), (3584, 0, 0)],
+        [(1792, 1, 0), (1792, 1, 0), (1792, 0, 0)],
+        [(2688, 1, 0), (2688, 1, 0), (2688, 0, 0)],
+        [(3584, 1, 0), (3584, 0, 0), (3584, 0, 0)],
+        [(1024, 1, 0), (1024, 1, 0), (896, 1, 0)],
+        [(1536, 1, 0), (1536, 1, 0), (1344, 1, 0)],
+        [(2048, 1, 0), (1792, 1, 0), (1792, 1, 0)],
+        [(512, 1, 0), (512, 1, 0), (512, 1, 0)],
+        [(768, 1, 0), (768, 1, 0), (768, 1, 0)],
+        [(1024, 1, 0), (1024, 1, 0), (1024, 1, 0)],
+        [(2048, 1, 0), (2048, 1, 0), (2048, 1, 0)],
+        [(256, 1, 1), (256, 1, 1), (256, 1, 1)],
+        [(384, 1, 1), (384, 1, 1), (384, 1, 1)],
+        [(512, 1, 1), (512, 1, 1), (512, 1, 1)],
+        [(2048, 1, 1), (2048, 1, 1), (2048, 1, 1)],
+    ],
+    64: [
+        [(3584, 0, 0), (3584, 0, 0), (3584, 0, 0)],
+        [(1792, 1, 0), (1792, 0, 0), (1792, 0, 0)],
+        [(2688, 1, 0), (2688, 0, 0), (2688, 0, 0)],
+        [(3584, 0, 0), (3584, 0, 0), (3584, 0, 0)],
+        [(1024, 1, 0), (896, 1, 0), (896, 1, 0)],
+        [(1536, 1, 0), (1344, 1, 0), (1344, 1, 0)],
+        [(1792, 1, 0), (1792, 1, 0), (1792, 1, 0)],
+        [(512, 1, 0), (512, 1, 0), (512, 1, 0)],
+        [(768, 1, 0), (768, 1, 0), (768, 1, 0)],
+        [(1024, 1, 0), (1024, 1, 0), (1024, 1, 0)],
+        [(2048, 1, 0), (2048, 1, 0), (2048, 1, 0)],
+        [(256, 1, 1), (256, 1, 1), (256, 1, 1)],
+        [(384, 1, 1), (384, 1, 1), (384, 1, 1)],
+        [(512, 1, 1), (512, 1, 1), (512, 1, 1)],
+        [(2048, 1, 1), (2048, 1, 1), (2048, 1, 1)],
+    ],
+    1024: [
+        [(3584, 1, 0), (3584, 1, 0), (3584, 1, 0)],
+        [(2048, 1, 0), (2048, 1, 0), (2048, 1, 0)],
+        [(3072, 1, 0), (3072, 1, 0), (3072, 1, 0)],
+        [(4096, 1, 0), (4096, 1, 0), (3584, 1, 0)],
+        [(1024, 1, 0), (1024, 1, 0), (1024, 1, 0)],
+        [(1536, 1, 0), (1536, 1, 0), (1536, 1, 0)],
+        [(2048, 1, 0), (2048, 1, 0), (2048, 1, 0)],
+        [(512, 1, 0), (512, 1, 0), (512, 1, 0)],
+        [(768, 1, 0), (768, 1, 0), (768, 1, 0)],
+        [(1024, 1, 0), (1024, 1, 0), (1024, 1, 0)],
+        [(2048, 1, 0), (2048, 1, 0), (2048, 1, 0)],
+        [(512, 1, 1), (512, 1, 1), (512, 1, 1)],
+        [(768, 1, 1), (768, 1, 1), (768, 1, 1)],
+        [(1024, 1, 1), (1024, 1, 1), (512, 1, 1)],
+        [(4096, 1, 1), (2048, 1, 1), (2048, 1, 1)],
+    ],
+}
+_BN_CHUNKS = [
+    [(18, 128), (8, 288), (4, 576)],
+    [(9, 128), (7, 160), (4, 288)],
+    [(9, 128), (6, 192), (3, 384)],
+    [(9, 128), (4, 288), (2, 576)],
+    [(5, 128), (5, 128), (4, 160)],
+    [(5, 128), (5, 128), (3, 192)],
+    [(5, 128), (4, 160), (2, 288)],
+    [(3, 96), (3, 96), (3, 96)],
+    [(3, 96), (3, 96), (3, 96)],
+    [(3, 96), (3, 96), (2, 160)],
+    [(3, 96), (2, 160), (1, 288)],
+    [(2, 96), (2, 96), (2, 96)],
+    [(2, 96), (2, 96), (2, 96)],
+    [(2, 96), (2, 96), (2, 96)],
+    [(2, 96), (1, 160), (1, 160)],
+]
+
+
+def test_bn_geometry_per_backbone_shape_is_pinned():
+    """The single-pass geometry, its predicates and the two-stage chunking answer what they answered before the BatchNorm
+    host layer was folded onto one launch helper; forcing the two-stage kernels turns every single-pass form off."""
+    import ctypes
+    from deepards_amd import _lib
+    lib = _lib.lib()
+    try:
+        for target, table in sorted(_BN_GEOMETRY.items()):
+            assert lib.da_bn_debug_target_blocks(target) == 0
+            for (L, C), row in zip(_BN_SHAPES, table):
+                got = [(lib.da_bn_mask_words(W, 20 * L, C) // W, lib.da_bn_two_ok(W, 20 * L, C), lib.da_bn_pool_ok(W, 20 * L, C, L))
+                       for W in (16, 64, 128)]
+                assert got == row, (target, L, C, got)
+                assert all(lib.da_bn_mask_words(W, 20 * L, C) % W == 0 for W in (16, 64, 128))
+                assert not lib.da_bn_pool_ok(64, 20 * L, C, 3) and not lib.da_bn_pool_ok(64, 20 * L, C, 0)      # 3 does not divide 20 L
+        assert lib.da_bn_debug_target_blocks(256) == 0 and lib.da_bn_debug_target_blocks(0) == -1
+        for (L, C), row in zip(_BN_SHAPES, _BN_CHUNKS):
+            for W, (P, chunk) in zip((16, 64, 128), row):
+                gp, gc = ctypes.c_int(), ctypes.c_int()
+                lib.da_bn_chunks(W, 20 * L, C, ctypes.byref(gp), ctypes.byref(gc))
+                assert (gp.value, gc.value) == (P, chunk), (L, C, W)
+                assert lib.da_bn_workspace(W, 20 * L, C) == 8 * W * C * P
+        assert lib.da_bn_debug_two_stage(1) == 0
+        for L, C in _BN_SHAPES:
+            assert lib.da_bn_mask_words(64, 20 * L, C) == 0 and not lib.da_bn_two_ok(64, 20 * L, C) and not lib.da_bn_pool_ok(64, 20 * L, C, L)
+    finally:
+        lib.da_bn_debug_two_stage(0)
+        lib.da_bn_debug_target_blocks(256)
+
+
 def _wgrad_job(rows, L, N, C, k, code=0, stride=1, xform=False, dy_half=False):
     """A da_wgrad_job descriptor of Conv1d(C, N, k, stride, pad = k // 2) on rows x L outputs; the plan query dereferences
     nothing, so every operand is one dummy non-null address (the launch's pointer checks) and the workspace stays NULL."""
