@@ -934,7 +934,13 @@ __global__ __launch_bounds__(256) void bn_relu_ss_kernel(const float* __restrict
 }
 
 // chunking of a window's Wn positions so that (W * C/32 * P) fills the chip (~4 blocks per CU)
+// No windows, no positions or fewer channels than one channel group: P = 0, chunk = 0 (nothing to launch).
 static void bn_chunks(int W, int Wn, int C, int* P, int* chunk) {
+  if (W < 1 || Wn < 1 || C < CG) {
+    *P = 0;
+    *chunk = 0;
+    return;
+  }
   long base = (long)W * (C / CG);
   int p = (int)((1024 + base - 1) / base);
   int maxp = (Wn + 127) / 128;                   // at least 128 positions (4 per slot) per chunk
@@ -1023,7 +1029,7 @@ size_t da_bn_workspace(int W, int Wn, int C) {
 // stage 1 of the statistics: part[w][p][{mean,M2}][C] chunk records (da_bn_workspace() bytes).
 int da_bn_stats_partial(const void* x, int ld, int W, int Wn, int C, float* part, hipStream_t stream) {
   DA_ENTER();
-  if (!x || !part || C % CG || ld % 4 || Wn < 1) return DA_EINVAL;
+  if (!x || !part || C < CG || C % CG || ld % 4 || Wn < 1 || W < 0) return DA_EINVAL;
   if (W == 0) return DA_OK;
   int P, chunk;
   bn_chunks(W, Wn, C, &P, &chunk);
@@ -1037,7 +1043,7 @@ int da_bn_stats_partial(const void* x, int ld, int W, int Wn, int C, float* part
 // xrows (rows, Lin) float, wt (C, 1, 7); window = R rows of Lc = Lin / 2 conv outputs.  Records as da_bn_stats_partial's.
 int da_stem_stats_partial(const float* xrows, const float* wt, int rows, int R, int Lin, int C, float* part, hipStream_t stream) {
   DA_ENTER();
-  if (!xrows || !wt || !part || C % CG || R < 1 || rows % R || Lin < 2 || (Lin & 1)) return DA_EINVAL;
+  if (!xrows || !wt || !part || C < CG || C % CG || R < 1 || rows < 0 || rows % R || Lin < 2 || (Lin & 1)) return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const int W = rows / R, Lc = Lin / 2, Wn = R * Lc;
   int P, chunk;
@@ -1056,7 +1062,7 @@ int da_stem_stats_partial(const float* xrows, const float* wt, int rows, int R, 
 int da_bn_stats_merge(const float* part, int W, int Wn, int C, float eps, float* mean, float* invstd,
                       hipStream_t stream) {
   DA_ENTER();
-  if (!part || !mean || !invstd || C % CG) return DA_EINVAL;
+  if (!part || !mean || !invstd || C < CG || C % CG || Wn < 1 || W < 0) return DA_EINVAL;
   if (W == 0) return DA_OK;
   int P, chunk;
   bn_chunks(W, Wn, C, &P, &chunk);

@@ -1336,6 +1336,8 @@ def stem_fused_ok(x2d, w, R):
     # rows -- nb 40 x L 512 -- a chunk does not fit, and the stored-map stem takes the shape as before
     p_, chunk = ctypes.c_int(), ctypes.c_int()
     _lib.lib().da_bn_chunks(x2d.shape[0] // R, R * (lin // 2), w.shape[0], ctypes.byref(p_), ctypes.byref(chunk))
+    if p_.value == 0:                                  # no chunk geometry (da_bn_chunks: no positions): no fused stem
+        return False
     lc = lin // 2
     max_rows = (chunk.value + lc - 1) // lc + 1
     return (max_rows * (lin + 12) + 33 * 32) * 4 <= 64 * 1024

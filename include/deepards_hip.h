@@ -214,7 +214,9 @@ typedef struct da_bn_running_desc_ {
 } da_bn_running_desc;
 typedef struct da_bn_pgrad_desc_ { const float* s1; const float* s2; float* dgamma; float* dbeta; int W, C; } da_bn_pgrad_desc;
 
-/* two-stage statistics: P chunks of `chunk` positions per window so that W*C/32*P blocks fill the chip */
+/* two-stage statistics: P chunks of `chunk` positions per window so that W*C/32*P blocks fill the chip.  W < 1, Wn < 1 or
+ * C < 32 (less than one channel group) has no geometry: P = 0 and chunk = 0, and da_bn_workspace() returns 0; the entry
+ * points that launch over it (da_bn_stats_partial, da_bn_stats_merge, da_stem_stats_partial) answer DA_EINVAL for C < 32. */
 void da_bn_chunks(int W, int Wn, int C, int* P, int* chunk);
 size_t da_bn_workspace(int W, int Wn, int C);      /* bytes of part[w][p][{mean,M2}][C] / backward scratch */
 int da_bn_stats_partial(const da_act_t* x, int ld, int W, int Wn, int C, float* part, da_stream_t stream);

@@ -238,6 +238,23 @@ def test_bn_geometry_per_backbone_shape_is_pinned():
                 lib.da_bn_chunks(W, 20 * L, C, ctypes.byref(gp), ctypes.byref(gc))
                 assert (gp.value, gc.value) == (P, chunk), (L, C, W)
                 assert lib.da_bn_workspace(W, 20 * L, C) == 8 * W * C * P
+        # no windows, no positions, or fewer channels than one channel group of 32: no geometry -- P = 0, chunk = 0 and no
+        # workspace, answered without a signal (C < 32 used to divide by zero)
+        for W, Wn, C in [(16, 1120, 0), (16, 1120, 1), (16, 1120, 16), (16, 1120, 31), (0, 1120, 64), (-1, 1120, 64),
+                         (16, 0, 64), (16, -5, 64), (0, 0, 0)]:
+            gp, gc = ctypes.c_int(-7), ctypes.c_int(-7)
+            lib.da_bn_chunks(W, Wn, C, ctypes.byref(gp), ctypes.byref(gc))
+            assert (gp.value, gc.value) == (0, 0), (W, Wn, C)
+            assert lib.da_bn_workspace(W, Wn, C) == 0, (W, Wn, C)
+        # ... and the entry points that launch over that geometry refuse such a shape before they launch anything
+        buf = (ctypes.c_float * 64)()
+        for C in (0, 16):
+            assert lib.da_bn_stats_partial(buf, 32, 16, 1120, C, buf, None) == -1
+            assert lib.da_bn_stats_merge(buf, 16, 1120, C, 1e-5, buf, buf, None) == -1
+            assert lib.da_stem_stats_partial(buf, buf, 40, 20, 224, C, buf, None) == -1
+        gp, gc = ctypes.c_int(), ctypes.c_int()
+        lib.da_bn_chunks(1, 1, 32, ctypes.byref(gp), ctypes.byref(gc))          # the smallest shape that has one
+        assert (gp.value, gc.value) == (1, 32) and lib.da_bn_workspace(1, 1, 32) == 8 * 32
         assert lib.da_bn_debug_two_stage(1) == 0
         for L, C in _BN_SHAPES:
             assert lib.da_bn_mask_words(64, 20 * L, C) == 0 and not lib.da_bn_two_ok(64, 20 * L, C) and not lib.da_bn_pool_ok(64, 20 * L, C, L)
