@@ -153,6 +153,8 @@ SIGNATURES = {
     'da_global_avgpool_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'da_linear2_fwd': (_I, [_P, _P, _P, _P, _I, _I, _P]),
     'da_bce_logits': (_I, [_P, _P, _I, _F, _P, _P, _P]),
+    'da_confidence_loss': (_I, [_P, _P, _I, _I, _F, _F, _P, _P, _P]),
+    'da_vacillating_loss': (_I, [_P, _P, _I, _I, _F, _F, _P, _P, _P]),
     'da_linear2_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'da_head_groups': (_I, [_I, _I]),
     'da_head_fwd': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

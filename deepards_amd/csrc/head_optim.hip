@@ -61,6 +61,98 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ x, c
   if (threadIdx.x == 0) loss[0] = (red[0] + red[1] + red[2] + red[3]) * inv;
 }
 
+// The two per-breath losses of the reference's loss.py on logits x [W][nb][2] and window targets t [W][2] (nb = 1 for the
+// window-level heads), loss and d loss / d logits in ONE launch of one block: wave j takes the windows j, j + 16, ...,
+// its lanes the breaths.  Every sum is a lane-strided partial, a wave butterfly and a fixed-order fold over the 16 waves'
+// LDS slots -- no atomics, so a replay gives the same bits.  With n = W nb 2 and, per breath, d = x1 - x0,
+// p = softmax(x) (p1 = sigmoid(d)):
+//   both       bce = sum(max(x,0) - x t + log1p(exp(-|x|))) / n over all logits, the window target repeated over the breaths
+//   CONFIDENCE ConfidencePenaltyLoss(beta), loss.py:32-35:  bce + beta sum_c(p_c log p_c) / n, log p as a log-softmax
+//              (log p1 = -softplus(-d)); with S = sum_c p_c log p_c of the breath  dx_c = (sigmoid(x_c) - t_c + beta p_c (log p_c - S)) / n
+//   VACILLATE  VacillatingLoss(alpha), loss.py:15-23:  bce + mean over [W][2] of v(xm), xm[w][c] = mean over the breaths of p_c,
+//              v(xm) = -log(2 (e^-alpha - 1) xm + 1) for xm <= 0.5 and -log(2 e^-alpha (1 - xm) + 2 xm - 1) above.  The two
+//              classes of a window sum to 1, so with m = xm1 - xm0 = mean(tanh(d / 2)) BOTH arguments are
+//              A = |m| + 2 e^-alpha min(xm0, xm1) = |m| (1 - e^-alpha) + e^-alpha: the term is sum_w(-log A_w) / W.  |m| is
+//              summed from the breaths' tanh(d / 2) directly, never as 2 xm - 1 (no cancellation), and e^-alpha = 0 at
+//              alpha = inf leaves -log|m| = -log(1 - 2 xm) = -log(2 xm - 1) without a NaN.  xm == 0.5 exactly (m == 0), where
+//              the reference's two masks differ in size and it raises, takes the LEFT branch here: -log(e^-alpha) = alpha.
+//              d/dd_t (-log A_w) / W = -sign(m) (1 - e^-alpha) 2 p0 p1 / (A_w W nb), dx1 = +that, dx0 = -that.
+// gscale multiplies the gradient only (the 1/world of data parallelism, like bce_kernel).
+enum { LOSS_CONFIDENCE = 0, LOSS_VACILLATE = 1 };
+template <int MODE>
+__global__ __launch_bounds__(1024) void breath_loss_kernel(const float* __restrict__ x, const float* __restrict__ t, int W,
+                                                           int nb, float param, float gscale, float* __restrict__ loss,
+                                                           float* __restrict__ dx) {
+  __shared__ float red[2][16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float inv_n = 1.0f / ((float)W * (float)nb * 2.0f);
+  const float ea = MODE == LOSS_VACILLATE ? expf(-param) : 0.f;          // e^-alpha (0 at alpha = inf)
+  const float one_m_ea = MODE == LOSS_VACILLATE ? -expm1f(-param) : 0.f; // 1 - e^-alpha
+  float bce = 0.f, extra = 0.f;           // extra: sum p log p (CONFIDENCE) / sum -log A (VACILLATE, lane 0 of the wave)
+  for (int w = wave; w < W; w += 16) {
+    const float t0 = t[(size_t)w * 2], t1 = t[(size_t)w * 2 + 1];
+    const float* xw = x + (size_t)w * nb * 2;
+    float* dw = dx ? dx + (size_t)w * nb * 2 : nullptr;
+    float msum = 0.f;
+    for (int b = lane; b < nb; b += 64) {
+      const float x0 = xw[b * 2], x1 = xw[b * 2 + 1];
+      bce += fmaxf(x0, 0.f) - x0 * t0 + log1pf(expf(-fabsf(x0)));
+      bce += fmaxf(x1, 0.f) - x1 * t1 + log1pf(expf(-fabsf(x1)));
+      const float d = x1 - x0, e = expf(-fabsf(d));
+      if (MODE == LOSS_CONFIDENCE) {
+        const float sp = log1pf(e);                       // softplus(-|d|)
+        const float lp_hi = -sp, lp_lo = -fabsf(d) - sp;  // log p of the larger / the smaller logit
+        const float p_hi = 1.0f / (1.0f + e), p_lo = e / (1.0f + e);
+        const float s = p_hi * lp_hi + p_lo * lp_lo;
+        extra += s;
+        if (dw) {
+          const bool up = d >= 0.f;                       // class 1 holds the larger logit
+          const float p0 = up ? p_lo : p_hi, p1 = up ? p_hi : p_lo;
+          const float l0 = up ? lp_lo : lp_hi, l1 = up ? lp_hi : lp_lo;
+          const float s0 = 1.0f / (1.0f + expf(-x0)), s1 = 1.0f / (1.0f + expf(-x1));
+          dw[b * 2] = (s0 - t0 + param * p0 * (l0 - s)) * inv_n * gscale;
+          dw[b * 2 + 1] = (s1 - t1 + param * p1 * (l1 - s)) * inv_n * gscale;
+        }
+      } else {
+        const float th = (1.0f - e) / (1.0f + e);         // tanh(|d| / 2) = p_hi - p_lo
+        msum += d >= 0.f ? th : -th;
+      }
+    }
+    if (MODE == LOSS_VACILLATE) {
+      const float m = wave_sum(msum) / (float)nb;         // xm1 - xm0 (every lane holds it)
+      const float A = fabsf(m) * one_m_ea + ea;
+      if (lane == 0) extra += -logf(A);
+      if (dw) {
+        const float sgn = m > 0.f ? 1.0f : (m < 0.f ? -1.0f : 0.f);
+        const float k = -sgn * one_m_ea * 2.0f / (A * (float)W * (float)nb);
+        for (int b = lane; b < nb; b += 64) {
+          const float x0 = xw[b * 2], x1 = xw[b * 2 + 1];
+          const float e = expf(-fabsf(x1 - x0));
+          const float pp = e / ((1.0f + e) * (1.0f + e));  // p0 p1
+          const float s0 = 1.0f / (1.0f + expf(-x0)), s1 = 1.0f / (1.0f + expf(-x1));
+          dw[b * 2] = ((s0 - t0) * inv_n - k * pp) * gscale;
+          dw[b * 2 + 1] = ((s1 - t1) * inv_n + k * pp) * gscale;
+        }
+      }
+    }
+  }
+  bce = wave_sum(bce);
+  extra = wave_sum(extra);
+  if (lane == 0) {
+    red[0][wave] = bce;
+    red[1][wave] = extra;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sb = 0.f, se = 0.f;
+    for (int k = 0; k < 16; ++k) {
+      sb += red[0][k];
+      se += red[1][k];
+    }
+    loss[0] = MODE == LOSS_CONFIDENCE ? (sb + param * se) * inv_n : sb * inv_n + se / (float)W;
+  }
+}
+
 // dflat[b][i] = dl[b][0] W[0][i] + dl[b][1] W[1][i]
 __global__ __launch_bounds__(256) void linear2_bwd_input_kernel(const float* __restrict__ dl, const float* __restrict__ W,
                                                                 float* __restrict__ dflat, int B, int K) {
@@ -873,6 +965,28 @@ int da_bce_logits(const float* logits, const float* target, int n, float gscale,
   DA_ENTER();
   if (!logits || !target || !loss || n < 1) return DA_EINVAL;
   hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(256), 0, stream, logits, target, n, gscale, loss, dlogits);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+// logits [n_windows][nb][2], target [n_windows][2], loss: 1 float, dlogits [n_windows][nb][2] or null (test epoch).
+int da_confidence_loss(const float* logits, const float* target, int n_windows, int nb, float beta, float gscale,
+                       float* loss, float* dlogits, hipStream_t stream) {
+  DA_ENTER();
+  if (!logits || !target || !loss || n_windows < 1 || nb < 1) return DA_EINVAL;
+  hipLaunchKernelGGL(breath_loss_kernel<LOSS_CONFIDENCE>, dim3(1), dim3(1024), 0, stream, logits, target, n_windows, nb,
+                     beta, gscale, loss, dlogits);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+// alpha > 0, inf included (the reference's default --valpha).
+int da_vacillating_loss(const float* logits, const float* target, int n_windows, int nb, float alpha, float gscale,
+                        float* loss, float* dlogits, hipStream_t stream) {
+  DA_ENTER();
+  if (!logits || !target || !loss || n_windows < 1 || nb < 1 || !(alpha > 0.f)) return DA_EINVAL;
+  hipLaunchKernelGGL(breath_loss_kernel<LOSS_VACILLATE>, dim3(1), dim3(1024), 0, stream, logits, target, n_windows, nb,
+                     alpha, gscale, loss, dlogits);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

