@@ -436,46 +436,53 @@ __global__ __launch_bounds__(256) void clamp_sgd_nesterov_kernel(float* __restri
   }
 }
 
-// torch.optim.Adam (no weight decay, no amsgrad): bc1 = 1-b1^t, bc2 = 1-b2^t supplied by the host
-__global__ __launch_bounds__(256) void clamp_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
-                                                         float lr, float b1, float b2, float eps, float bc1, float bc2,
-                                                         float clip, float gscale) {
-  const float step = lr / bc1;
-  const float rs = 1.0f / sqrtf(bc2);
+// torch.optim.Adam (no weight decay, no amsgrad).  The betas cross the ABI as doubles, as torch holds them: 1 - beta and
+// the bias corrections 1 - beta^t are formed in double and rounded once (1.f - 0.999f is 1.3e-5 off 0.001, which went
+// straight into v; 1.f - powf(b2, 1) cancels to 2^-24 b2 / (1 - b2) = 6e-5 relative)
+struct AdamCoef {
+  float b1, b2, omb1, omb2;      // beta, 1 - beta
+  float step, rs;                // lr / (1 - b1^t), 1 / sqrt(1 - b2^t)
+};
+__host__ __device__ __forceinline__ AdamCoef adam_coef(double b1, double b2, double t, float lr) {
+  AdamCoef c;
+  c.b1 = (float)b1;
+  c.b2 = (float)b2;
+  c.omb1 = (float)(1.0 - b1);
+  c.omb2 = (float)(1.0 - b2);
+  c.step = lr / (float)(1.0 - pow(b1, t));
+  c.rs = 1.0f / sqrtf((float)(1.0 - pow(b2, t)));
+  return c;
+}
+__device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, size_t n, const AdamCoef c, float eps, float clip,
+                                            float gscale) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
     if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float mi = c.b1 * m[i] + c.omb1 * gi;
+    float vi = c.b2 * v[i] + c.omb2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
-    float denom = sqrtf(vi) * rs + eps;
-    p[i] -= step * (mi / denom);
+    float denom = sqrtf(vi) * c.rs + eps;
+    p[i] -= c.step * (mi / denom);
   }
 }
 
+// the coefficients of step t from the host
+__global__ __launch_bounds__(256) void clamp_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
+                                                         AdamCoef c, float eps, float clip, float gscale) {
+  adam_update(p, g, m, v, n, c, eps, clip, gscale);
+}
+
 // the same with the step count on the device (a captured graph replays it): *step_ptr is incremented by the first thread
-// of a preceding launch (counter_inc_kernel), every thread derives the bias corrections from it
+// of a preceding launch (counter_inc_kernel), every thread derives the coefficients from it
 __global__ __launch_bounds__(256) void clamp_adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                              float* __restrict__ m, float* __restrict__ v, size_t n,
-                                                             float lr, float b1, float b2, float eps,
+                                                             float lr, double b1, double b2, float eps,
                                                              const long long* __restrict__ step_ptr, float clip,
                                                              float gscale) {
-  const float t = (float)step_ptr[0];
-  const float bc1 = 1.0f - powf(b1, t), bc2 = 1.0f - powf(b2, t);
-  const float step = lr / bc1;
-  const float rs = 1.0f / sqrtf(bc2);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float gi = g[i] * gscale;
-    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    float denom = sqrtf(vi) * rs + eps;
-    p[i] -= step * (mi / denom);
-  }
+  adam_update(p, g, m, v, n, adam_coef(b1, b2, (double)step_ptr[0], lr), eps, clip, gscale);
 }
 
 __global__ void counter_inc_kernel(long long* c) {
@@ -1115,22 +1122,20 @@ int da_clamp_sgd_nesterov(float* p, const float* g, float* buf, size_t n, float 
   return DA_OK;
 }
 
-int da_clamp_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+int da_clamp_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps,
                   int step, float clip, float gscale, hipStream_t stream) {
   DA_ENTER();
   if (!p || !g || !m || !v || step < 1) return DA_EINVAL;
   if (n == 0) return DA_OK;
-  float bc1 = 1.0f - powf(beta1, (float)step);
-  float bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(clamp_adam_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, bc1, bc2, clip, gscale);
+  hipLaunchKernelGGL(clamp_adam_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, p, g, m, v, n,
+                     adam_coef(beta1, beta2, (double)step, lr), eps, clip, gscale);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
 
 // da_clamp_adam with the step count in device memory (int64, starts at 0): incremented here, then used -- the whole
 // update is stream-ordered device work, so a captured graph can replay it (torch.optim.Adam, train_ards_detector.py:421).
-int da_clamp_adam_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+int da_clamp_adam_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps,
                       long long* step, float clip, float gscale, hipStream_t stream) {
   DA_ENTER();
   if (!p || !g || !m || !v || !step) return DA_EINVAL;

@@ -456,10 +456,11 @@ int da_head_flat_bwd(const float* part, const float* bias, const float* target, 
  * gradient all-reduce (the clamp runs AFTER the reduce, SURVEY.md finding 7). */
 int da_clamp_sgd_nesterov(float* p, const float* g, float* buf, size_t n, float lr, float momentum,
                           float weight_decay, float clip, float gscale, int first, da_stream_t stream);
-int da_clamp_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+/* Adam's betas are doubles (as torch holds them): 1 - beta and the bias corrections 1 - beta^t are formed in double */
+int da_clamp_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2,
                   float eps, int step, float clip, float gscale, da_stream_t stream);
 /* the same with the step count in device memory (int64, incremented by the call): graph-replayable */
-int da_clamp_adam_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+int da_clamp_adam_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps,
                       long long* step, float clip, float gscale, da_stream_t stream);
 
 /* ---- device-resident window store: batch gather fused with the (x-mu)/std normalisation -------------------

@@ -158,6 +158,30 @@ def avgpool3s2p1_bwd(dy, l):
     return avgpool_bwd(dy, 3, 2, l + 2)[:, :, 1:l + 1]
 
 
+def avgpool_slide_fwd(x, k):
+    """nn.AvgPool1d(k, 1) on a map longer than k, then ``x.view(x.size(0), -1)`` (resnet.py:159-160,
+    densenet.py:183-184 on seq_len > 224): x (N,C,L) -> (N, C * Lout), feature index c * Lout + j."""
+    n, c, l = x.shape
+    lo = l - k + 1
+    feat = np.zeros((n, c, lo), dtype=x.dtype)
+    for j in range(lo):
+        feat[:, :, j] = x[:, :, j:j + k].sum(axis=2) / k
+    return feat.reshape(n, c * lo)                                  # channel slowest, as view() of (N,C,Lout)
+
+
+def avgpool_slide_bwd(dfeat, k, l, c):
+    """Backward of avgpool_slide_fwd: dfeat (N, C * Lout) -> dx (N,C,L); position p is covered by the windows
+    j = max(0, p - k + 1) .. min(p, Lout - 1), each of which hands it dfeat[c * Lout + j] / k."""
+    n = dfeat.shape[0]
+    lo = l - k + 1
+    d3 = dfeat.reshape(n, c, lo)
+    dx = np.zeros((n, c, l), dtype=dfeat.dtype)
+    for p in range(l):
+        for j in range(max(0, p - k + 1), min(p, lo - 1) + 1):
+            dx[:, :, p] += d3[:, :, j] / k
+    return dx
+
+
 def linear_fwd(x, w, b):
     return x @ w.T + b
 
@@ -168,6 +192,46 @@ def bce_with_logits(x, t):
     loss = np.maximum(x, 0) - x * t + np.log1p(np.exp(-np.abs(x)))
     sig = 1.0 / (1.0 + np.exp(-x))
     return loss.mean(), (sig - t) / x.size
+
+
+def head_chain(xmap, w, bias, target, rows_per_window, gscale=1.0):
+    """The head of CNNLinearNetwork on the breath block's last map and its backward: AvgPool1d(L, 1) + view
+    (resnet.py:112,159-160), linear_final on view(-1) of the window's (NB, F) block
+    (torch_cnn_linear_network.py:102,110-112), BCEWithLogitsLoss (train_ards_detector.py:530).
+    xmap (B * NB, F, L), w (2, NB * F), bias (2,), target (B, 2).  gscale multiplies the gradients only (the 1 / world
+    of data parallelism).  -> dict(flat, logits, loss, dlogits, dx (B * NB, F, L), dw, dbias)."""
+    rows, f, l = xmap.shape
+    b = rows // rows_per_window
+    flat = xmap.mean(axis=2).reshape(b, rows_per_window * f)
+    logits = linear_fwd(flat, w, bias)
+    loss, dl = bce_with_logits(logits, target)
+    dl = dl * gscale
+    dflat = dl @ w
+    dx = np.repeat(dflat.reshape(rows, f)[:, :, None] / l, l, axis=2)
+    return dict(flat=flat, logits=logits, loss=loss, dlogits=dl, dx=dx, dw=dl.T @ flat, dbias=dl.sum(axis=0))
+
+
+def vote_table(logits, group, n_groups, votes=None):
+    """Window predictions and the per-patient vote table of the test epoch (train_ards_detector.py:932-936
+    outputs.argmax, metrics.py:572-604): pred[b] = argmax(logits[b]) with the FIRST maximum (class 0 on a tie, -0.0 and
+    0.0 are a tie), votes[group[b]][pred[b]] += 1 onto ``votes`` (zeros if None); a group outside [0, n_groups) adds
+    nothing.  NaN logits are not defined here.  -> pred (B,) int, votes (n_groups, 2) int."""
+    pred = (logits[:, 1] > logits[:, 0]).astype(np.int64)
+    votes = np.zeros((n_groups, 2), dtype=np.int64) if votes is None else votes.astype(np.int64)
+    ok = (group >= 0) & (group < n_groups)
+    np.add.at(votes, (group[ok], pred[ok]), 1)
+    return pred, votes
+
+
+def gather_normalize(tiles, idx, mu, std):
+    """ARDSRawDataset.__getitem__'s normalisation in float64 (dataset.py:1364,1379) of the windows idx, then the
+    .float() cast of train_ards_detector.py:150-152.  tiles (N, ...) float64; mu / std scalars, or one value per
+    channel of (N, NB, C, L) tiles (dataset.py:627-649).  -> (B, ...) float32."""
+    x = np.asarray(tiles, dtype=np.float64)[idx]
+    if np.ndim(mu):
+        mu = np.asarray(mu, dtype=np.float64).reshape(1, 1, -1, 1)
+        std = np.asarray(std, dtype=np.float64).reshape(1, 1, -1, 1)
+    return ((x - mu) / std).astype(np.float32)
 
 
 def clamp_grad(g, clip):

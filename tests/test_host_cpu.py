@@ -46,6 +46,92 @@ def test_abi_structs_agree_between_header_library_and_binding(tmp_path):
     assert header == list(out) == binding, (header, list(out), binding)
 
 
+def _header_prototypes():
+    """{name: (return type text, [parameter type texts])} of every function the public header declares: comments,
+    preprocessor lines, the extern "C" braces and struct bodies stripped, one statement per ';'."""
+    import re
+    from deepards_amd import _lib
+    txt = open(_lib.HEADER).read()
+    txt = re.sub(r'/\*.*?\*/', ' ', txt, flags=re.S)
+    txt = re.sub(r'//[^\n]*', ' ', txt)
+    txt = re.sub(r'^\s*#[^\n]*$', ' ', txt, flags=re.M)
+    txt = re.sub(r'extern\s+"C"\s*\{', ' ', txt)
+    while True:                                                   # struct bodies (none is nested, the loop costs nothing)
+        cut = re.sub(r'\{[^{}]*\}', ' ', txt)
+        if cut == txt:
+            break
+        txt = cut
+    protos = {}
+    for stmt in txt.split(';'):
+        stmt = ' '.join(stmt.replace('}', ' ').split())
+        m = re.match(r'^(.*?)\b(da_[a-z0-9_]+)\s*\((.*)\)$', stmt)
+        if not m or stmt.startswith('typedef'):
+            continue
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        assert name not in protos, 'declared twice: ' + name
+        plist = [] if params in ('', 'void') else [p.strip() for p in params.split(',')]
+        protos[name] = (ret, plist)
+    return protos
+
+
+def _c_class(decl, is_return=False):
+    """A C declaration (parameter with its name, or a return type) -> ('ptr',) / ('void',) / ('int', bytes, signed) /
+    ('float', bytes)."""
+    import ctypes
+    import re
+    if '*' in decl or '[' in decl:
+        return ('ptr',)
+    words = [w for w in decl.split() if w != 'const']
+    if not is_return:
+        words = words[:-1]                                        # the parameter's name
+    t = ' '.join(words)
+    if t == 'da_stream_t':
+        return ('ptr',)
+    table = {'void': ('void',), 'int': ('int', 4, True), 'unsigned': ('int', 4, False), 'unsigned int': ('int', 4, False),
+             'size_t': ('int', ctypes.sizeof(ctypes.c_size_t), False), 'long': ('int', ctypes.sizeof(ctypes.c_long), True),
+             'long long': ('int', 8, True), 'int64_t': ('int', 8, True), 'float': ('float', 4), 'double': ('float', 8)}
+    assert t in table, 'a type this check does not know: %r in %r' % (t, decl)
+    assert re.match(r'^[A-Za-z_ ]+$', t)
+    return table[t]
+
+
+def _ctypes_class(c):
+    """The same classes for a ctypes type (c_long and c_longlong are one class on LP64: size and signedness decide)."""
+    import ctypes
+    if c is None:
+        return ('void',)
+    if issubclass(c, (ctypes._Pointer, ctypes.Array)) or c in (ctypes.c_void_p, ctypes.c_char_p):
+        return ('ptr',)
+    code = c._type_
+    if code in 'fd':
+        return ('float', ctypes.sizeof(c))
+    assert code in 'bhilqBHILQ', 'a ctypes class this check does not know: %r' % (c,)
+    return ('int', ctypes.sizeof(c), code.islower())
+
+
+def test_every_binding_matches_its_header_prototype():
+    """_lib.SIGNATURES against include/deepards_hip.h, entry by entry: the return type and every parameter's class
+    (pointer / da_stream_t <-> a pointer type; int, unsigned, size_t, long, float, double <-> the ctypes class of the same
+    kind, size and signedness).  ctypes converts silently, so a size_t bound as c_int or a double bound as c_float would
+    hand the library a wrong value without any error."""
+    from deepards_amd import _lib
+    protos = _header_prototypes()
+    assert set(protos) == set(_lib.SIGNATURES)
+    assert len(protos) >= 115
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = _lib.SIGNATURES[name]
+        if _c_class(ret, is_return=True) != _ctypes_class(res):
+            bad.append('%s: returns %r, bound as %r' % (name, ret, res))
+        if len(params) != len(args):
+            bad.append('%s: %d parameters in the header, %d bound' % (name, len(params), len(args)))
+            continue
+        for i, (p, a) in enumerate(zip(params, args)):
+            if _c_class(p) != _ctypes_class(a):
+                bad.append('%s: parameter %d %r bound as %r' % (name, i, p, a))
+    assert not bad, '\n'.join(bad)
+
+
 def test_product_path_refuses_cpu_tensors():
     import deepards_amd.models as M
     from deepards_amd import hip_ops as H
