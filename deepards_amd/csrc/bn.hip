@@ -387,15 +387,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const AT* __restrict_
 // -------------------------------------------------------------------------------------------------
 #define FUSED_NPOS 10
 
-// counter-based dropout keep mask of head_optim.hip (da_dropout): element i of the contiguous [npos][G] tensor
-__device__ __forceinline__ uint32_t bn_mix32(uint32_t a, uint32_t b) {
-  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
-  h ^= h >> 16; h *= 0x85EBCA6Bu;
-  h ^= h >> 13; h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-
 // Options of the dense-block BatchNorm backward (da_bn_bwd_ss): mean / invstd from a pitched table; the ReLU decision in
 // the scale / shift form above; the upstream gradient at HALF resolution (a transition's AvgPool1d(2,2) folded in front of
 // its 1x1 conv: dh[2j] = dh[2j+1] = dpooled[j] / 2); a dropout mask applied to the LAST drop_g channels of dx on store
@@ -737,13 +728,13 @@ __device__ __forceinline__ void bn_bwd_fused_body(const AT* __restrict__ dout, i
       }
       if (EXT && ext.p > 0.f && c0 >= ext.drop_c0) {  // (wave-uniform for 16- / 32-channel blocks and 32-channel segments)
         const long long sd = ext.seed[0];
-        const uint32_t key = bn_mix32((uint32_t)sd ^ (uint32_t)(sd >> 32), ext.salt), thr = (uint32_t)(ext.p * 4294967296.0);
+        const uint32_t key = mix32((uint32_t)sd ^ (uint32_t)(sd >> 32), ext.salt), thr = (uint32_t)(ext.p * 4294967296.0);
         const float scale = 1.0f / (1.0f - ext.p);
         const size_t i0 = (base + p) * (size_t)ext.drop_g + (c0 - ext.drop_c0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const size_t i = i0 + e;
-          const uint32_t hsh = bn_mix32(key, (uint32_t)i ^ (uint32_t)(i >> 32) * 0x27d4eb2fu);
+          const uint32_t hsh = mix32(key, (uint32_t)i ^ (uint32_t)(i >> 32) * 0x27d4eb2fu);
           d[e] = hsh >= thr ? d[e] * scale : 0.f;
         }
       }

@@ -19,8 +19,28 @@ typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 #define DA_OK 0
 #define DA_EINVAL (-1)
 
+// XCD-aware block order (MI355X: 8 XCDs, blocks are dealt to them round-robin, each with its own 4 MiB L2):
+// give every XCD a CONTIGUOUS chunk of the linear tile order, so that consecutive work items -- tiles which share an
+// operand panel -- run on the same L2 close together in time.  Bijective for any block count; affects speed only.
+__device__ __forceinline__ int xcd_chunked(int id, int total) {
+  const int q = total >> 3, r = total & 7;
+  const int xcd = id & 7, s = id >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + s;
+}
+
+// The hash of the counter-based dropout keep masks: element i of a contiguous tensor is kept iff
+// mix32(mix32(seed, salt), i) >= p * 2^32 (da_dropout; the Winograd epilogue and the dense-block BatchNorm backward
+// regenerate the same mask).
+__device__ __forceinline__ uint32_t mix32(uint32_t a, uint32_t b) {
+  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
+  h ^= h >> 16; h *= 0x85EBCA6Bu;
+  h ^= h >> 13; h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
 // Row-partitioned kernels (BatchNorm, pools: one block per window of rows) take their window from the block index the way
-// the convolutions take their tiles (conv_gemm.hip xcd_chunked): the blocks that the hardware places on XCD k (block id
+// the convolutions take their tiles (xcd_chunked above): the blocks that the hardware places on XCD k (block id
 // mod 8) work on the k-th EIGHTH of the rows, so the activation rows a convolution's XCD left in its 4 MB L2 are read by
 // blocks of the same XCD, and what they write waits in the L2 the next convolution's tiles of those rows run on.
 __device__ __forceinline__ int row_xcd_chunk(int id, int total) {

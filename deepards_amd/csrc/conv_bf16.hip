@@ -15,14 +15,6 @@
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-// block id -> work item so that CONSECUTIVE work items share an XCD (blocks are dealt to the 8 XCDs round-robin): the
-// channel tiles of one position tile, which read the same activation panel, then hit the same L2 (conv_gemm.hip)
-__device__ __forceinline__ int xcd_chunked_bf(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, s = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + s;
-}
-
 struct ConvBf16Args {
   const void* x;        // [M][ldx] activations (float or bf16: template AT), first C channels
   const __bf16* w;      // [3][N][C] bf16 taps
@@ -106,7 +98,7 @@ __device__ __forceinline__ void conv3_bf16_body(const ConvBf16Args& a, unsigned 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntn = a.N / CB_TN;
-  const int tile = xcd_chunked_bf(blockIdx.x, gridDim.x);
+  const int tile = xcd_chunked(blockIdx.x, gridDim.x);
   const int P0 = (tile / ntn) * CB_TM, n_blk = (tile % ntn) * CB_TN;
 
   // X loader: 32 rows x 8 channel quads per pass; lanes 8..15 of every 16 take the row 4 below lanes 0..7 so that a
@@ -481,7 +473,7 @@ __global__ __launch_bounds__(256) void conv_bf16_gen_kernel(ConvBf16GenTable t) 
   __shared__ __attribute__((aligned(16))) unsigned char lds[XBYTES + 3 * CB_TN * CB_PITCH];
   int i = 0;
   while (i + 1 < t.n && (int)blockIdx.x >= t.first_block[i + 1]) ++i;      // wave-uniform
-  conv_bf16_gen_body<SS, AT>(t.d[i], xcd_chunked_bf(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
+  conv_bf16_gen_body<SS, AT>(t.d[i], xcd_chunked(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
 }
 
 // wf[t][co][ci] = bf16(w[co][ci][t]) (forward taps), wd[t][ci][co] = bf16(w[co][ci][2 - t]) (data-gradient taps)
@@ -858,7 +850,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_multi_kernel(WgradBf16Table t)
   __shared__ __attribute__((aligned(16))) unsigned char lds[WB<NS>::LDS_BYTES];
   int i = 0;
   while (i + 1 < t.n && (int)blockIdx.x >= t.first_block[i + 1]) ++i;      // wave-uniform
-  const int b = xcd_chunked_bf(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]);   // a split's tiles share an XCD
+  const int b = xcd_chunked(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]);   // a split's tiles share an XCD
   if (t.d[i].mode == 0) wgrad_bf16_body<AT, NS>(t.d[i], b, lds);
   else if (t.d[i].mode == 1) wgrad_bf16_s2_body<3, AT, NS>(t.d[i], b, lds);
   else wgrad_bf16_s2_body<1, AT, NS>(t.d[i], b, lds);
@@ -870,7 +862,7 @@ __global__ __launch_bounds__(256) void wgrad_x3p_multi_kernel(WgradBf16Table t) 
   __shared__ __attribute__((aligned(16))) unsigned char lds[WB<3>::LDS_BYTES];
   int i = 0;
   while (i + 1 < t.n && (int)blockIdx.x >= t.first_block[i + 1]) ++i;      // wave-uniform
-  const int b = xcd_chunked_bf(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]);
+  const int b = xcd_chunked(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]);
   if (t.d[i].mode == 0) wgrad_bf16_body<X3T, 3>(t.d[i], b, lds);
   else if (t.d[i].mode == 1) wgrad_bf16_s2_body<3, X3T, 3>(t.d[i], b, lds);
   else wgrad_bf16_s2_body<1, X3T, 3>(t.d[i], b, lds);
@@ -939,6 +931,21 @@ int bf16_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, in
   return flush();
 }
 
+// What da_conv3_bf16 and da_conv3_bf16_bn share: the shape refusals and every ConvBf16Args field but the BatchNorm ones.
+// -> the launch's tile count (0: rows == 0), or -1: refused.
+static long conv3_bf16_fill(ConvBf16Args& a, const void* x, const void* wpk, void* y, int rows, int L, int ldx, int C, int ldy,
+                            int N, int accumulate) {
+  if (!x || !wpk || !y || rows < 0 || L < 1 || C % 32 || N % CB_TN || C < 32 || N < CB_TN || ldx % 4 || ldx < C || ldy < N)
+    return -1;
+  const long M = (long)rows * L;
+  if (M >= 0x7fffffffl) return -1;
+  a.x = x; a.w = reinterpret_cast<const __bf16*>(wpk); a.y = y;
+  a.M = (int)M; a.L = L; a.ldx = ldx; a.C = C; a.ldy = ldy; a.N = N; a.accumulate = accumulate;
+  a.divL = make_fastdiv((uint32_t)L);
+  const long tiles = ((M + CB_TM - 1) / CB_TM) * (N / CB_TN);
+  return tiles > 0x7fffffffl ? -1 : tiles;
+}
+
 extern "C" {
 
 // y (+)= conv1d(x, k = 3, stride 1, pad 1) per row of L positions, bf16 products / fp32 sums.  x: [rows][L][ldx] fp32
@@ -947,19 +954,12 @@ extern "C" {
 int da_conv3_bf16(const void* x, const void* wpk, void* y, int rows, int L, int ldx, int C, int ldy, int N,
                   int accumulate, hipStream_t stream) {
   DA_ENTER();
-  if (!x || !wpk || !y || rows < 0 || L < 1 || C % 32 || N % CB_TN || C < 32 || N < CB_TN || ldx % 4 || ldx < C || ldy < N)
-    return DA_EINVAL;
-  if (rows == 0) return DA_OK;
-  const long M = (long)rows * L;
-  if (M >= 0x7fffffffl) return DA_EINVAL;
   ConvBf16Args a;
-  a.x = x; a.w = reinterpret_cast<const __bf16*>(wpk); a.y = y;
-  a.M = (int)M; a.L = L; a.ldx = ldx; a.C = C; a.ldy = ldy; a.N = N; a.accumulate = accumulate;
-  a.divL = make_fastdiv((uint32_t)L);
+  const long tiles = conv3_bf16_fill(a, x, wpk, y, rows, L, ldx, C, ldy, N, accumulate);
+  if (tiles < 0) return DA_EINVAL;
+  if (rows == 0) return DA_OK;
   a.Wn = 1; a.stat_part = nullptr; a.in_pend = nullptr; a.in_mean = a.in_invstd = nullptr; a.in_gamma = a.in_beta = nullptr;
   a.in_tiles = 0; a.in_eps = 0.f;
-  const long tiles = ((M + CB_TM - 1) / CB_TM) * (N / CB_TN);
-  if (tiles > 0x7fffffffl) return DA_EINVAL;
   DA_ACT_DISPATCH(hipLaunchKernelGGL(conv3_bf16_kernel<AT>, dim3((unsigned)tiles), dim3(256), 0, stream, a));
   DA_CHECK_LAUNCH();
   return DA_OK;
@@ -975,21 +975,14 @@ int da_conv3_bf16_bn(const void* x, const void* wpk, void* y, int rows, int L, i
                      const float* in_pend, float* in_mean, float* in_invstd, const float* gamma, const float* beta, float eps,
                      float* stat_part, hipStream_t stream) {
   DA_ENTER();
-  if (!x || !wpk || !y || rows < 0 || L < 1 || C % 32 || N % CB_TN || C < 32 || N < CB_TN || ldx % 4 || ldx < C || ldy < N)
-    return DA_EINVAL;
+  ConvBf16Args a;
+  const long tiles = conv3_bf16_fill(a, x, wpk, y, rows, L, ldx, C, ldy, N, 0);
+  if (tiles < 0) return DA_EINVAL;
   if (R < 1 || rows % R || (long)R * L < CB_TM + 2 || (!stat_part && !in_pend)) return DA_EINVAL;
   if (in_pend && (!in_mean || !in_invstd || !gamma || !beta || C > 1024)) return DA_EINVAL;
   if (rows == 0) return DA_OK;
-  const long M = (long)rows * L;
-  if (M >= 0x7fffffffl) return DA_EINVAL;
-  ConvBf16Args a;
-  a.x = x; a.w = reinterpret_cast<const __bf16*>(wpk); a.y = y;
-  a.M = (int)M; a.L = L; a.ldx = ldx; a.C = C; a.ldy = ldy; a.N = N; a.accumulate = 0;
-  a.divL = make_fastdiv((uint32_t)L);
   a.Wn = R * L; a.stat_part = stat_part; a.in_pend = in_pend; a.in_mean = in_mean; a.in_invstd = in_invstd;
-  a.in_gamma = gamma; a.in_beta = beta; a.in_tiles = (int)((M + 63) / 64); a.in_eps = eps;
-  const long tiles = ((M + CB_TM - 1) / CB_TM) * (N / CB_TN);
-  if (tiles > 0x7fffffffl) return DA_EINVAL;
+  a.in_gamma = gamma; a.in_beta = beta; a.in_tiles = (int)(((long)a.M + 63) / 64); a.in_eps = eps;
   const size_t shm = in_pend ? (size_t)4 * C * sizeof(float) : 0;
 #define CB_BN_LAUNCH(ST, XF_)                                                                                           \
   DA_ACT_DISPATCH(hipLaunchKernelGGL((conv3_bf16_bn_kernel<AT, ST, XF_>), dim3((unsigned)tiles), dim3(256), shm, stream, a))

@@ -35,15 +35,6 @@
                      // vector-memory instructions queue in front of its MFMAs; 3 leaves a quarter step of cover.
 #endif
 
-// XCD-aware block order (MI355X: 8 XCDs, blocks are dealt to them round-robin, each with its own 4 MiB L2):
-// give every XCD a CONTIGUOUS chunk of the linear tile order, so that tiles which share an operand
-// panel run on the same L2 close together in time.  Bijective for any block count; affects speed only.
-__device__ __forceinline__ int xcd_linear_tile(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, s = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + s;
-}
-
 struct ConvGemmArgs {
   const float* x;
   const float* w;
@@ -196,7 +187,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvGemmArgs& a, const int 
 template <int TM, int TN, int WGM, int WGN>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs a) {
   __shared__ float lds[(TM * WGM * 32 + TN * WGN * 32) * 36];
-  conv_gemm_body<TM, TN, WGM, WGN>(a, xcd_linear_tile(blockIdx.x, gridDim.x), lds);
+  conv_gemm_body<TM, TN, WGM, WGN>(a, xcd_chunked(blockIdx.x, gridDim.x), lds);
 }
 
 template <int TM, int TN, int WGM, int WGN>
@@ -224,7 +215,7 @@ __device__ __forceinline__ void conv3_halo_body(const ConvGemmArgs& a, const int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = a.N / BN;
-  const int lin = xcd_linear_tile(block_id, nblocks);
+  const int lin = xcd_chunked(block_id, nblocks);
   const int m_blk = (lin / ntn) * BM, n_blk = (lin % ntn) * BN;
   const int lr = tid >> 3, lq = tid & 7;
   const int L = (int)a.divLm.d;
@@ -451,7 +442,7 @@ __global__ __launch_bounds__(256) void conv_gemm_tailed_kernel(ConvGemmArgs a, i
     return;
   }
   if (HALO) conv3_halo_body(a, blockIdx.x - nmini_pad, full, lds);
-  else conv_gemm_body<1, 1, 2, 2>(a, xcd_linear_tile(blockIdx.x - nmini_pad, full), lds);
+  else conv_gemm_body<1, 1, 2, 2>(a, xcd_chunked(blockIdx.x - nmini_pad, full), lds);
 }
 
 static int g_use_tail = 1;
@@ -503,7 +494,7 @@ __global__ __launch_bounds__(256) void conv_gemm_multi_kernel(ConvGemmTable t, i
   int i = 0;
   while (i + 1 < t.n && g >= t.first_block[i + 1]) ++i;      // wave-uniform
   // every problem spreads over all XCDs (a contiguous chunk of ITS tiles per XCD): problems differ in work per tile
-  conv_gemm_body<1, 1, 2, 2>(t.d[i], xcd_linear_tile(g - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
+  conv_gemm_body<1, 1, 2, 2>(t.d[i], xcd_chunked(g - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
 }
 
 static int launch_conv_multi(const ConvGemmArgs* a, int n, hipStream_t s) {
@@ -607,7 +598,7 @@ __global__ __launch_bounds__(256) void conv1x1_bn_kernel(Conv1x1BnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = a.N >> 6;
-  const int lin = xcd_linear_tile(blockIdx.x, gridDim.x);
+  const int lin = xcd_chunked(blockIdx.x, gridDim.x);
   const int m_blk = (lin / ntn) * 64, n_blk = (lin % ntn) * 64;
   const int lr = tid >> 3, lq = tid & 7;
   const int w0 = (int)fdiv((uint32_t)m_blk, a.divWn);
@@ -815,7 +806,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, const int block_i
   const int ntn = a.C / BN, ntm = a.N / BM;
   const int tiles = ntm * ntn * a.ntaps;
   // tile fastest: the tiles that re-read one position chunk of dY / X are consecutive on one XCD
-  const int lin = xcd_linear_tile(block_id, nblocks);
+  const int lin = xcd_chunked(block_id, nblocks);
   int bx = lin % tiles;
   const int split = lin / tiles;
   const int t = bx / (ntm * ntn);
@@ -1320,6 +1311,20 @@ int wgrad_plan_jobs(const da_wgrad_job* jobs, int n, int chained, WgradPlan* pla
   return DA_OK;
 }
 
+// ConvGemmArgs of one job (da_conv_gemm's argument list travels as a job too).  Refusals are the entry points' own.
+static void conv_gemm_fill(ConvGemmArgs& g, const da_conv_job& j) {
+  g.x = j.x; g.w = j.w; g.y = j.y;
+  g.x2 = j.x2 ? j.x2 : j.x; g.w2 = j.w2 ? j.w2 : j.w; g.tap_split = j.x2 ? j.tap_split : 3;
+  g.M = j.rows * j.Lm; g.Lsrc = j.Lsrc; g.ldx = j.ldx; g.C = j.C;
+  g.Ldst = j.Ldst; g.ldy = j.ldy; g.N = j.N;
+  g.dst_stride = j.dst_stride; g.dst_off = j.dst_off; g.src_stride = j.src_stride;
+  g.ntaps = j.ntaps;
+  g.so0 = j.src_off[0]; g.so1 = j.ntaps > 1 ? j.src_off[1] : 0; g.so2 = j.ntaps > 2 ? j.src_off[2] : 0;
+  g.wt0 = j.wtap[0]; g.wt1 = j.ntaps > 1 ? j.wtap[1] : 0; g.wt2 = j.ntaps > 2 ? j.wtap[2] : 0;
+  g.accumulate = j.accumulate;
+  g.divLm = make_fastdiv((uint32_t)j.Lm);
+}
+
 extern "C" {
 
 // Comparison forms the tests flip.  key 3: 0 = no half-tile tail round in the 64x64 conv launches.  key 7: 0 = the
@@ -1342,17 +1347,16 @@ int da_conv_gemm(const float* x, const float* w, float* y, int rows, int Lm, int
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;              // float activations only
   if (!x || !w || !y || rows < 0 || Lm < 1 || ntaps < 1 || ntaps > 3) return DA_EINVAL;
+  da_conv_job j = {};                            // (one source: x2 == NULL)
+  j.x = x; j.w = w; j.y = y;
+  j.rows = rows; j.Lm = Lm; j.Lsrc = Lsrc; j.ldx = ldx; j.C = C; j.Ldst = Ldst; j.ldy = ldy; j.N = N;
+  j.dst_stride = dst_stride; j.dst_off = dst_off; j.src_stride = src_stride; j.ntaps = ntaps; j.accumulate = accumulate;
+  for (int t = 0; t < ntaps; ++t) {
+    j.src_off[t] = src_off[t];
+    j.wtap[t] = wtap[t];
+  }
   ConvGemmArgs a;
-  a.x = x; a.w = w; a.y = y;
-  a.x2 = x; a.w2 = w; a.tap_split = 3;
-  a.M = rows * Lm; a.Lsrc = Lsrc; a.ldx = ldx; a.C = C;
-  a.Ldst = Ldst; a.ldy = ldy; a.N = N;
-  a.dst_stride = dst_stride; a.dst_off = dst_off; a.src_stride = src_stride;
-  a.ntaps = ntaps;
-  a.so0 = src_off[0]; a.so1 = ntaps > 1 ? src_off[1] : 0; a.so2 = ntaps > 2 ? src_off[2] : 0;
-  a.wt0 = wtap[0]; a.wt1 = ntaps > 1 ? wtap[1] : 0; a.wt2 = ntaps > 2 ? wtap[2] : 0;
-  a.accumulate = accumulate;
-  a.divLm = make_fastdiv((uint32_t)Lm);
+  conv_gemm_fill(a, j);
   return conv_gemm_dispatch(a, stream);
 }
 
@@ -1368,18 +1372,8 @@ int da_conv_gemm_multi(const da_conv_job* jobs, int n, hipStream_t stream) {
     if (!j.x || !j.w || !j.y || j.rows < 0 || j.Lm < 1 || j.ntaps < 1 || j.ntaps > 3 || j.C % 32 || j.N % 64 || j.ldx % 4)
       return DA_EINVAL;
     if ((uint64_t)j.rows * j.Lm * (uint64_t)j.Lm >= 0xffffffffull) return DA_EINVAL;
-    ConvGemmArgs& g = a[i];
-    g.x = j.x; g.w = j.w; g.y = j.y;
-    g.x2 = j.x2 ? j.x2 : j.x; g.w2 = j.w2 ? j.w2 : j.w; g.tap_split = j.x2 ? j.tap_split : 3;
     if (j.x2 && (!j.w2 || j.tap_split < 1 || j.tap_split >= j.ntaps)) return DA_EINVAL;
-    g.M = j.rows * j.Lm; g.Lsrc = j.Lsrc; g.ldx = j.ldx; g.C = j.C;
-    g.Ldst = j.Ldst; g.ldy = j.ldy; g.N = j.N;
-    g.dst_stride = j.dst_stride; g.dst_off = j.dst_off; g.src_stride = j.src_stride;
-    g.ntaps = j.ntaps;
-    g.so0 = j.src_off[0]; g.so1 = j.ntaps > 1 ? j.src_off[1] : 0; g.so2 = j.ntaps > 2 ? j.src_off[2] : 0;
-    g.wt0 = j.wtap[0]; g.wt1 = j.ntaps > 1 ? j.wtap[1] : 0; g.wt2 = j.ntaps > 2 ? j.wtap[2] : 0;
-    g.accumulate = j.accumulate;
-    g.divLm = make_fastdiv((uint32_t)j.Lm);
+    conv_gemm_fill(a[i], j);
   }
   return launch_conv_multi(a, n, stream);
 }

@@ -52,20 +52,6 @@ struct WinoArgs {
   float in_eps;
 };
 
-__device__ __forceinline__ uint32_t wino_mix32(uint32_t a, uint32_t b) {      // head_optim.hip mix32
-  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
-  h ^= h >> 16; h *= 0x85EBCA6Bu;
-  h ^= h >> 13; h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-
-__device__ __forceinline__ int xcd_chunked(int id, int total) {   // same block order as conv_gemm.hip
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, s = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + s;
-}
-
 // MFMA row (0..15) -> row of the 16-row tile it holds: rows 4..11 the even ones, 0..3 and 12..15 the odd ones
 __device__ __forceinline__ int wino_row(int i) {
   return (i >= 4 && i < 12) ? 2 * (i - 4) : (i < 4 ? 2 * i + 1 : 2 * (i - 12) + 9);
@@ -268,7 +254,7 @@ __device__ __forceinline__ void conv3_wino_body(const WinoArgs& a, const int til
   float dscale = 1.f;
   if (drop) {
     const long long sd = a.drop_seed[0];
-    dkey = wino_mix32((uint32_t)sd ^ (uint32_t)(sd >> 32), a.drop_salt);
+    dkey = mix32((uint32_t)sd ^ (uint32_t)(sd >> 32), a.drop_salt);
     dthr = (uint32_t)(a.drop_p * 4294967296.0);
     dscale = 1.0f / (1.0f - a.drop_p);
   }
@@ -291,8 +277,8 @@ __device__ __forceinline__ void conv3_wino_body(const WinoArgs& a, const int til
       float y1 = acc[1][nt][r] - acc[2][nt][r] - acc[3][nt][r];
       if (drop) {                                        // element (position, channel) of the contiguous [rows L][N] tensor
         const size_t e0 = ((size_t)rr * a.L + 2 * i) * (size_t)a.N + n_blk + prow + nt * 16, e1 = e0 + a.N;
-        y0 = wino_mix32(dkey, (uint32_t)e0 ^ (uint32_t)(e0 >> 32) * 0x27d4eb2fu) >= dthr ? y0 * dscale : 0.f;
-        y1 = wino_mix32(dkey, (uint32_t)e1 ^ (uint32_t)(e1 >> 32) * 0x27d4eb2fu) >= dthr ? y1 * dscale : 0.f;
+        y0 = mix32(dkey, (uint32_t)e0 ^ (uint32_t)(e0 >> 32) * 0x27d4eb2fu) >= dthr ? y0 * dscale : 0.f;
+        y1 = mix32(dkey, (uint32_t)e1 ^ (uint32_t)(e1 >> 32) * 0x27d4eb2fu) >= dthr ? y1 * dscale : 0.f;
       }
       float* q0 = y0p + nt * 16;
       if (live) {
@@ -1263,40 +1249,6 @@ __global__ __launch_bounds__(256) void wino4_weight_kernel(const float* __restri
 
 extern "C" {
 
-// F(4,3) variant of da_conv3_winograd; u = 6 * N * C floats from da_wino4_weights.
-int da_conv3_winograd4(const float* x, const float* u, float* y, int rows, int L, int ldx, int C, int ldy, int N,
-                       int accumulate, hipStream_t stream) {
-  DA_ENTER();
-  if (g_act_bf16) return DA_EINVAL;              // float activations only
-  if (!x || !u || !y || rows < 0 || L < 1 || C % 32 || N % 32 || C < 32 || N < 32 || ldx % 4 || ldx < C || ldy < N)
-    return DA_EINVAL;
-  if (rows == 0) return DA_OK;
-  if ((uint64_t)rows * L * (uint64_t)(ldx > ldy ? ldx : ldy) >= 0x7fffffffull) return DA_EINVAL;
-  WinoArgs a;
-  a.x = x; a.u = u; a.y = y;
-  a.L = L; a.PL = (L + 3) / 4; a.MP = rows * a.PL;        // PL / MP count quads here
-  a.ldx = ldx; a.C = C; a.ldy = ldy; a.N = N; a.accumulate = accumulate;
-  a.drop_seed = nullptr; a.drop_salt = 0u; a.drop_p = 0.f;
-  a.stat_part = nullptr; a.stat_Wu = 1;
-  a.in_pend = nullptr; a.in_mean = a.in_invstd = nullptr; a.in_gamma = a.in_beta = nullptr; a.in_tiles = 0; a.in_Wu = 1; a.in_eps = 0.f;
-  a.divPL = make_fastdiv((uint32_t)a.PL);
-  if ((uint64_t)a.MP * (uint64_t)a.PL >= 0xffffffffull) return DA_EINVAL;
-  const int tiles = ((a.MP + 63) / 64) * (N / 32);
-  const int R = tiles % 256;
-  int nmini = 0, full = tiles;
-  if (g_wino_tail && tiles > 256 && R >= 1 && R <= 128) {
-    nmini = 2 * R;
-    full = tiles - R;
-  }
-  const int nmini_pad = (nmini + 7) / 8 * 8;
-  if (g_wino4_k16)
-    hipLaunchKernelGGL(conv3_wino4k_kernel, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
-  else
-    hipLaunchKernelGGL(conv3_wino4_kernel, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
-}
-
 int da_wino4_weights(const float* w, float* u, int co, int ci, int transpose, hipStream_t stream) {
   DA_ENTER();
   if (!w || !u || co < 1 || ci < 1) return DA_EINVAL;
@@ -1313,18 +1265,20 @@ struct WinoBnIn {       // the XFW operands of conv3_winograd_impl (in_pend == N
   const float* pend; float* mean; float* invstd; const float* gamma; const float* beta; float eps;
 };
 
+// outs: outputs per tile unit -- 2: F(2,3) on pairs, 4: F(4,3) on quads (PL / MP count them; plain input and output only)
 static int conv3_winograd_impl(const float* x, const float* u, float* y, int rows, int L, int ldx, int C, int ldy, int N,
                                int accumulate, const long long* drop_seed, unsigned drop_salt, float drop_p, float* stat_part,
-                               int stat_R, hipStream_t stream, const WinoBnIn* bn = nullptr) {
+                               int stat_R, hipStream_t stream, const WinoBnIn* bn = nullptr, int outs = 2) {
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;              // float activations only
+  if (outs == 4 && (stat_part || bn || drop_p > 0.f)) return DA_EINVAL;   // (no public entry asks: the F(2,3) bodies only)
   if (!x || !u || !y || rows < 0 || L < 1 || C % 32 || N % 32 || C < 32 || N < 32 || ldx % 4 || ldx < C || ldy < N)
     return DA_EINVAL;
   if (rows == 0) return DA_OK;
   if ((uint64_t)rows * L * (uint64_t)(ldx > ldy ? ldx : ldy) >= 0x7fffffffull) return DA_EINVAL;   // 32-bit element offsets
   WinoArgs a;
   a.x = x; a.u = u; a.y = y;
-  a.L = L; a.PL = (L + 1) / 2; a.MP = rows * a.PL;
+  a.L = L; a.PL = (L + outs - 1) / outs; a.MP = rows * a.PL;
   a.ldx = ldx; a.C = C; a.ldy = ldy; a.N = N; a.accumulate = accumulate;
   a.drop_seed = drop_seed; a.drop_salt = drop_salt; a.drop_p = drop_p;
   a.stat_part = stat_part; a.stat_Wu = (stat_part || bn) ? stat_R * a.PL : 1;
@@ -1347,7 +1301,11 @@ static int conv3_winograd_impl(const float* x, const float* u, float* y, int row
     full = tiles - R;
   }
   const int nmini_pad = (nmini + 7) / 8 * 8;
-  if (bn && stat_part) hipLaunchKernelGGL(conv3_wino_bn_kernel<true>, dim3(full), dim3(256), 0, stream, a, full);
+  if (outs == 4 && g_wino4_k16)
+    hipLaunchKernelGGL(conv3_wino4k_kernel, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
+  else if (outs == 4)
+    hipLaunchKernelGGL(conv3_wino4_kernel, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
+  else if (bn && stat_part) hipLaunchKernelGGL(conv3_wino_bn_kernel<true>, dim3(full), dim3(256), 0, stream, a, full);
   else if (bn) hipLaunchKernelGGL(conv3_wino_bn_kernel<false>, dim3(full), dim3(256), 0, stream, a, full);
   else if (stat_part) hipLaunchKernelGGL(conv3_wino_stats_kernel, dim3(full), dim3(256), 0, stream, a, full);
   else if (dropping) hipLaunchKernelGGL(conv3_wino_drop_kernel, dim3(full), dim3(256), 0, stream, a, full);
@@ -1359,6 +1317,12 @@ static int conv3_winograd_impl(const float* x, const float* u, float* y, int row
 int da_conv3_winograd(const float* x, const float* u, float* y, int rows, int L, int ldx, int C, int ldy, int N,
                       int accumulate, hipStream_t stream) {
   return conv3_winograd_impl(x, u, y, rows, L, ldx, C, ldy, N, accumulate, nullptr, 0u, 0.f, nullptr, 0, stream);
+}
+
+// F(4,3) variant of da_conv3_winograd; u = 6 * N * C floats from da_wino4_weights.
+int da_conv3_winograd4(const float* x, const float* u, float* y, int rows, int L, int ldx, int C, int ldy, int N,
+                       int accumulate, hipStream_t stream) {
+  return conv3_winograd_impl(x, u, y, rows, L, ldx, C, ldy, N, accumulate, nullptr, 0u, 0.f, nullptr, 0, stream, nullptr, 4);
 }
 
 // da_conv3_winograd followed by F.dropout(p) in the epilogue: y = dropout(conv(x)) with the keep mask of da_dropout

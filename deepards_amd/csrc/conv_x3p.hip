@@ -33,12 +33,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define XP_PITCH 112
 #define XP_BCHUNK (18 * 1024)                       // bytes of one (64-channel tile, K step) weight chunk
 
-__device__ __forceinline__ int xcd_chunked_xp(int id, int total) {   // consecutive work items share an XCD (conv_gemm.hip)
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, s = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + s;
-}
-
 // LDS fragment reads the compiler does not track (it would wait for ALL outstanding LDS reads in front of every MFMA group):
 // the K loop issues the reads of the next group, then waits -- by count -- for the current group's only.
 __device__ __forceinline__ f32x4 lds_read16(const unsigned char* p) {
@@ -265,10 +259,10 @@ __global__ __launch_bounds__(512, 1) void conv3_x3p_dma_kernel(ConvX3pArgs a) {
   const int ntn = a.N / XP_TN;
   const int tail_blocks = 4 * a.tail_m * ntn;
   if ((int)blockIdx.x < tail_blocks) {
-    const int id = xcd_chunked_xp(blockIdx.x, tail_blocks);
+    const int id = xcd_chunked(blockIdx.x, tail_blocks);
     conv3_x3p_dma_body<1, 2>(a, a.full_m * XP_TM + (id / ntn) * 64, (id % ntn) * XP_TN, lds);
   } else {
-    const int tile = xcd_chunked_xp(blockIdx.x - tail_blocks, a.full_m * ntn);
+    const int tile = xcd_chunked(blockIdx.x - tail_blocks, a.full_m * ntn);
     conv3_x3p_dma_body<2, 4>(a, (tile / ntn) * XP_TM, (tile % ntn) * XP_TN, lds);
   }
 }
@@ -473,10 +467,10 @@ __global__ __launch_bounds__(512, 1) void conv_x3p_s2_kernel(ConvX3pS2Args a) {
   const int ntn = a.N / XP_TN;
   const int tail_blocks = 2 * a.tail_m * ntn;
   if ((int)blockIdx.x < tail_blocks) {
-    const int id = xcd_chunked_xp(blockIdx.x, tail_blocks);
+    const int id = xcd_chunked(blockIdx.x, tail_blocks);
     conv_x3p_s2_body<DGRAD, 2>(a, a.full_m * 128 + (id / ntn) * 64, (id % ntn) * XP_TN, lds);
   } else {
-    const int tile = xcd_chunked_xp(blockIdx.x - tail_blocks, a.full_m * ntn);
+    const int tile = xcd_chunked(blockIdx.x - tail_blocks, a.full_m * ntn);
     conv_x3p_s2_body<DGRAD, 4>(a, (tile / ntn) * 128, (tile % ntn) * XP_TN, lds);
   }
 }

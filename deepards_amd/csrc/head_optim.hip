@@ -662,13 +662,6 @@ __global__ __launch_bounds__(256) void slice_copy_kernel(const float* __restrict
 
 // counter-based keep mask: keep iff hash(seed, idx) >= p * 2^32; y = x * keep / (1-p).  The mask is
 // regenerated from (seed, idx) in backward, nothing is stored.
-__device__ __forceinline__ uint32_t mix32(uint32_t a, uint32_t b) {
-  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
-  h ^= h >> 16; h *= 0x85EBCA6Bu;
-  h ^= h >> 13; h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n,
                                                       const int64_t* __restrict__ seed_ptr, uint32_t salt, float p) {
   const uint32_t seed = (uint32_t)seed_ptr[0] ^ (uint32_t)(seed_ptr[0] >> 32);

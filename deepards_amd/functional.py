@@ -173,6 +173,29 @@ def _conv_dgrad(dy, w, stride, pad, l_in, out=None, accumulate=False):
     return fn(dy, pk, out=out, accumulate=accumulate)
 
 
+def _entry_fwd(entry, x, x3, w1, wd, stride):
+    """(y1, yd) of a stride-2 block entry -- conv1 and the 1x1 downsample conv read the same input -- in the ONE launch of the
+    kernel ``entry`` (H.s2_entry_kernel: X3 on the x3 input, BF16, DIRECT)."""
+    if entry == H.X3:
+        return H.conv_x3p_s2_fwd(x3, _pack(w1, H.X3)[2], _pack(wd, H.X3)[2])
+    if entry == H.BF16:
+        return H.conv_fwd_bf16_s2(x, _pack(w1, H.BF16)[2], _pack(wd, H.BF16)[2])
+    return H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 1), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
+
+
+def _entry_dgrad(entry, dy1, w1, dyd, wd, stride, lin):
+    """dx = conv1's data gradient + the downsample conv's, in the one launch of the entry form the forward chose -- or as
+    two launches, the second accumulating: ``entry`` None (separate convs), or BF16 with _BF16_DGRAD_PAIR off."""
+    if entry == H.X3:
+        return H.conv_x3p_s2_dgrad(dy1, _pack(w1, H.X3)[3], dyd, _pack(wd, H.X3)[3])
+    if entry == H.DIRECT:
+        return H.conv_dgrad_s2_pair(dy1, _pack(w1, H.DIRECT)[1], dyd, _pack(wd, H.DIRECT)[1], lin)
+    if entry == H.BF16 and _BF16_DGRAD_PAIR:
+        return H.conv_dgrad_bf16_s2_pair(dy1, _pack(w1, H.BF16)[3], dyd, _pack(wd, H.BF16)[3], lin)
+    dx = _conv_dgrad(dy1, w1, stride, 1, lin)
+    return _conv_dgrad(dyd, wd, stride, 0, lin, out=dx, accumulate=True)
+
+
 # A captured training step may run WITHOUT the zero-fill of the gradient bucket: every gradient destination is then written
 # exactly once, by a writer that has an overwrite form (the step's queued folds / slab reductions, the fused head).  The
 # trainer learns whether that holds from the eager warm-up pass in front of the capture (_OV['ok'] stays True) and switches
@@ -473,16 +496,12 @@ class BasicBlockFunction(Function):
         fuse1 = _BN1_FUSED and not in3 and stride == 1 and R * x.shape[1] >= 130 and x.shape[0] % R == 0 and \
             want1 == H.BF16 and want2 == H.BF16 and H.bn_single_pass(x.shape[0] // R, R * x.shape[1], w1.shape[0])
         ctx.fuse1, ctx.entry = fuse1, entry
-        if entry == H.X3:  # the stride-2 block entry on the pre-split input: conv1 and the downsample conv in one launch
-            y1, yd = H.conv_x3p_s2_fwd(x3, _pack(w1, H.X3)[2], _pack(wd, H.X3)[2])
+        if pair:          # the stride-2 conv and the 1x1 downsample read the same input: one launch
+            y1, yd = _entry_fwd(entry, x, x3, w1, wd, stride)
         elif in3:         # k3 s1 conv on the pre-split input
             y1 = _conv_fwd(x3, w1, 1, 1)
         elif fuse1:       # conv dtype bf16, stride 1: the statistics records of y1 come out of the conv's epilogue
             y1, rec1 = H.conv3_bf16_bn(x, _pack(w1, H.BF16)[2], R, want_records=True)
-        elif entry == H.BF16:     # conv dtype bf16: the same shared launch on the bf16 kernel
-            y1, yd = H.conv_fwd_bf16_s2(x, _pack(w1, H.BF16)[2], _pack(wd, H.BF16)[2])
-        elif pair:        # the stride-2 conv and the 1x1 downsample read the same input: one launch
-            y1, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 1), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
         else:
             y1 = _conv_fwd(x, w1, stride, 1)
         mid3 = H.x3_block_ok(y1.shape[0], y1.shape[1], y1.shape[2], R) and want2 == H.X3
@@ -612,15 +631,7 @@ class BasicBlockFunction(Function):
         dw1 = _wgrad(dy1, x, 3, stride, 1, tw1)
         if ctx.has_ds:
             dwd = _wgrad(dyd, x, 1, stride, 0, twd)
-            if ctx.entry == H.X3:   # the entry form the forward chose
-                dx = H.conv_x3p_s2_dgrad(dy1, _pack(w1, H.X3)[3], dyd, _pack(wd, H.X3)[3])
-            elif ctx.entry == H.DIRECT:
-                dx = H.conv_dgrad_s2_pair(dy1, _pack(w1, H.DIRECT)[1], dyd, _pack(wd, H.DIRECT)[1], lin)
-            elif ctx.entry == H.BF16 and _BF16_DGRAD_PAIR:    # conv dtype bf16: the same shared launch (two sources in the even problem)
-                dx = H.conv_dgrad_bf16_s2_pair(dy1, _pack(w1, H.BF16)[3], dyd, _pack(wd, H.BF16)[3], lin)
-            else:
-                dx = _conv_dgrad(dy1, w1, stride, 1, lin)
-                _conv_dgrad(dyd, wd, stride, 0, lin, out=dx, accumulate=True)
+            dx = _entry_dgrad(ctx.entry, dy1, w1, dyd, wd, stride, lin)    # the entry form the forward chose
         else:
             dwd = dgd = dbd = None
             if ctx.split_dx and _STEP['on'] and not in3 and g is not None:

@@ -93,6 +93,18 @@ def _ints(vals):
     return (ctypes.c_int * len(vals))(*vals)
 
 
+def _out(out, shape, dtype, device, accumulate, who, alloc=torch.empty, strict=False):
+    """The destination of a wrapper: ``out`` if given (its shape must fit; strict: float-exact dtype and contiguous too), or
+    a new tensor -- which an accumulating call cannot have."""
+    if out is None:
+        if accumulate:
+            raise ValueError('%s: accumulate needs out' % who)
+        return alloc(tuple(shape), device=device, dtype=dtype)
+    if tuple(out.shape) != tuple(shape) or (strict and (out.dtype != dtype or not out.is_contiguous())):
+        raise ValueError('%s: bad out %s %s, expected %s' % (who, tuple(out.shape), out.dtype, tuple(shape)))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution
 # ------------------------------------------------------------------------------------------------
@@ -119,10 +131,7 @@ def conv_fwd(x, wf, stride, pad, out=None):
     if c != ci or ci % 32 or co % 32:
         raise ValueError('conv_fwd: unsupported shape x%s wf%s' % (tuple(x.shape), tuple(wf.shape)))
     lo = conv_out_len(l, k, stride, pad)
-    if out is None:
-        out = torch.empty((rows, lo, co), device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, lo, co):
-        raise ValueError('conv_fwd: bad out shape')
+    out = _out(out, (rows, lo, co), torch.float32, x.device, False, 'conv_fwd')
     ldy = _pv(out, 'out')
     so = [t - pad for t in range(k)]
     wt = list(range(k))
@@ -161,12 +170,7 @@ def conv3_winograd(x, u, out=None, accumulate=False, drop=None, stats_R=0):
     four, n, c2 = u.shape
     if four not in (4, 6) or c2 != c or c % 32 or n % 32:
         raise ValueError('conv3_winograd: unsupported shape x%s u%s' % (tuple(x.shape), tuple(u.shape)))
-    if out is None:
-        if accumulate:
-            raise ValueError('accumulate needs out')
-        out = torch.empty((rows, l, n), device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, l, n):
-        raise ValueError('conv3_winograd: bad out shape')
+    out = _out(out, (rows, l, n), torch.float32, x.device, accumulate, 'conv3_winograd')
     ldy = _pv(out, 'out') if out.dtype == torch.float32 else n
     if (drop is not None and drop[2] > 0) or stats_R:
         if four != 4 or accumulate:
@@ -221,19 +225,11 @@ def conv3_bf16(x, wpk, out=None, accumulate=False):
     """k3 s1 p1 conv of x (rows, L, C) fp32 with bf16 taps wpk (3, N, C): bf16 products, fp32 sums -> (rows, L, N)."""
     _rlc(x, 'x')
     rows, l, c = x.shape
-    three, n, c2 = wpk.shape
-    if three != 3 or c2 != c or c % 32 or n % 64 or wpk.dtype != torch.bfloat16 or not wpk.is_contiguous():
-        raise ValueError('conv3_bf16: unsupported shape x%s w%s' % (tuple(x.shape), tuple(wpk.shape)))
-    if out is None:
-        if accumulate:
-            raise ValueError('accumulate needs out')
-        out = torch.empty((rows, l, n), device=x.device, dtype=ACT)
-    elif tuple(out.shape) != (rows, l, n):
-        raise ValueError('conv3_bf16: bad out shape')
+    _, n = _check_bf16_pack(x, wpk, 'conv3_bf16', ks=(3,))
+    out = _out(out, (rows, l, n), ACT, x.device, accumulate, 'conv3_bf16')
     _chk(_lib.lib().da_conv3_bf16(_p(x), _p(wpk), _p(out), rows, l, c, c, n, n, 1 if accumulate else 0, _stream()),
          'da_conv3_bf16')
     return out
-
 
 
 def conv3_bf16_bn(x, wpk, R, rec=None, mean=None, invstd=None, gamma=None, beta=None, eps=1e-5, want_records=False):
@@ -242,9 +238,9 @@ def conv3_bf16_bn(x, wpk, R, rec=None, mean=None, invstd=None, gamma=None, beta=
     staged; want_records: -> (out, records of the output as stored; units = positions)."""
     _rlc(x, 'x')
     rows, l, c = x.shape
-    three, n, c2 = wpk.shape
-    if three != 3 or c2 != c or c % 32 or n % 64 or wpk.dtype != torch.bfloat16 or not wpk.is_contiguous() or rows % R:
-        raise ValueError('conv3_bf16_bn: unsupported shape x%s w%s' % (tuple(x.shape), tuple(wpk.shape)))
+    _, n = _check_bf16_pack(x, wpk, 'conv3_bf16_bn', ks=(3,))
+    if rows % R:
+        raise ValueError('conv3_bf16_bn: %d rows are no whole windows of %d' % (rows, R))
     L = _lib.lib()
     if rec is not None:
         w = rows // R
@@ -279,11 +275,16 @@ def x3_split(x):
     return out
 
 
+def _x3(t, who):
+    """A contiguous x3 CUDA tensor -> (rows, L, channel groups of 16)."""
+    if not (is_x3(t) and t.is_cuda and t.is_contiguous()):
+        raise ValueError('%s: a contiguous x3 CUDA tensor expected, got %s %s' % (who, tuple(t.shape), t.dtype))
+    return tuple(t.shape[:3])
+
+
 def x3_merge(x3):
     """x3 (rows, L, C/16, 3, 16) -> fp32 (rows, L, C) = h + m + l (exact)."""
-    if not (is_x3(x3) and x3.is_cuda and x3.is_contiguous()):
-        raise ValueError('x3_merge: a contiguous x3 CUDA tensor expected')
-    rows, l, g = x3.shape[:3]
+    rows, l, g = _x3(x3, 'x3_merge')
     out = torch.empty((rows, l, g * 16), device=x3.device, dtype=torch.float32)
     _chk(_lib.lib().da_x3_merge(_p(x3), _p(out), g * 16, rows * l, g * 16, _stream()), 'da_x3_merge')
     return out
@@ -292,20 +293,13 @@ def x3_merge(x3):
 def conv3_x3p(x3, wpk, out=None, accumulate=False):
     """k3 s1 p1 conv of an x3 activation (rows, L, C/16, 3, 16) with the chunked split-bf16 pack wpk (N/64, C/16, 18, 64, 8)
     (repack_multi form X3): fp32-equivalent products on the bf16 matrix cores, fp32 sums -> (rows, L, N) fp32."""
-    if not (is_x3(x3) and x3.is_cuda and x3.is_contiguous()):
-        raise ValueError('conv3_x3p: a contiguous x3 CUDA tensor expected, got %s %s' % (tuple(x3.shape), x3.dtype))
-    rows, l, g = x3.shape[:3]
+    rows, l, g = _x3(x3, 'conv3_x3p')
     c = g * 16
     if wpk.dim() != 5 or wpk.shape[1] != g or tuple(wpk.shape[2:]) != (18, 64, 8) or wpk.dtype != torch.bfloat16 or \
             not wpk.is_contiguous():
         raise ValueError('conv3_x3p: unsupported shape x%s w%s' % (tuple(x3.shape), tuple(wpk.shape)))
     n = wpk.shape[0] * 64
-    if out is None:
-        if accumulate:
-            raise ValueError('accumulate needs out')
-        out = torch.empty((rows, l, n), device=x3.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, l, n) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError('conv3_x3p: bad out')
+    out = _out(out, (rows, l, n), torch.float32, x3.device, accumulate, 'conv3_x3p', strict=True)
     _chk(_lib.lib().da_conv3_x3p(_p(x3), _p(wpk), _p(out), rows, l, c, n, n, 1 if accumulate else 0, _stream()),
          'da_conv3_x3p')
     return out
@@ -319,9 +313,7 @@ def conv_x3p_s2_fwd(x3, w1pk, wdpk):
     """The stride-2 block entry on x3 operands: (y1, yd) = (conv k3 s2 p1, conv 1x1 s2) of the x3 activation
     (rows, Lin, C/16, 3, 16), Lin even, from ONE read of it.  w1pk / wdpk: forward packs of repack_multi form X3
     (N/64, C/16, 18, 64, 8), the 1x1 weights packed with K = 1 (tap 1 of the chunks)."""
-    if not (is_x3(x3) and x3.is_cuda and x3.is_contiguous()):
-        raise ValueError('conv_x3p_s2_fwd: a contiguous x3 CUDA tensor expected')
-    rows, lin, g = x3.shape[:3]
+    rows, lin, g = _x3(x3, 'conv_x3p_s2_fwd')
     if lin % 2 or not _x3p_pack_ok(w1pk, w1pk.shape[0], g) or not _x3p_pack_ok(wdpk, w1pk.shape[0], g):
         raise ValueError('conv_x3p_s2_fwd: unsupported shape x%s w1%s wd%s' % (tuple(x3.shape), tuple(w1pk.shape), tuple(wdpk.shape)))
     n = w1pk.shape[0] * 64
@@ -334,37 +326,69 @@ def conv_x3p_s2_fwd(x3, w1pk, wdpk):
 def conv_x3p_s2_dgrad(dy1_3, w1pk, dyd_3, wdpk, out=None):
     """dx (rows, 2 Lout, C) fp32 = the data gradients of the two convs of conv_x3p_s2_fwd, summed; dy1_3 / dyd_3 x3
     activations (rows, Lout, N/16, 3, 16), packs: the DATA-GRADIENT side of repack_multi form X3 (C/64, N/16, 18, 64, 8)."""
-    for t in (dy1_3, dyd_3):
-        if not (is_x3(t) and t.is_cuda and t.is_contiguous()):
-            raise ValueError('conv_x3p_s2_dgrad: contiguous x3 CUDA tensors expected')
-    rows, lout, g = dy1_3.shape[:3]
+    _x3(dyd_3, 'conv_x3p_s2_dgrad')
+    rows, lout, g = _x3(dy1_3, 'conv_x3p_s2_dgrad')
     if tuple(dyd_3.shape) != tuple(dy1_3.shape) or not _x3p_pack_ok(w1pk, w1pk.shape[0], g) or not _x3p_pack_ok(wdpk, w1pk.shape[0], g):
         raise ValueError('conv_x3p_s2_dgrad: unsupported shapes')
     c = w1pk.shape[0] * 64
-    if out is None:
-        out = torch.empty((rows, 2 * lout, c), device=dy1_3.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, 2 * lout, c) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError('conv_x3p_s2_dgrad: bad out')
+    out = _out(out, (rows, 2 * lout, c), torch.float32, dy1_3.device, False, 'conv_x3p_s2_dgrad', strict=True)
     _chk(_lib.lib().da_conv_x3p_s2_dgrad(_p(dy1_3), _p(w1pk), _p(dyd_3), _p(wdpk), _p(out), rows, lout, g * 16, c, _stream()),
          'da_conv_x3p_s2_dgrad')
     return out
 
 
-def _conv_bf16_multi(jobs):
-    """jobs: [(x, wpk, out, lm, lsrc, ldst, dst_stride, dst_off, src_stride, src_off, wtap, accumulate)] in one call."""
-    arr = (_lib.ConvJob * len(jobs))()
-    for d, (x, wpk, out, lm, lsrc, ldst, dst_stride, dst_off, src_stride, so, wt, acc) in zip(arr, jobs):
-        rows, _, c = x.shape
-        n = wpk.shape[1]
-        _conv_job(d, x, wpk, out, rows, lm, lsrc, c, c, ldst, n, n, dst_stride, dst_off, src_stride, so, wt, acc)
-    _chk(_lib.lib().da_conv_bf16_multi(arr, len(jobs), _stream()), 'da_conv_bf16_multi')
-
-
-def _check_bf16_pack(x, w16, name):
+def _check_bf16_pack(x, w16, name, ks=(1, 3)):
     k, n, c2 = w16.shape
-    if k not in (1, 3) or c2 != x.shape[2] or c2 % 32 or n % 64 or w16.dtype != torch.bfloat16 or not w16.is_contiguous():
+    if k not in ks or c2 != x.shape[2] or c2 % 32 or n % 64 or w16.dtype != torch.bfloat16 or not w16.is_contiguous():
         raise ValueError('%s: unsupported shape x%s w%s' % (name, tuple(x.shape), tuple(w16.shape)))
     return k, n
+
+
+def _s2_entry_rows(form, k=3, tap_reversed=False):
+    """The geometry of a stride-2 block entry (k3 s2 p1 conv + 1x1 s2 p0 downsample, even input length) as job rows
+    (dst_stride, dst_off, src_stride, src_off, wtap, tap_split) -- integers only.  ``form``:
+    'fwd': the forward of the conv with ``k`` taps (one row);
+    'dgrad': that conv's data gradient, the even input positions, then (k3) the odd ones;
+    'dgrad_pair': both convs' data gradients summed: the odd positions, then the even ones as one contraction over two
+    sources (tap_split 1: row tap 0 reads dy1 with the conv's pack, row tap 1 reads dyd with the downsample's).
+    ``tap_reversed``: the data-gradient pack holds the taps in reverse order (the bf16 packs: pack tap t = w's tap 2 - t);
+    the direct packs (K, Ci, Co) keep w's order."""
+    if form == 'fwd':                                # y[j] = sum_t x[2j + t - pad] w[t], pad = k // 2
+        return [(1, 0, 2, [t - k // 2 for t in range(k)], list(range(k)), 0)]
+    # dx[2j + r] takes dy[i] through w's tap t where 2i - pad + t = 2j + r.  Even positions (r = 0): the centre tap, i = j
+    # (the centre of a reversed pack is the centre)
+    even = (2, 0, 1, [0], [k // 2], 0)
+    if k == 1:
+        return [even]
+    # odd positions (r = 1): w's tap 0 reads dy[j + 1], w's tap 2 reads dy[j].  Pack taps [0, 2] are w's taps [0, 2] in a
+    # direct pack -> offsets [1, 0]; in a tap-reversed pack they are w's taps [2, 0] -> offsets [0, 1]
+    odd = (2, 1, 1, [0, 1] if tap_reversed else [1, 0], [0, 2], 0)
+    if form == 'dgrad':
+        return [even, odd]
+    return [odd, (2, 0, 1, [0, 0], [1, 0], 1)]
+
+
+def _conv_job(d, x, w, y, rows, lm, lsrc, ldx, c, ldst, ldy, n, dst_stride, dst_off, src_stride, so, wt, accumulate,
+              x2=None, w2=None, tap_split=0):
+    d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
+    d.x2, d.w2, d.tap_split = _p(x2), _p(w2), tap_split
+    d.rows, d.Lm, d.Lsrc, d.ldx, d.C, d.Ldst, d.ldy, d.N = rows, lm, lsrc, ldx, c, ldst, ldy, n
+    d.dst_stride, d.dst_off, d.src_stride, d.ntaps = dst_stride, dst_off, src_stride, len(so)
+    for t in range(3):
+        d.src_off[t] = so[t] if t < len(so) else 0
+        d.wtap[t] = wt[t] if t < len(wt) else 0
+    d.accumulate = 1 if accumulate else 0
+
+
+def _conv_jobs(fn, name, jobs):
+    """jobs: [(x, w, y, lm, row, accumulate[, x2, w2])] on contiguous tensors, row as _s2_entry_rows gives it: ONE launch
+    of ``fn`` (da_conv_gemm_multi / da_conv_bf16_multi)."""
+    arr = (_lib.ConvJob * len(jobs))()
+    for d, (x, w, y, lm, row, acc, *two) in zip(arr, jobs):
+        rows, lsrc, c = x.shape
+        ldst, n = y.shape[1:]
+        _conv_job(d, x, w, y, rows, lm, lsrc, c, c, ldst, n, n, *row[:5], acc, *two, tap_split=row[5])
+    _chk(fn(arr, len(jobs), _stream()), name)
 
 
 def conv_fwd_bf16_s2(x, *packs):
@@ -374,15 +398,13 @@ def conv_fwd_bf16_s2(x, *packs):
     rows, l, c = x.shape
     if l % 2 or not packs:
         raise ValueError('conv_fwd_bf16_s2: even length and at least one pack expected')
-    jobs, outs = [], []
+    jobs = []
     for wf16 in packs:
         k, n = _check_bf16_pack(x, wf16, 'conv_fwd_bf16_s2')
         out = torch.empty((rows, l // 2, n), device=x.device, dtype=ACT)
-        so, wt = ([-1, 0, 1], [0, 1, 2]) if k == 3 else ([0], [0])
-        jobs.append((x, wf16, out, l // 2, l, l // 2, 1, 0, 2, so, wt, False))
-        outs.append(out)
-    _conv_bf16_multi(jobs)
-    return outs[0] if len(outs) == 1 else outs
+        jobs.append((x, wf16, out, l // 2, _s2_entry_rows('fwd', k)[0], False))
+    _conv_jobs(_lib.lib().da_conv_bf16_multi, 'da_conv_bf16_multi', jobs)
+    return jobs[0][2] if len(jobs) == 1 else [j[2] for j in jobs]
 
 
 def conv_dgrad_bf16_s2(dy, wd16, l_in, out=None, accumulate=False):
@@ -394,19 +416,12 @@ def conv_dgrad_bf16_s2(dy, wd16, l_in, out=None, accumulate=False):
     k, ci = _check_bf16_pack(dy, wd16, 'conv_dgrad_bf16_s2')
     if l_in != 2 * lo:
         raise ValueError('conv_dgrad_bf16_s2: l_in must be twice the output length')
-    if out is None:
-        if accumulate:
-            raise ValueError('accumulate needs out')
-        out = (torch.zeros if k == 1 else torch.empty)((rows, l_in, ci), device=dy.device, dtype=ACT)
-    elif tuple(out.shape) != (rows, l_in, ci):
-        raise ValueError('conv_dgrad_bf16_s2: bad out shape')
-    elif k == 1 and not accumulate:
+    given = out is not None
+    out = _out(out, (rows, l_in, ci), ACT, dy.device, accumulate, 'conv_dgrad_bf16_s2', alloc=torch.zeros if k == 1 else torch.empty)
+    if given and k == 1 and not accumulate:
         out.zero_()
-    if k == 3:       # wd16[t'] = w[..][2 - t']: dx[2j] = dy[j] w1;  dx[2j+1] = dy[j] w2 + dy[j+1] w0
-        _conv_bf16_multi([(dy, wd16, out, lo, lo, l_in, 2, 0, 1, [0], [1], accumulate),
-                          (dy, wd16, out, lo, lo, l_in, 2, 1, 1, [0, 1], [0, 2], accumulate)])
-    else:
-        _conv_bf16_multi([(dy, wd16, out, lo, lo, l_in, 2, 0, 1, [0], [0], accumulate)])
+    _conv_jobs(_lib.lib().da_conv_bf16_multi, 'da_conv_bf16_multi',
+               [(dy, wd16, out, lo, row, accumulate) for row in _s2_entry_rows('dgrad', k, tap_reversed=True)])
     return out
 
 
@@ -422,11 +437,9 @@ def conv_dgrad_bf16_s2_pair(dy1, wd1_16, dyd, wdd_16, l_in):
     if (k1, kd) != (3, 1) or ci != ci2 or tuple(dyd.shape) != tuple(dy1.shape) or l_in != 2 * lo:
         raise ValueError('conv_dgrad_bf16_s2_pair: shapes dy1%s dyd%s' % (tuple(dy1.shape), tuple(dyd.shape)))
     out = torch.empty((rows, l_in, ci), device=dy1.device, dtype=ACT)
-    a = (_lib.ConvJob * 2)()
-    _conv_job(a[0], dy1, wd1_16, out, rows, lo, lo, co, co, l_in, ci, ci, 2, 1, 1, [0, 1], [0, 2], False)
-    _conv_job(a[1], dy1, wd1_16, out, rows, lo, lo, co, co, l_in, ci, ci, 2, 0, 1, [0, 0], [1, 0], False,
-              x2=dyd, w2=wdd_16, tap_split=1)
-    _chk(_lib.lib().da_conv_bf16_multi(a, 2, _stream()), 'da_conv_bf16_multi(dgrad pair)')
+    odd, even = _s2_entry_rows('dgrad_pair', tap_reversed=True)
+    _conv_jobs(_lib.lib().da_conv_bf16_multi, 'da_conv_bf16_multi(dgrad pair)',
+               [(dy1, wd1_16, out, lo, odd, False), (dy1, wd1_16, out, lo, even, False, dyd, wdd_16)])
     return out
 
 
@@ -438,12 +451,7 @@ def conv_dgrad(dy, wd, stride, pad, l_in, out=None, accumulate=False):
     rows, lo, c = dy.shape
     if c != co or ci % 32 or co % 32:
         raise ValueError('conv_dgrad: unsupported shape')
-    if out is None:
-        if accumulate:
-            raise ValueError('accumulate needs out')
-        out = torch.empty((rows, l_in, ci), device=dy.device, dtype=torch.float32)
-    elif tuple(out.shape) != (rows, l_in, ci):
-        raise ValueError('conv_dgrad: bad out shape')
+    out = _out(out, (rows, l_in, ci), torch.float32, dy.device, accumulate, 'conv_dgrad')
     ldo = _pv(out, 'out')
     L = _lib.lib()
     for r in range(stride):
@@ -463,26 +471,13 @@ def conv_dgrad(dy, wd, stride, pad, l_in, out=None, accumulate=False):
     return out
 
 
-def _conv_job(d, x, w, y, rows, lm, lsrc, ldx, c, ldst, ldy, n, dst_stride, dst_off, src_stride, so, wt, accumulate,
-              x2=None, w2=None, tap_split=0):
-    d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
-    d.x2, d.w2, d.tap_split = _p(x2), _p(w2), tap_split
-    d.rows, d.Lm, d.Lsrc, d.ldx, d.C, d.Ldst, d.ldy, d.N = rows, lm, lsrc, ldx, c, ldst, ldy, n
-    d.dst_stride, d.dst_off, d.src_stride, d.ntaps = dst_stride, dst_off, src_stride, len(so)
-    for t in range(3):
-        d.src_off[t] = so[t] if t < len(so) else 0
-        d.wtap[t] = wt[t] if t < len(wt) else 0
-    d.accumulate = 1 if accumulate else 0
-
-
 def conv_fwd_multi(problems):
     """[(x, wf, stride, pad)] (<= 4, Co % 64 == 0) -> [y]: independent forward convs in ONE launch (a block's stride-2
     conv and its 1x1 downsample read the same input; alone each has 2-4 tiles per CU)."""
     if len(problems) > 4 or any(wf.shape[1] % 64 for _, wf, _, _ in problems):
         return [conv_fwd(x, wf, s_, p_) for x, wf, s_, p_ in problems]
-    arr = (_lib.ConvJob * len(problems))()
-    outs = []
-    for d, (x, wf, stride, pad) in zip(arr, problems):
+    jobs = []
+    for x, wf, stride, pad in problems:
         _rlc(x, 'x')
         k, co, ci = wf.shape
         rows, l, c = x.shape
@@ -490,10 +485,11 @@ def conv_fwd_multi(problems):
             raise ValueError('conv_fwd_multi: unsupported shape x%s wf%s' % (tuple(x.shape), tuple(wf.shape)))
         lo = conv_out_len(l, k, stride, pad)
         y = torch.empty((rows, lo, co), device=x.device, dtype=torch.float32)
-        _conv_job(d, x, wf, y, rows, lo, l, c, ci, lo, co, co, 1, 0, stride, [t - pad for t in range(k)], list(range(k)), False)
-        outs.append(y)
-    _chk(_lib.lib().da_conv_gemm_multi(arr, len(problems), _stream()), 'da_conv_gemm_multi(fwd)')
-    return outs
+        row = _s2_entry_rows('fwd', k)[0] if _s2_entry(k, stride, pad) else \
+            (1, 0, stride, [t - pad for t in range(k)], list(range(k)), 0)        # (any other conv: the same form)
+        jobs.append((x, wf, y, lo, row, False))
+    _conv_jobs(_lib.lib().da_conv_gemm_multi, 'da_conv_gemm_multi(fwd)', jobs)
+    return [j[2] for j in jobs]
 
 
 def conv_dgrad_s2_pair(dy1, wd1, dyd, wdd, l_in):
@@ -509,14 +505,9 @@ def conv_dgrad_s2_pair(dy1, wd1, dyd, wdd, l_in):
         dx = conv_dgrad(dy1, wd1, 2, 1, l_in)
         return conv_dgrad(dyd, wdd, 2, 0, l_in, out=dx, accumulate=True)
     dx = torch.empty((rows, l_in, ci), device=dy1.device, dtype=torch.float32)
-    lm = l_in // 2
-    a = (_lib.ConvJob * 2)()
-    # odd input positions 2j+1: taps t = 0, 2 of the k3 conv, source positions (1 + 1 - t) / 2 + j
-    _conv_job(a[0], dy1, wd1, dx, rows, lm, lo, co, co, l_in, ci, ci, 2, 1, 1, [1, 0], [0, 2], False)
-    # even input positions 2j: tap 1 of the k3 conv from dy1 AND the downsample's only tap from dyd, one contraction
-    _conv_job(a[1], dy1, wd1, dx, rows, lm, lo, co, co, l_in, ci, ci, 2, 0, 1, [0, 0], [1, 0], False,
-              x2=dyd, w2=wdd, tap_split=1)
-    _chk(_lib.lib().da_conv_gemm_multi(a, 2, _stream()), 'da_conv_gemm_multi(dgrad)')
+    odd, even = _s2_entry_rows('dgrad_pair')
+    _conv_jobs(_lib.lib().da_conv_gemm_multi, 'da_conv_gemm_multi(dgrad)',
+               [(dy1, wd1, dx, l_in // 2, odd, False), (dy1, wd1, dx, l_in // 2, even, False, dyd, wdd)])
     return dx
 
 
@@ -529,47 +520,35 @@ def conv_wgrad(dy, x, k, stride, pad, out=None, accumulate=False, defer=False):
     rows2, l, ci = x.shape
     if rows != rows2 or lo != conv_out_len(l, k, stride, pad) or ci % 32 or co % 32 or (k > 3 and defer):
         raise ValueError('conv_wgrad: unsupported shape')
-    if k > 3:         # a kernel longer than 3 taps (resnet's k7 conv2, double_conv_first only): tap groups into slices
-        if out is None:
-            if accumulate:
-                raise ValueError('accumulate needs out')
-            out = torch.empty((co, ci, k), device=x.device, dtype=torch.float32)
-        for g in range(0, k, 3):
-            n = min(3, k - g)
-            part = _conv_wgrad_taps(dy, x, [t - pad for t in range(g, g + n)], stride)
-            if accumulate:
-                out[:, :, g:g + n].add_(part)
-            else:
-                out[:, :, g:g + n].copy_(part)
-        return out
-    L = _lib.lib()
-    nbytes = L.da_conv_wgrad_workspace(rows, lo, co, ci, k)
-    ws = torch.empty((nbytes // 4,), device=x.device, dtype=torch.float32)
     so = [t - pad for t in range(k)]
     if defer:
-        _chk(L.da_conv_wgrad(_p(dy), _p(x), None, _p(ws), rows, lo, lo, co, co, l, ci, ci, 1, 0, stride, k,
-                             _ints(so), 0, _stream()), 'da_conv_wgrad')
-        return ws, L.da_conv_wgrad_splits(rows, lo, co, ci, k), k, co, ci
-    if out is None:
+        return _conv_wgrad_taps(dy, x, so, stride, defer=True), _lib.lib().da_conv_wgrad_splits(rows, lo, co, ci, k), k, co, ci
+    if out is None:             # (a given out is taken as it is)
+        out = _out(None, (co, ci, k), torch.float32, x.device, accumulate, 'conv_wgrad')
+    if k <= 3:
+        return _conv_wgrad_taps(dy, x, so, stride, out, accumulate)
+    for g in range(0, k, 3):    # a kernel longer than 3 taps (resnet's k7 conv2, double_conv_first only): tap groups into slices
+        part = _conv_wgrad_taps(dy, x, so[g:g + 3], stride)
         if accumulate:
-            raise ValueError('accumulate needs out')
-        out = torch.empty((co, ci, k), device=x.device, dtype=torch.float32)
-    _chk(L.da_conv_wgrad(_p(dy), _p(x), _p(out), _p(ws), rows, lo, lo, co, co, l, ci, ci, 1, 0, stride, k,
-                         _ints(so), 1 if accumulate else 0, _stream()), 'da_conv_wgrad')
+            out[:, :, g:g + part.shape[2]].add_(part)
+        else:
+            out[:, :, g:g + part.shape[2]].copy_(part)
     return out
 
 
-def _conv_wgrad_taps(dy, x, src_off, stride):
-    """(Co, Ci, len(src_off)) weight gradient of the taps that read x at stride * j + src_off[t]."""
+def _conv_wgrad_taps(dy, x, src_off, stride, out=None, accumulate=False, defer=False):
+    """The da_conv_wgrad launch: the (Co, Ci, len(src_off)) weight gradient of the taps that read x at stride * j + src_off[t]
+    -> out (a new tensor if None), or -- defer -- the split-K slabs alone."""
     rows, lo, co = dy.shape
     l, ci = x.shape[1], x.shape[2]
     n = len(src_off)
     L = _lib.lib()
     ws = torch.empty((L.da_conv_wgrad_workspace(rows, lo, co, ci, n) // 4,), device=x.device, dtype=torch.float32)
-    out = torch.empty((co, ci, n), device=x.device, dtype=torch.float32)
+    if out is None and not defer:
+        out = torch.empty((co, ci, n), device=x.device, dtype=torch.float32)
     _chk(L.da_conv_wgrad(_p(dy), _p(x), _p(out), _p(ws), rows, lo, lo, co, co, l, ci, ci, 1, 0, stride, n,
-                         _ints(src_off), 0, _stream()), 'da_conv_wgrad')
-    return out
+                         _ints(src_off), 1 if accumulate else 0, _stream()), 'da_conv_wgrad')
+    return ws if defer else out
 
 
 # ---- which kernel a conv runs on ---------------------------------------------------------------------------------------------
@@ -648,7 +627,8 @@ def wgrad_kernel(co, ci, k, stride, pad, l, x3=False, operand_form=False):
 
 def s2_entry_kernel(w1, wd, stride, l_in, x3):
     """How a block's conv1 (weight shape ``w1``) and downsample conv (``wd`` or None) run: in ONE launch on the X3 (``x3``: the
-    input is in the x3 format), BF16 or DIRECT kernels (a stride-2 entry: the two read the same input), or -- None -- apart."""
+    input is in the x3 format), BF16 or DIRECT kernels (a stride-2 entry: the two read the same input), or -- None -- apart.
+    functional._entry_fwd / _entry_dgrad carry the name to the launches; their job rows come from _s2_entry_rows."""
     if wd is None or stride != 2:
         return None
     if x3:                                          # even input length, channel counts multiples of 64
@@ -748,15 +728,21 @@ def conv_wgrad_multi(jobs, dws=None, accumulate=True):
     return outs
 
 
+def _reduce_descs(items, who):
+    """items: ((slab, splits, k, co, ci), dw) -> the WgradReduceDesc array of their slab reductions."""
+    arr = (_lib.WgradReduceDesc * len(items))()
+    for d, ((slab, splits, k, co, ci), dw) in zip(arr, items):
+        if tuple(dw.shape) != (co, ci, k):
+            raise ValueError('%s: bad dw shape' % who)
+        d.slab, d.dw, d.splits, d.ntaps, d.N, d.C = slab.data_ptr(), dw.data_ptr(), splits, k, co, ci
+    return arr
+
+
 def wgrad_reduce_multi(items, accumulate=True):
     """items: ((slab, splits, k, co, ci), dw) -- one launch per 32 convolutions."""
     if not items:
         return
-    arr = (_lib.WgradReduceDesc * len(items))()
-    for d, ((slab, splits, k, co, ci), dw) in zip(arr, items):
-        if tuple(dw.shape) != (co, ci, k):
-            raise ValueError('wgrad_reduce_multi: bad dw shape')
-        d.slab, d.dw, d.splits, d.ntaps, d.N, d.C = slab.data_ptr(), dw.data_ptr(), splits, k, co, ci
+    arr = _reduce_descs(items, 'wgrad_reduce_multi')
     _chk(_lib.lib().da_wgrad_reduce_multi(arr, len(items), 1 if accumulate else 0, _stream()), 'da_wgrad_reduce_multi')
 
 
@@ -782,11 +768,7 @@ def step_tail_multi(items, pgrad, running, accumulate=True, stem=None):
             part, nblk, n, dw = stem
             _chk(_lib.lib().da_stem_wgrad_reduce(_p(part), nblk, n, _p(dw), 1 if accumulate else 0, _stream()), 'da_stem_wgrad_reduce')
         return
-    arr = (_lib.WgradReduceDesc * len(items))()
-    for d, ((slab, splits, k, co, ci), dw) in zip(arr, items):
-        if tuple(dw.shape) != (co, ci, k):
-            raise ValueError('step_tail_multi: bad dw shape')
-        d.slab, d.dw, d.splits, d.ntaps, d.N, d.C = slab.data_ptr(), dw.data_ptr(), splits, k, co, ci
+    arr = _reduce_descs(items, 'step_tail_multi')
     pg = (_lib.BnPgradDesc * max(1, len(pgrad)))()
     for d, (ds, dg, db) in zip(pg, pgrad):
         _, w, c = ds.shape

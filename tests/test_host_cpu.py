@@ -738,3 +738,206 @@ def test_driver_mirror_names_and_no_cpu_path():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError, match='no CPU fallback'):
             T.CNNLinearModel(T.make_args())
+
+
+# The job rows (dst_stride, dst_off, src_stride, src_off, wtap, tap_split; ntaps = len(src_off)) the stride-2 wrappers handed
+# to the library before they took them from one geometry function -- recorded from conv_fwd_multi / conv_fwd_bf16_s2 (forward
+# pair: both give the same rows), conv_dgrad_s2_pair / conv_dgrad_bf16_s2_pair (odd problem, then the even one with two
+# sources) and conv_dgrad / conv_dgrad_bf16_s2 (single convs: even positions, then odd).  The direct packs keep w's tap order,
+# the bf16 packs come tap-reversed: the odd problem's source offsets are [1, 0] against [0, 1].
+_S2_ROWS = {
+    ('fwd', 3, False): [(1, 0, 2, [-1, 0, 1], [0, 1, 2], 0)],
+    ('fwd', 1, False): [(1, 0, 2, [0], [0], 0)],
+    ('fwd', 3, True): [(1, 0, 2, [-1, 0, 1], [0, 1, 2], 0)],
+    ('fwd', 1, True): [(1, 0, 2, [0], [0], 0)],
+    ('dgrad_pair', 3, False): [(2, 1, 1, [1, 0], [0, 2], 0), (2, 0, 1, [0, 0], [1, 0], 1)],
+    ('dgrad_pair', 3, True): [(2, 1, 1, [0, 1], [0, 2], 0), (2, 0, 1, [0, 0], [1, 0], 1)],
+    ('dgrad', 3, False): [(2, 0, 1, [0], [1], 0), (2, 1, 1, [1, 0], [0, 2], 0)],
+    ('dgrad', 3, True): [(2, 0, 1, [0], [1], 0), (2, 1, 1, [0, 1], [0, 2], 0)],
+    ('dgrad', 1, False): [(2, 0, 1, [0], [0], 0)],
+    ('dgrad', 1, True): [(2, 0, 1, [0], [0], 0)],
+}
+
+
+def test_s2_entry_geometry_is_pinned():
+    """The pure geometry function of a stride-2 block entry returns exactly the rows the wrappers spelled out one by one."""
+    from deepards_amd import hip_ops as H
+    for (form, k, rev), rows in sorted(_S2_ROWS.items()):
+        got = H._s2_entry_rows(form, k, tap_reversed=rev)
+        assert [tuple(r) for r in got] == rows, (form, k, rev, got)
+        assert [len(r[3]) for r in got] == [len(r[3]) for r in rows]          # ntaps
+        assert all(isinstance(v, int) for r in got for v in (r[0], r[1], r[2], r[5], *r[3], *r[4]))
+
+
+def test_conv_entry_refusal_codes_are_pinned():
+    """One refusal per distinct check of the convolution entry points (tests/tools/diff_conv_refusals.py holds the grid that
+    was compared with the build before their argument fills were shared): DA_EINVAL before any launch, DA_OK for no rows."""
+    import ctypes
+    from deepards_amd import _lib
+    lib = _lib.lib()
+    P = 4096                                                    # a dummy non-null address; a refusal dereferences nothing
+    E = -1
+
+    def job(**kw):
+        j = _lib.ConvJob()
+        vals = dict(x=P, w=P, y=P, rows=40, Lm=28, Lsrc=56, ldx=64, C=64, Ldst=28, ldy=64, N=64, dst_stride=1, dst_off=0,
+                    src_stride=2, ntaps=3, src_off=(-1, 0, 1), wtap=(0, 1, 2), accumulate=0, x2=None, w2=None, tap_split=0)
+        vals.update(kw)
+        for k, v in vals.items():
+            if k in ('src_off', 'wtap'):
+                for t in range(3):
+                    getattr(j, k)[t] = v[t]
+            else:
+                setattr(j, k, v)
+        return j
+
+    def multi(fn, *jobs, n=None):
+        return fn((_lib.ConvJob * len(jobs))(*jobs), len(jobs) if n is None else n, None)
+
+    for wino in (lib.da_conv3_winograd, lib.da_conv3_winograd4):
+        w = lambda rows=40, L=56, ldx=64, C=64, ldy=64, N=64, x=P: wino(x, P, P, rows, L, ldx, C, ldy, N, 0, None)
+        assert w(x=None) == E and w(rows=-1) == E and w(L=0) == E and w(C=48, ldx=48) == E and w(N=48) == E and w(C=0) == E
+        assert w(ldx=66) == E and w(ldx=32) == E and w(ldy=32) == E
+        assert w(rows=0) == 0
+        assert w(rows=1 << 20) == E                             # 32-bit element offsets
+        assert w(rows=2, L=1 << 18) == E                        # tile units x units per row within 32 bits
+    drop = lambda p=0.2, seed=P, part=P, R=20, rows=40, L=56: lib.da_conv3_winograd_drop(P, P, P, rows, L, 64, 64, 64, 64, seed, 7, p, part, R, None)
+    assert drop(p=-0.1) == E and drop(p=1.0) == E and drop(seed=None) == E
+    assert drop(R=0) == E and drop(R=3) == E and drop(R=2) == E  # records: whole windows of >= 64 pairs
+    assert drop(rows=0) == 0
+    bn = lambda R=20, pend=P, mean=P, C=64, p=0.2, rows=40: lib.da_conv3_winograd_bn(P, P, P, rows, 56, C, 64, 64, R, pend, mean, P, P, P, 1e-5,
+                                                                                    P, 7, p, None, None)
+    assert bn(pend=None) == E and bn(mean=None) == E and bn(C=160) == E and bn(R=1) == E and bn(R=3) == E and bn(p=1.0) == E
+    assert bn(rows=0) == 0
+    b = lambda rows=40, L=56, ldx=64, C=64, ldy=64, N=64, x=P: lib.da_conv3_bf16(x, P, P, rows, L, ldx, C, ldy, N, 0, None)
+    assert b(x=None) == E and b(rows=-1) == E and b(L=0) == E and b(C=48, ldx=48) == E and b(N=32, ldy=32) == E and b(ldx=66) == E
+    assert b(ldx=32) == E and b(ldy=32) == E and b(rows=0) == 0
+    assert b(rows=1 << 16, L=1 << 15) == E and b(rows=(1 << 21) - 1, L=1 << 10, ldy=12800, N=12800) == E
+    bb = lambda R=20, pend=P, mean=P, part=P, C=64, rows=40, L=56, N=64: lib.da_conv3_bf16_bn(P, P, P, rows, L, C, C, N, N, R, pend, mean, P, P, P,
+                                                                                              1e-5, part, None)
+    assert bb(N=32) == E and bb(R=0) == E and bb(R=3) == E and bb(R=2) == E and bb(pend=None, part=None) == E and bb(mean=None) == E
+    assert bb(C=2048) == E and bb(rows=1 << 16, L=1 << 15) == E
+    assert bb(rows=0) == 0 and bb(rows=0, R=0) == E
+    so, wt = (ctypes.c_int * 3)(-1, 0, 1), (ctypes.c_int * 3)(0, 1, 2)
+    g = lambda rows=40, Lm=28, ldx=64, C=64, N=64, ntaps=3, x=P: lib.da_conv_gemm(x, P, P, rows, Lm, 56, ldx, C, 28, 64, N, 1, 0, 2, ntaps, so, wt, 0, None)
+    assert g(x=None) == E and g(rows=-1) == E and g(Lm=0) == E and g(ntaps=0) == E and g(ntaps=4) == E
+    assert g(C=48) == E and g(N=48) == E and g(ldx=66) == E and g(rows=1, Lm=1 << 16) == E
+    assert g(rows=0) == 0 and g(rows=0, C=48) == 0              # (no rows: answered in front of the shape checks)
+    gm = lib.da_conv_gemm_multi
+    assert gm(None, 1, None) == E and multi(gm, job(), n=0) == E and multi(gm, *[job(rows=0)] * 5) == E
+    for kw in (dict(x=None), dict(rows=-1), dict(Lm=0), dict(ntaps=4), dict(C=48), dict(N=32), dict(N=96), dict(ldx=66),
+               dict(rows=1, Lm=1 << 16, Lsrc=1 << 17, Ldst=1 << 16), dict(x2=P), dict(x2=P, w2=P, tap_split=0), dict(x2=P, w2=P, tap_split=3)):
+        assert multi(gm, job(rows=0), job(**kw)) == E, kw
+    assert multi(gm, job(rows=0), job(rows=0)) == 0
+    bm = lib.da_conv_bf16_multi
+    assert bm(None, 1, None) == E and multi(bm, job(), n=-1) == E and bm(None, 0, None) == 0
+    for kw in (dict(x=None), dict(rows=-1), dict(Lm=0), dict(ntaps=4), dict(C=48), dict(C=0), dict(N=32), dict(ldx=66), dict(ldx=32),
+               dict(ldy=32), dict(src_stride=3), dict(src_stride=1), dict(Lsrc=55), dict(dst_stride=0), dict(dst_off=-1),
+               dict(dst_off=1), dict(Ldst=27), dict(wtap=(0, 1, 3)), dict(src_off=(-2, 0, 1)), dict(x2=P), dict(x2=P, w2=P, tap_split=3),
+               dict(rows=1 << 16, Lm=1 << 15, Lsrc=1 << 16, Ldst=1 << 15), dict(rows=1 << 14, Lm=1 << 16, Lsrc=1 << 17, Ldst=1 << 16),
+               dict(rows=1 << 12, Lm=1 << 10, Lsrc=1 << 11, Ldst=1 << 30)):
+        assert multi(bm, job(rows=0), job(**kw)) == E, kw
+    assert multi(bm, *[job(rows=0)] * 8, job(C=48)) == E        # more than 4 jobs: launches of 4, the ninth is still looked at
+    assert multi(bm, *[job(rows=0)] * 9) == 0
+    try:                                                        # bf16 activation storage: the fp32 kernels refuse
+        assert lib.da_set_act_dtype(1) == 0
+        assert lib.da_conv3_winograd(P, P, P, 40, 56, 64, 64, 64, 64, 0, None) == E
+        assert lib.da_conv3_winograd4(P, P, P, 40, 56, 64, 64, 64, 64, 0, None) == E
+        assert g() == E and multi(gm, job()) == E and g(rows=0) == E
+    finally:
+        lib.da_set_act_dtype(0)
+
+
+class _OnGpu(object):
+    """Stands in for a CUDA tensor as far as the wrappers' host checks look: a meta tensor that says it is on the GPU."""
+    is_cuda = True
+
+    def __init__(self, *shape, **kw):
+        self.t = torch.empty(shape, device='meta', dtype=kw.get('dtype', torch.float32))
+
+    def __getattr__(self, name):
+        return getattr(self.t, name)
+
+    def data_ptr(self):
+        return 4096
+
+
+def test_conv_wrappers_refuse_what_they_refused():
+    """The shapes and out / accumulate combinations every conv wrapper of hip_ops refused before its checks moved into shared
+    helpers still raise ValueError, in front of any library call (the operands have no memory)."""
+    from deepards_amd import hip_ops as H
+    T, bf = _OnGpu, torch.bfloat16
+    x, x48 = T(4, 8, 64), T(4, 8, 48)
+    x3 = T(4, 8, 4, 3, 16, dtype=bf)
+    pk = T(2, 4, 18, 64, 8, dtype=bf)
+    dy = T(4, 4, 128)
+    cases = [
+        # a CPU tensor is refused by every wrapper's first look
+        lambda: H.conv3_winograd(torch.zeros(4, 8, 64), T(4, 64, 64)),
+        lambda: H.conv3_x3p(torch.zeros(4, 8, 4, 3, 16, dtype=bf), pk),
+        lambda: H.conv_fwd(x, T(3, 64, 32), 1, 1),
+        lambda: H.conv_fwd(x48, T(3, 64, 48), 1, 1),
+        lambda: H.conv_fwd(x, T(3, 64, 64), 1, 1, out=T(4, 7, 64)),
+        lambda: H.conv3_winograd(x, T(5, 64, 64)),
+        lambda: H.conv3_winograd(x, T(4, 64, 32)),
+        lambda: H.conv3_winograd(x, T(4, 48, 64)),
+        lambda: H.conv3_winograd(x, T(4, 64, 64), accumulate=True),
+        lambda: H.conv3_winograd(x, T(4, 64, 64), out=T(4, 8, 32)),
+        lambda: H.conv3_winograd(x, T(4, 64, 64), out=T(4, 64, 8).transpose(1, 2)),
+        lambda: H.conv3_winograd(x, T(6, 64, 64), stats_R=2),
+        lambda: H.conv3_winograd(x, T(4, 64, 64), out=T(4, 8, 64), accumulate=True, stats_R=2),
+        lambda: H.conv3_bf16(x, T(1, 64, 64, dtype=bf)),
+        lambda: H.conv3_bf16(x, T(3, 32, 64, dtype=bf)),
+        lambda: H.conv3_bf16(x, T(3, 64, 32, dtype=bf)),
+        lambda: H.conv3_bf16(x, T(3, 64, 64)),
+        lambda: H.conv3_bf16(x, T(3, 64, 64, dtype=bf), accumulate=True),
+        lambda: H.conv3_bf16(x, T(3, 64, 64, dtype=bf), out=T(4, 8, 128)),
+        lambda: H.conv3_bf16_bn(x, T(3, 64, 64, dtype=bf), 3, want_records=True),
+        lambda: H.conv3_bf16_bn(x, T(1, 64, 64, dtype=bf), 2, want_records=True),
+        lambda: H.conv3_bf16_bn(x, T(3, 64, 64), 2, want_records=True),
+        lambda: H.x3_merge(x),
+        lambda: H.x3_merge(T(4, 8, 4, 3, 16)),
+        lambda: H.conv3_x3p(x, pk),
+        lambda: H.conv3_x3p(x3, T(2, 3, 18, 64, 8, dtype=bf)),
+        lambda: H.conv3_x3p(x3, T(2, 4, 18, 64, 8)),
+        lambda: H.conv3_x3p(x3, pk, accumulate=True),
+        lambda: H.conv3_x3p(x3, pk, out=T(4, 8, 64)),
+        lambda: H.conv3_x3p(x3, pk, out=T(4, 8, 128, dtype=bf)),
+        lambda: H.conv3_x3p(x3, pk, out=T(4, 128, 8).transpose(1, 2)),
+        lambda: H.conv_x3p_s2_fwd(x, pk, pk),
+        lambda: H.conv_x3p_s2_fwd(T(4, 7, 4, 3, 16, dtype=bf), pk, pk),
+        lambda: H.conv_x3p_s2_fwd(x3, pk, T(1, 4, 18, 64, 8, dtype=bf)),
+        lambda: H.conv_x3p_s2_dgrad(x3, pk, x, pk),
+        lambda: H.conv_x3p_s2_dgrad(x3, pk, T(4, 4, 4, 3, 16, dtype=bf), pk),
+        lambda: H.conv_x3p_s2_dgrad(x3, pk, x3, pk, out=T(4, 16, 64)),
+        lambda: H.conv_x3p_s2_dgrad(x3, pk, x3, pk, out=T(4, 16, 128, dtype=bf)),
+        lambda: H.conv_fwd_bf16_s2(T(4, 7, 64), T(3, 128, 64, dtype=bf)),
+        lambda: H.conv_fwd_bf16_s2(x),
+        lambda: H.conv_fwd_bf16_s2(x, T(2, 128, 64, dtype=bf)),
+        lambda: H.conv_fwd_bf16_s2(x, T(3, 128, 64)),
+        lambda: H.conv_dgrad_bf16_s2(dy, T(3, 64, 128, dtype=bf), 9),
+        lambda: H.conv_dgrad_bf16_s2(dy, T(3, 64, 128, dtype=bf), 8, accumulate=True),
+        lambda: H.conv_dgrad_bf16_s2(dy, T(1, 64, 128, dtype=bf), 8, out=T(4, 8, 128)),
+        lambda: H.conv_dgrad_bf16_s2(dy, T(3, 64, 64, dtype=bf), 8),
+        lambda: H.conv_dgrad_bf16_s2_pair(dy, T(1, 64, 128, dtype=bf), dy, T(1, 64, 128, dtype=bf), 8),
+        lambda: H.conv_dgrad_bf16_s2_pair(dy, T(3, 64, 128, dtype=bf), dy, T(1, 128, 128, dtype=bf), 8),
+        lambda: H.conv_dgrad_bf16_s2_pair(dy, T(3, 64, 128, dtype=bf), T(4, 5, 128), T(1, 64, 128, dtype=bf), 8),
+        lambda: H.conv_dgrad_bf16_s2_pair(dy, T(3, 64, 128, dtype=bf), dy, T(1, 64, 128, dtype=bf), 10),
+        lambda: H.conv_dgrad(dy, T(3, 64, 64), 2, 1, 8),
+        lambda: H.conv_dgrad(dy, T(3, 48, 128), 2, 1, 8),
+        lambda: H.conv_dgrad(dy, T(3, 64, 128), 2, 1, 8, accumulate=True),
+        lambda: H.conv_dgrad(dy, T(3, 64, 128), 2, 1, 8, out=T(4, 9, 64)),
+        lambda: H.conv_fwd_multi([(x, T(3, 128, 32), 2, 1), (x, T(1, 128, 64), 2, 0)]),
+        lambda: H.conv_fwd_multi([(x48, T(3, 128, 48), 2, 1)]),
+        lambda: H.conv_wgrad(dy, x, 3, 2, 1, accumulate=True),
+        lambda: H.conv_wgrad(dy, x, 3, 1, 1),
+        lambda: H.conv_wgrad(dy, T(3, 8, 64), 3, 2, 1),
+        lambda: H.conv_wgrad(T(4, 8, 128), x, 7, 1, 3, accumulate=True),
+        lambda: H.conv_wgrad(T(4, 8, 128), x, 7, 1, 3, defer=True),
+        lambda: H.wgrad_reduce_multi([((x, 2, 3, 128, 64), T(128, 64, 1))]),
+        lambda: H.step_tail_multi([((x, 2, 3, 128, 64), T(64, 128, 3))], [], []),
+    ]
+    for n, call in enumerate(cases):
+        with pytest.raises(ValueError):
+            call()
+            pytest.fail('case %d was accepted' % n)
