@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip.so')   # (override: A/B builds, scripts/)
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
-SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip']
+SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -170,6 +170,9 @@ SIGNATURES = {
     'da_window_median_bwd': (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     'da_lstm_fwd': (_I, [_P] * 11 + [_I, _I, _I, _P]),
     'da_lstm_bwd': (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    'da_tfm_block_fwd': (_I, [_P] * 9 + [_I] * 4 + [_P, _U, _U, _F, _P]),
+    'da_tfm_block_bwd': (_I, [_P] * 17 + [_I] * 4 + [_P, _U, _U, _F, _P]),
+    'da_tfm_block_pgrad': (_I, [_P] * 13 + [_I] * 5 + [_P, _U, _U, _F, _P]),
     'da_reduce_rows': (_I, [_P, _I, _I, _P, _I, _P]),
     'da_gather_rows': (_I, [_P, _P, _P, _I, _I, _P]),
     'da_vote_counts': (_I, [_P, _P, _I, _I, _P, _P, _P]),

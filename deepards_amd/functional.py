@@ -1089,6 +1089,35 @@ class LSTMFunction(Function):
         return dfeat.view(rows, f), dw_ih.view(g4, f), dw_hh, db, db.clone(), None, None, None
 
 
+class TransformerBlockFunction(Function):
+    """One Block of the cnn_transformer head (reference models/transformer.py:59-88): x (B, T, D) -> (out (B, T, D),
+    attention weights (B, 4, T, T)) in one launch; the backward is two (data, parameters).  ``seed`` (one-element int64
+    device tensor), ``salt`` and ``p`` are the dropout of the block's two sites (salt, salt + 1); p = 0: none.  The
+    incoming gradient is honoured; with a trainer's destinations on all sixteen parameters the parameter kernel writes
+    (or, outside an overwriting capture, accumulates) straight into the flat gradient bucket."""
+
+    @staticmethod
+    def forward(ctx, x, seed, salt, p, *params):
+        x = x.contiguous()
+        ctx.drop = (seed, salt, salt + 1, p) if p > 0 else None
+        y, saved = H.tfm_block_fwd(x, params, ctx.drop)
+        ctx.save_for_backward(x, *(tuple(params) + saved))
+        ctx.gt = _tgt(*params)
+        ctx.mark_non_differentiable(saved[3])
+        return y, saved[3]
+
+    @staticmethod
+    def backward(ctx, dy, _dweights=None):
+        t = ctx.saved_tensors
+        x, params, saved = t[0], t[1:1 + H.TFM_PARAMS], t[1 + H.TFM_PARAMS:]
+        dy = dy.contiguous()
+        dx, work = H.tfm_block_bwd(dy, x, params, saved, ctx.drop)
+        direct = all(g is not None for g in ctx.gt)
+        grads = H.tfm_block_pgrad(dy, x, params, saved, work, grads=list(ctx.gt) if direct else None,
+                                  accumulate=direct and _acc(), drop=ctx.drop)
+        return (dx, None, None, None) + ((None,) * H.TFM_PARAMS if direct else tuple(grads))
+
+
 class BCEWithLogitsFunction(Function):
     """torch.nn.BCEWithLogitsLoss() (mean) -- train_ards_detector.py:530,929-930."""
 

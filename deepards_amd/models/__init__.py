@@ -5,6 +5,7 @@ from .densenet import DenseNet, densenet18, densenet121, densenet169, densenet20
 from .torch_cnn_linear_network import (CNNLinearNetwork, CNNLinearToMean, CNNLinearComprToRF,      # noqa: F401
                                        CNNSingleBreathLinearNetwork, CNNDoubleLinearNetwork, CNNLSTMNetwork,
                                        BreathBlockLinear)
+from .transformer import MultiHeadAttention, Block, Transformer, CNNTransformerNetwork           # noqa: F401
 
 # the 1-D BasicBlock / growth-32 entries of the reference's base_networks (train_ards_detector.py:45-69); resnet34 is in
 # its models/resnet.py (:178) though not in that dict; densenet161 (growth 48) and the Bottleneck / SE / VGG nets are not built

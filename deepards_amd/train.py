@@ -265,7 +265,7 @@ class HotPathTrainer(object):
         if loss_calc not in LOSS_CALCS:
             raise ValueError('loss_calc must be one of %s, got %r' % (', '.join(LOSS_CALCS), loss_calc))
         from . import models as M_
-        per_breath = isinstance(model, (M_.CNNLSTMNetwork, M_.CNNSingleBreathLinearNetwork))
+        per_breath = isinstance(model, (M_.CNNLSTMNetwork, M_.CNNSingleBreathLinearNetwork, M_.CNNTransformerNetwork))
         check_loss_choice(loss, per_breath and loss_calc == 'all_breaths')
         if carry_state and not isinstance(model, M_.CNNLSTMNetwork):
             raise ValueError('carry_state needs a CNNLSTMNetwork')

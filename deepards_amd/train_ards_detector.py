@@ -51,7 +51,7 @@ BUILD_DEFAULTS = dict(
     clip_grad=None, with_fft=None, only_fft=None, fft_real_only=None, random_kfold=None, bootstrap=None,
     kfolds=None, only_fold=None, load_checkpoint=None, load_base_network=None, save_model=None, saved_models_dir=None,
     train_from_pickle=None, train_to_pickle=None, test_from_pickle=None, test_to_pickle=None,
-    experiment_name='deepards_amd', config_override=None, folds_in_flight=None, fold_groups=None,
+    experiment_name='deepards_amd', config_override=None, folds_in_flight=None, fold_groups=None, transformer_blocks=2,
 )
 
 # make_args(): the merged view with every reference default, for callers that build ``args`` in Python
@@ -60,7 +60,7 @@ DEFAULTS = dict(
     initial_planes=64, resnet_first_pool_type='max', resnet_double_conv=False,
     optimizer='sgd', dataset_type='unpadded_centered_sequences', learning_rate=0.001, n_sub_batches=20,
     weight_decay=0.0001, loss_func='bce', valpha=float('inf'), conf_beta=1.0, loss_calc='all_breaths', bm_to_linear=False,
-    clip_grad=False, clip_val=0.01, time_series_hidden_units=16,
+    clip_grad=False, clip_val=0.01, time_series_hidden_units=16, transformer_blocks=2,
     with_fft=False, only_fft=False, fft_real_only=False, freeze_base_network=False,
     kfolds=None, bootstrap=False, random_kfold=False, only_fold=None, unshuffled=False, no_train=False,
     no_test_after_epochs=False, debug=False, cuda=True, cuda_no_dp=False, cuda_device=0, load_checkpoint=None,
@@ -639,6 +639,23 @@ class CNNLSTMModel(PerBreathClassifierMixin, BaseTraining, PatientClassifierMixi
                                 self.args.time_series_hidden_units)
 
 
+class CNNTransformerModel(PerBreathClassifierMixin, BaseTraining, PatientClassifierMixin):
+    """:801-806.  Its test epoch is ``BaseTraining.run_test_epoch`` (no ``model.eval()``, :448): train-mode modules under
+    no_grad, so both dropouts stay on and BatchNorm uses batch statistics -- ResNet and DenseNet bases alike.  NOT in
+    ``network_map`` yet (README.md, "Networks"): build it directly, ``CNNTransformerModel(args).train_and_test()``."""
+    eval_in_test_epoch = False
+
+    def __init__(self, args):
+        if _flag(args, 'bm_to_linear'):
+            raise NotImplementedError('--bm-to-linear (metadata into the linear layer) is outside the accelerated path')
+        super(CNNTransformerModel, self).__init__(args)
+
+    def get_network(self, base_network):
+        blocks = getattr(self.args, 'transformer_blocks', None)
+        return M.CNNTransformerNetwork(base_network, self.n_metadata_inputs, bool(_flag(self.args, 'bm_to_linear')),
+                                       self.args.time_series_hidden_units, 2 if blocks is None else blocks)
+
+
 network_map = {
     'cnn_lstm': CNNLSTMModel,
     'cnn_linear': CNNLinearModel,
@@ -652,7 +669,7 @@ network_map = {
 OUT_OF_SCOPE_FLAGS = (
     '--transforms', '-tp', '--transform-probability', '--use-i', '-r2', '--drop-if-under-r2', '--drop-i-lim', '--drop-e-lim',
     '--truncate-e-lim', '--butter-low', '--butter-high', '--post-hoc-downsampling', '--fft-filtering-low',
-    '--fft-filtering-high', '--load-siamese', '--fl-gamma', '--fl-alpha', '--transformer-blocks',
+    '--fft-filtering-high', '--load-siamese', '--fl-gamma', '--fl-alpha',
     '--plot-untiled-disease-evol', '--plot-tiled-disease-evol', '--plot-dtw-with-disease', '--plot-pt-dtw-by-minute',
     '--perform-dtw-preprocessing', '--n-warm-epochs', '-pse', '--push-start-epoch', '--push-every-n', '--n-push-iters',
     '--clust-lambda', '--sep-lambda', '-vse', '--viz-start-epoch', '--viz-every-n', '--prototype-results-dir',
@@ -712,6 +729,7 @@ def build_parser():
     parser.add_argument('-lc', '--loss-calc', choices=['all_breaths', 'last_breath'], help='cnn_lstm: loss over every '
                         'breath\'s output or over the last breath\'s only')
     parser.add_argument('--time-series-hidden-units', type=int)
+    parser.add_argument('--transformer-blocks', type=int, help='cnn_transformer: number of Blocks (defaults.yml: 2)')
     true_false_flag('--unshuffled', 'dont shuffle data')
     true_false_flag('--oversample-minority', '')
     parser.add_argument('--oversample-all-factor', type=float)

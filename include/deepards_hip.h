@@ -487,6 +487,29 @@ int da_lstm_fwd(const float* gx, const float* whh, const float* bih, const float
 int da_lstm_bwd(const float* dh_all, const float* whh, const float* hs, const float* cs, const float* gates,
                 const float* h0, const float* c0, float* dgates, float* dwhh_part, int B, int T, int H,
                 da_stream_t stream);
+/* ---- cnn_transformer head: one Block of Transformer (reference models/transformer.py:13-88; CNNTransformerNetwork
+ * models/cnn_transformer.py:8-44) in three fp32 launches.  x, y [B][T][D]; `params` = the block's sixteen parameter
+ * pointers in named_parameters() order (q / k / v / joint_linear weight, bias; attention_norm; ff.0; ff.2; ff_norm), each
+ * 16-byte aligned; 4 heads.  T in [1, 64], D a multiple of 64 up to 2048, H a multiple of 8 in [8, 64]; else -1.
+ * Dropout (transformer.py:78-79,87-88): the mask of da_dropout on the contiguous [B T][D] tensor, (seed, salt1) behind
+ * the attention, (seed, salt2) behind the feed-forward; p == 0: none (seed may be NULL).
+ * forward (transformer.py:34-56,86-88): saves q, k, v, hid [B][T][H], the attention weights aw [B][4][T][T] and
+ * stats [B][T][4] = {mean, rstd} of attention_norm then of ff_norm */
+int da_tfm_block_fwd(const float* x, const float* const* params, float* y, float* q, float* k, float* v, float* aw, float* hid,
+                     float* stats, int B, int T, int D, int H, const int64_t* seed, unsigned salt1, unsigned salt2, float p,
+                     da_stream_t stream);
+/* data backward: dy -> dx, and what da_tfm_block_pgrad reads: the gradients at the q / k / v / ff.0 outputs (dq, dk, dv, dhid
+ * [B][T][H], dhid behind the ReLU), at the two LayerNorm inputs (da1, da2 [B][T][D]) and the re-joined heads wv [B][T][H] */
+int da_tfm_block_bwd(const float* dy, const float* x, const float* const* params, const float* q, const float* k, const float* v,
+                     const float* aw, const float* hid, const float* stats, float* dx, float* dq, float* dk, float* dv,
+                     float* dhid, float* da1, float* da2, float* wv, int B, int T, int D, int H, const int64_t* seed,
+                     unsigned salt1, unsigned salt2, float p, da_stream_t stream);
+/* parameter backward: grads[16] (the order of `params`) (+)= the block's parameter gradients; every sum in a fixed order */
+int da_tfm_block_pgrad(const float* dy, const float* x, const float* const* params, const float* hid, const float* stats,
+                       const float* wv, const float* dq, const float* dk, const float* dv, const float* dhid, const float* da1,
+                       const float* da2, float* const* grads, int accumulate, int B, int T, int D, int H, const int64_t* seed,
+                       unsigned salt1, unsigned salt2, float p, da_stream_t stream);
+
 /* out[n] (+)= column sums of m [rows][n] in a fixed order */
 int da_reduce_rows(const float* m, int rows, int n, float* out, int accumulate, da_stream_t stream);
 
