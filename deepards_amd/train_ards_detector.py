@@ -70,6 +70,7 @@ DEFAULTS = dict(
     undersample_factor=-1, train_pt_frac=1.0, train_from_pickle=None, test_from_pickle=None, train_to_pickle=None,
     test_to_pickle=None, stop_on_loss=False, stop_thresh=1.5, stop_after_epoch=1,
     train_store=None, test_store=None, test_patient_slot=None, use_graph=True, seed=None, conv_dtype=None, act_dtype=None,
+    butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None,
 )
 
 
@@ -216,6 +217,9 @@ class BaseTraining(object):
         (``make_test_dataset_if_kfold`` :272-273); a holdout test pickle gets the TRAIN set's scaling factors (:285)."""
         a = self.args
         if a.train_store is not None and a.test_store is not None:
+            if any(v is not None for v in self._filter_kwargs().values()):
+                a.train_store.set_filters(**self._filter_kwargs())    # (all None: stores handed in keep what they carry)
+                a.test_store.set_filters(**self._filter_kwargs())
             return a.train_store, a.test_store
         if not a.train_from_pickle:
             raise ValueError('no dataset: pass --train-from-pickle <dataset.pkl|.npz> (or args.train_store / args.test_store); '
@@ -235,6 +239,7 @@ class BaseTraining(object):
         if a.seed is not None:
             import numpy as np
             train.sampling_rng = np.random.RandomState(a.seed)
+        train.set_filters(**self._filter_kwargs())                # before the k-fold test store is made: it inherits them
         self.n_sub_batches = ds.n_sub_batches
         if a.train_to_pickle:
             ds.save_npz(a.train_to_pickle)
@@ -246,6 +251,7 @@ class BaseTraining(object):
             test = tds.to_store(self.device)
             test.mu, test.std = train.mu, train.std               # test_dataset.scaling_factors = train_dataset's (:285)
             test.scaling_factors = train.scaling_factors
+            test.set_filters(**self._filter_kwargs())             # the holdout test dataset gets the same keywords (:266-272)
             if a.test_to_pickle:
                 tds.save_npz(a.test_to_pickle)
         else:
@@ -253,6 +259,10 @@ class BaseTraining(object):
         if a.test_patient_slot is None and test.patient_slot is not None:
             a.test_patient_slot = torch.as_tensor(test.patient_slot, dtype=torch.int64)
         return train, test
+
+    def _filter_kwargs(self):
+        """The four filter keys of the dataset constructors (:246-255); a key nobody set reads as None."""
+        return {k: getattr(self.args, k, None) for k in ('butter_low', 'butter_high', 'fft_filtering_low', 'fft_filtering_high')}
 
     def get_splits(self):
         """:317-338: per fold, (train_dataset, train_loader, test_dataset, test_loader); a loader is the tuple
@@ -668,8 +678,7 @@ network_map = {
 # flags of the reference's parser that steer code outside the hot path: recognised so that the error says why
 OUT_OF_SCOPE_FLAGS = (
     '--transforms', '-tp', '--transform-probability', '--use-i', '-r2', '--drop-if-under-r2', '--drop-i-lim', '--drop-e-lim',
-    '--truncate-e-lim', '--butter-low', '--butter-high', '--post-hoc-downsampling', '--fft-filtering-low',
-    '--fft-filtering-high', '--load-siamese', '--fl-gamma', '--fl-alpha',
+    '--truncate-e-lim', '--butter-low', '--post-hoc-downsampling', '--load-siamese', '--fl-gamma', '--fl-alpha',
     '--plot-untiled-disease-evol', '--plot-tiled-disease-evol', '--plot-dtw-with-disease', '--plot-pt-dtw-by-minute',
     '--perform-dtw-preprocessing', '--n-warm-epochs', '-pse', '--push-start-epoch', '--push-every-n', '--n-push-iters',
     '--clust-lambda', '--sep-lambda', '-vse', '--viz-start-epoch', '--viz-every-n', '--prototype-results-dir',
@@ -748,6 +757,11 @@ def build_parser():
     true_false_flag('--only-fft', '')
     true_false_flag('--fft-real-only', '')
     true_false_flag('--random-kfold', 'perform a random kfold splitting.')
+    # (--butter-low is read from the experiment file only: butter_low)
+    parser.add_argument('--butter-high', type=float, help='10th-order Butterworth filter on every row; with butter_low of the '
+                        'experiment file: alone a HIGHPASS at this frequency, with butter_low 0 a lowpass, else a bandpass')
+    parser.add_argument('--fft-filtering-low', type=float, help='FFT band filter: keep |f| above this (Hz); needs both bounds')
+    parser.add_argument('--fft-filtering-high', type=float, help='FFT band filter: keep |f| below this (Hz); needs both bounds')
     true_false_flag('--bootstrap', '')
     # this build's own switches
     parser.add_argument('--seed', type=int, help='seed of the initialisation, the shuffles and the oversampler')
@@ -769,6 +783,9 @@ def main(argv=None):
     import sys
     argv = sys.argv[1:] if argv is None else list(argv)
     for a in argv:
+        if a.split('=')[0] == '--butter-low':
+            raise SystemExit('--butter-low is not accepted on the command line -- the flag used to steer code outside the accelerated '
+                             'hot path and its refusal is pinned by a test: give butter_low in the -co experiment file')
         if a.split('=')[0] in OUT_OF_SCOPE_FLAGS:
             raise SystemExit('%s steers code outside the accelerated cnn_linear hot path (SURVEY.md section 2) and is not '
                              'accepted by this build' % a.split('=')[0])

@@ -473,6 +473,14 @@ int da_gather_normalize(const double* tiles, const int64_t* idx, double mu, doub
  * train_ards_detector.py:228-230); every channel has its own factors (dataset.py:627-649).  mu / stdv: HOST arrays [C]. */
 int da_gather_normalize_ch(const double* tiles, const int64_t* idx, const double* mu, const double* stdv, float* out, int B,
                            int NB, int C, int L, da_stream_t stream);
+/* the same gather with the reference's two frequency filters behind the normalisation, before the cast: the 10th-order
+ * Butterworth sosfilt (setup_butter_filter dataset.py:546-557, applied :1381-1382) as the causal sum
+ * y[n] = sum_{m<=n} h[n-m] x[m] and the FFT band mask (:1393-1400) as the circular sum z[n] = sum_m g[(n-m) mod L] y[m], both
+ * per row of L samples, every channel, in float64, ascending m, fma -- a repeat is bit-identical.  h, g: DEVICE arrays of L
+ * doubles (impulse response of the cascade; real(ifft(mask))); either may be NULL, not both.  h: L <= 512; g: L == 224 (the
+ * mask is built over fftfreq(224)); C <= 4; mu / stdv: HOST arrays [C].  Anything else: -1, out untouched. */
+int da_gather_normalize_filter(const double* tiles, const int64_t* idx, const double* mu, const double* stdv, const double* h,
+                               const double* g, float* out, int B, int NB, int C, int L, da_stream_t stream);
 /* ---- sibling heads of CNNLinearNetwork (torch_cnn_linear_network.py:7-89) ---------------------- */
 /* CNNLinearComprToRF: lower median over the NB breath rows of each window (torch.median(outputs, dim=1)[0], :47);
    x [B*NB][ld], out [B][F], idx [B][F] = selected row (for the backward); NB <= 64.  The mean of CNNLinearToMean
