@@ -168,6 +168,8 @@ SIGNATURES = {
     'da_gather_normalize': (_I, [_P, _P, ctypes.c_double, ctypes.c_double, _P, _I, _I, _P]),
     'da_gather_normalize_ch': (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'da_gather_normalize_filter': (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _P, _P, _P, _I, _I, _I, _I, _P]),
+    'da_gather_normalize_chain': (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _I, _P, _P, _I, _P, _P,
+                                       _I, _I, _I, _I, _P]),
     'da_window_median_fwd': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'da_window_median_bwd': (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     'da_lstm_fwd': (_I, [_P] * 11 + [_I, _I, _I, _P]),

@@ -37,6 +37,7 @@ class DeviceTileStore(object):
         self.sampling_rng = None                      # np.random.RandomState for the oversampler; None: numpy's global RNG
         self.hours = None                             # (N, NB) seq_hours of the windows when ingested from a pickle
         self.patient_slot = None                      # (N,) patient slot per window when ingested from a pickle
+        self.padded = False                           # a padded_breath_by_breath dataset: mu only off non-zero samples (:1375-1377)
         self.set_filters()                            # no frequency filter (dataset.py:546-559 with every key None)
 
     @staticmethod
@@ -49,22 +50,37 @@ class DeviceTileStore(object):
         return float(a[0]) if chans == 1 else tuple(float(q) for q in a)
 
     # ---- frequency filters of ARDSRawDataset.__getitem__ (dataset.py:546-557, 1381-1400) -----------------------------
-    def set_filters(self, butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None):
+    def set_filters(self, butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None,
+                    post_hoc_downsampling=None):
         """The reference's dataset keywords of the same names: a 10th-order Butterworth ``sosfilt`` chosen by butter_low /
         butter_high and an FFT band mask, active when BOTH fft values are given; applied behind the normalisation to
         every row of every channel.  The filters become two float64 kernels h / g (``deepards_amd.filters``), computed
         here once and kept on the device; ``batch`` / ``batch_from_device`` then gather through
         ``gather_normalize_filter`` -- still one gather launch per batch.  All None: the unfiltered gather.
-        An FFT filter on windows that are not 224 samples long raises ValueError (the mask is built over fftfreq(224))."""
-        from .filters import filter_kernels
-        h, g = filter_kernels(butter_low, butter_high, fft_filtering_low, fft_filtering_high, L=self.tiles.shape[3])
+        An FFT filter on windows that are not 224 samples long raises ValueError (the mask is built over fftfreq(224)).
+        post_hoc_downsampling (dataset.py:1384-1391): between the two filters every row is resampled to int(L / factor)
+        samples and zero-padded back to L; the resampling matrix R (``filters.resample_matrix``) stays on the device as
+        ``filter_r`` and the gather goes through ``gather_normalize_chain``.  A factor with int(L / factor) outside [1, L], or
+        rows of more than 512 samples, raise ValueError."""
+        from .filters import MAX_BUTTER_LEN, filter_kernels, post_hoc_new_len, resample_matrix
+        L = self.tiles.shape[3]
+        h, g = filter_kernels(butter_low, butter_high, fft_filtering_low, fft_filtering_high, L=L)
+        r = None
+        if post_hoc_downsampling is not None:
+            if L > MAX_BUTTER_LEN:
+                raise ValueError('post-hoc downsampling runs on rows of up to %d samples, not %d' % (MAX_BUTTER_LEN, L))
+            r = H.resample_operand(resample_matrix(L, post_hoc_new_len(L, post_hoc_downsampling)), self.tiles.device)
         dev = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64).contiguous().to(self.tiles.device)
-        self.filter_h, self.filter_g = dev(h), dev(g)
+        self.filter_h, self.filter_g, self.filter_r = dev(h), dev(g), r
         self.butter_low, self.butter_high = butter_low, butter_high
         self.fft_filtering_low, self.fft_filtering_high = fft_filtering_low, fft_filtering_high
+        self.post_hoc_downsampling = post_hoc_downsampling
         return self
 
     def _gather(self, idx, out):
+        if self.padded or self.filter_r is not None:
+            return H.gather_normalize_chain(self.tiles, idx, self.mu, self.std, self.padded, self.filter_h, self.filter_r,
+                                            self.filter_g, out=out)
         if self.filter_h is None and self.filter_g is None:
             return H.gather_normalize(self.tiles, idx, self.mu, self.std, out=out)
         return H.gather_normalize_filter(self.tiles, idx, self.mu, self.std, self.filter_h, self.filter_g, out=out)
@@ -103,7 +119,7 @@ class DeviceTileStore(object):
 
     def make_test_store_if_kfold(self):
         """``ARDSRawDataset.make_test_dataset_if_kfold`` (dataset.py:672-700): the same windows, splits and TRAIN-fold
-        scaling factors and frequency filters (:696-700), serving the test patients of each fold (no copy of the device
+        scaling factors, padding rule, frequency filters and post-hoc downsampling (:696-700), serving the test patients of each fold (no copy of the device
         tiles)."""
         if self.total_kfolds is None:
             raise ValueError('enable_kfolds first')

@@ -14,6 +14,13 @@ Both are linear maps on one row of L samples, and that is how the device applies
     z[n] = sum_m g[(n - m) mod 224] y[m]         g = real(ifft(mask)): the mask is symmetric in |f|, so the circular
                                                  convolution is exactly real and dropping ``.imag`` loses nothing
 
+Two more steps of the item complete the chain, in the reference's order: normalise, ``sosfilt``, DOWNSAMPLE, FFT mask.
+
+* padded datasets (every ``dataset_type`` that contains ``padded_breath_by_breath``, :1375-1377, 1406-1409): ``mu`` is
+  subtracted only where the raw sample is non-zero, so padding stays exactly 0 (``normalize_host``);
+* ``post_hoc_downsampling`` (:1384-1391): ``scipy.signal.resample(data, int(L / factor), axis=-1)``, zero-padded at the end
+  back to L samples.  Fourier resampling of a real row is linear as well: r = R y with ``R = resample_matrix(L, new_len)``.
+
 This module chooses the filter, designs it (``scipy.signal.butter``, the reference's own designer, imported lazily),
 turns it into ``h`` / ``g`` and restates the two sums in numpy (``apply_host``) for the CPU tests.  ``dataset.py`` itself
 does not import here; parity is pinned to the library calls it makes (tests/tools/make_golden_filters.py).
@@ -94,9 +101,48 @@ def filter_kernels(butter_low=None, butter_high=None, fft_filtering_low=None, ff
     return (None if sos is None else impulse_response(sos, L)), g
 
 
-def apply_host(x, h=None, g=None):
-    """The device's two sums in numpy on rows x (..., L), float64: y = causal convolution with h, z = circular convolution
-    of y with g.  A filter that is None is skipped."""
+def post_hoc_new_len(L, factor):
+    """``int(L / factor)`` (dataset.py:1386).  ValueError unless 1 <= new_len <= L: in the reference a factor below 1 makes
+    ``np.pad`` raise (a negative pad length) and a factor above L resamples the row to nothing."""
+    if not float(factor) > 0:
+        raise ValueError('post_hoc_downsampling must be a positive factor, got %r' % (factor,))
+    new_len = int(int(L) / float(factor))
+    if not 1 <= new_len <= int(L):
+        raise ValueError('post_hoc_downsampling %r turns rows of %d samples into %d: 1 <= int(L / factor) <= L is needed' % (factor, L, new_len))
+    return new_len
+
+
+def resample_matrix(L, new_len):
+    """R (new_len, L) float64 with ``scipy.signal.resample(x, new_len, axis=-1) == x @ R.T`` for real rows x of L samples: the
+    routine's own steps on the unit vectors -- rfft, keep min(new_len, L) // 2 + 1 bins, double the Nyquist bin when new_len
+    is even and smaller than L (halve it when larger: unreachable here), irfft to new_len samples, scale by new_len / L."""
+    L, new_len = int(L), int(new_len)
+    if not 1 <= new_len <= L:
+        raise ValueError('1 <= new_len <= L expected, got new_len %d, L %d' % (new_len, L))
+    spectrum = np.fft.rfft(np.eye(L, dtype=np.float64), axis=0)          # column j: the spectrum of the unit vector e_j
+    n = min(new_len, L)
+    kept = np.zeros((new_len // 2 + 1, L), dtype=spectrum.dtype)
+    kept[:n // 2 + 1] = spectrum[:n // 2 + 1]
+    if n % 2 == 0 and new_len < L:
+        kept[n // 2] *= 2.0                                              # the bin stands for +Nyquist and -Nyquist of the new grid
+    return np.ascontiguousarray(np.fft.irfft(kept, new_len, axis=0) * (float(new_len) / float(L)))
+
+
+def normalize_host(x, mu, std, padded=False):
+    """The first step of the item on raw rows x (..., C, L), float64; mu / std scalars or one per channel.  padded:
+    ``(x - where(x != 0, mu, 0)) / std`` (dataset.py:1375-1377, 1406-1409; a NaN is non-zero), else ``(x - mu) / std``."""
+    x = np.asarray(x, dtype=np.float64)
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1, 1)
+    std = np.asarray(std, dtype=np.float64).reshape(-1, 1)
+    if not padded:
+        return (x - mu) / std
+    return np.where(x != 0, (x - mu) / std, x / std)
+
+
+def apply_host(x, h=None, g=None, r=None):
+    """The device's sums in numpy on rows x (..., L), float64, in the item's order: y = causal convolution with h,
+    r-stage = R y zero-padded at the end back to L samples (r: the (new_len, L) matrix of ``resample_matrix``),
+    z = circular convolution with g.  A stage that is None is skipped."""
     y = np.asarray(x, dtype=np.float64)
     L = y.shape[-1]
     n, m = np.arange(L)[:, None], np.arange(L)[None, :]
@@ -105,6 +151,11 @@ def apply_host(x, h=None, g=None):
         if h.shape != (L,):
             raise ValueError('h must hold one sample per sample of a row')
         y = y @ np.where(m <= n, h[(n - m) % L], 0.0).T
+    if r is not None:
+        r = np.asarray(r, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != L or not 1 <= r.shape[0] <= L:
+            raise ValueError('r must be (new_len <= L, L)')
+        y = np.concatenate([y @ r.T, np.zeros(y.shape[:-1] + (L - r.shape[0],))], axis=-1)
     if g is not None:
         g = np.asarray(g, dtype=np.float64)
         if g.shape != (L,):

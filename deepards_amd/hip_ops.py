@@ -1748,4 +1748,4 @@ def vote_counts(logits, group, votes, want_pred=True):
 
 from .loss_ops import confidence_loss, vacillating_loss          # noqa: E402,F401
 from .transformer_ops import TFM_PARAMS, tfm_check_shape, tfm_block_fwd, tfm_block_bwd, tfm_block_pgrad   # noqa: E402,F401
-from .filter_ops import gather_normalize_filter                  # noqa: E402,F401
+from .filter_ops import gather_normalize_filter, gather_normalize_chain, resample_operand   # noqa: E402,F401

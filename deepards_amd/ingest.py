@@ -514,6 +514,7 @@ class IngestedDataset(object):
         store.hours = self.hours
         store.patient_slot = self.patient_slot
         store.train = self.train
+        store.padded = 'padded_breath_by_breath' in str(self.dataset_type)     # the reference's own test (dataset.py:1375)
         if self.total_kfolds is not None:
             if self.patient_slot is None:
                 raise ValueError('k-fold splits are patient-wise (dataset.py:765-830) and this dataset file carries no '

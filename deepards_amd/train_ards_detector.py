@@ -70,7 +70,7 @@ DEFAULTS = dict(
     undersample_factor=-1, train_pt_frac=1.0, train_from_pickle=None, test_from_pickle=None, train_to_pickle=None,
     test_to_pickle=None, stop_on_loss=False, stop_thresh=1.5, stop_after_epoch=1,
     train_store=None, test_store=None, test_patient_slot=None, use_graph=True, seed=None, conv_dtype=None, act_dtype=None,
-    butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None,
+    butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None, post_hoc_downsampling=None,
 )
 
 
@@ -261,8 +261,12 @@ class BaseTraining(object):
         return train, test
 
     def _filter_kwargs(self):
-        """The four filter keys of the dataset constructors (:246-255); a key nobody set reads as None."""
-        return {k: getattr(self.args, k, None) for k in ('butter_low', 'butter_high', 'fft_filtering_low', 'fft_filtering_high')}
+        """The four filter keys of the dataset constructors (:246-255); a key nobody set reads as None.  The fifth,
+        post_hoc_downsampling, is passed on only when it is set."""
+        kw = {k: getattr(self.args, k, None) for k in ('butter_low', 'butter_high', 'fft_filtering_low', 'fft_filtering_high')}
+        if getattr(self.args, 'post_hoc_downsampling', None) is not None:
+            kw['post_hoc_downsampling'] = self.args.post_hoc_downsampling
+        return kw
 
     def get_splits(self):
         """:317-338: per fold, (train_dataset, train_loader, test_dataset, test_loader); a loader is the tuple
@@ -719,7 +723,7 @@ def build_parser():
     true_false_flag('--no-test-after-epochs', '')
     true_false_flag('--debug', 'debug code and dont train')
     parser.add_argument('--optimizer', choices=['adam', 'sgd'])
-    parser.add_argument('-dt', '--dataset-type', choices=['unpadded_centered_sequences',
+    parser.add_argument('-dt', '--dataset-type', choices=['unpadded_centered_sequences', 'padded_breath_by_breath',
                                                           'padded_breath_by_breath_with_flow_time_features'])
     parser.add_argument('-lr', '--learning-rate', type=float)
     parser.add_argument('--loader-threads', type=int, help='accepted and ignored: batches are gathered on the device')
@@ -757,7 +761,7 @@ def build_parser():
     true_false_flag('--only-fft', '')
     true_false_flag('--fft-real-only', '')
     true_false_flag('--random-kfold', 'perform a random kfold splitting.')
-    # (--butter-low is read from the experiment file only: butter_low)
+    # (--butter-low and --post-hoc-downsampling are read from the experiment file only: butter_low, post_hoc_downsampling)
     parser.add_argument('--butter-high', type=float, help='10th-order Butterworth filter on every row; with butter_low of the '
                         'experiment file: alone a HIGHPASS at this frequency, with butter_low 0 a lowpass, else a bandpass')
     parser.add_argument('--fft-filtering-low', type=float, help='FFT band filter: keep |f| above this (Hz); needs both bounds')
@@ -786,6 +790,10 @@ def main(argv=None):
         if a.split('=')[0] == '--butter-low':
             raise SystemExit('--butter-low is not accepted on the command line -- the flag used to steer code outside the accelerated '
                              'hot path and its refusal is pinned by a test: give butter_low in the -co experiment file')
+        if a.split('=')[0] == '--post-hoc-downsampling':
+            raise SystemExit('--post-hoc-downsampling is not accepted on the command line -- the flag used to steer code outside the '
+                             'accelerated hot path and its refusal is pinned by a test: give post_hoc_downsampling in the -co '
+                             'experiment file')
         if a.split('=')[0] in OUT_OF_SCOPE_FLAGS:
             raise SystemExit('%s steers code outside the accelerated cnn_linear hot path (SURVEY.md section 2) and is not '
                              'accepted by this build' % a.split('=')[0])

@@ -481,6 +481,17 @@ int da_gather_normalize_ch(const double* tiles, const int64_t* idx, const double
  * mask is built over fftfreq(224)); C <= 4; mu / stdv: HOST arrays [C].  Anything else: -1, out untouched. */
 int da_gather_normalize_filter(const double* tiles, const int64_t* idx, const double* mu, const double* stdv, const double* h,
                                const double* g, float* out, int B, int NB, int C, int L, da_stream_t stream);
+/* the whole item chain of ARDSRawDataset.__getitem__ (dataset.py:1375-1400) in one gather launch, float64 then the cast:
+ * the normalisation -- padded != 0: (x - mu) / std where x != 0 and x / std where x == 0, the padded_breath_by_breath rule
+ * (_get_padding_mask :1406-1409; a NaN counts as non-zero); padded == 0: (x - mu) / std, the bits of da_gather_normalize --,
+ * the causal sum with h, post-hoc downsampling (:1384-1391: scipy.signal.resample to new_len samples, zeros behind them) as
+ * r[n] = sum_m R[n][m] y[m], and the circular sum with g over the zero-padded row.  Ascending m, fma, one accumulator per
+ * output -- a repeat is bit-identical.  h, rt, g: DEVICE arrays, each may be NULL (that stage is absent), all three too.
+ * rt: [L][new_len] doubles, the TRANSPOSE of the (new_len, L) resampling matrix; NULL needs new_len == 0, otherwise
+ * 1 <= new_len <= L.  L <= 512; g: L == 224; C <= 4; mu / stdv: HOST arrays [C].  Anything else: -1, out untouched. */
+int da_gather_normalize_chain(const double* tiles, const int64_t* idx, const double* mu, const double* stdv, int padded,
+                              const double* h, const double* rt, int new_len, const double* g, float* out, int B, int NB, int C,
+                              int L, da_stream_t stream);
 /* ---- sibling heads of CNNLinearNetwork (torch_cnn_linear_network.py:7-89) ---------------------- */
 /* CNNLinearComprToRF: lower median over the NB breath rows of each window (torch.median(outputs, dim=1)[0], :47);
    x [B*NB][ld], out [B][F], idx [B][F] = selected row (for the backward); NB <= 64.  The mean of CNNLinearToMean

@@ -4,7 +4,10 @@
 
 ``DeviceTileStore.batch_from_device`` at B windows of (20, 1, 224), written into fixed ``out=`` buffers the way the captured
 step is fed, in four forms: plain (no filter: ``da_gather_normalize``, the only path before the filters existed), butter
-(lowpass 10 Hz), fft (band (0, 6) Hz) and both.  Two figures per form:
+(lowpass 10 Hz), fft (band (0, 6) Hz) and both (``da_gather_normalize_filter``); and, on windows whose rows are zero behind a
+random length (a padded_breath_by_breath dataset), in the forms of ``da_gather_normalize_chain``: padded (the padded
+normalisation alone), down_2 and down_1p2 (post-hoc downsampling by 2.0 and by 1.2: new_len 112 and 186) and chain
+(Butterworth + downsampling by 1.2 + FFT band).  Two figures per form:
 
 * ``us_per_batch``   a host clock around ``calls`` batches (gather launch + ``gather_rows`` + the Python around them) ending in
                      a device synchronise: what a training loop pays per step when nothing else hides it;
@@ -25,8 +28,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-FORMS = (('plain', {}), ('butter', dict(butter_low=0, butter_high=10)), ('fft', dict(fft_filtering_low=0, fft_filtering_high=6)),
-         ('both', dict(butter_low=0, butter_high=10, fft_filtering_low=0, fft_filtering_high=6)))
+BOTH = dict(butter_low=0, butter_high=10, fft_filtering_low=0, fft_filtering_high=6)
+# name, set_filters keywords, padded dataset
+FORMS = (('plain', {}, False), ('butter', dict(butter_low=0, butter_high=10), False),
+         ('fft', dict(fft_filtering_low=0, fft_filtering_high=6), False), ('both', BOTH, False),
+         ('padded', {}, True), ('down_2', dict(post_hoc_downsampling=2.0), True), ('down_1p2', dict(post_hoc_downsampling=1.2), True),
+         ('chain', dict(BOTH, post_hoc_downsampling=1.2), True))
 
 
 def main():
@@ -42,12 +49,15 @@ def main():
     from deepards_amd.data import DeviceTileStore
     rng = np.random.default_rng(0)
     windows = rng.standard_normal((a.windows, 20, 1, 224)) * 28 + 2
+    lengths = rng.integers(30, 225, (a.windows, 20, 1, 1))
+    padded_windows = np.where(np.arange(224).reshape(1, 1, 1, 224) < lengths, windows, 0.0)
     targets = np.eye(2, dtype=np.float32)[rng.integers(0, 2, a.windows)]
     stores, graphs = {}, {}
     perm = torch.from_numpy(rng.permutation(a.windows))
     n_batches = a.windows // a.batch
-    for name, kw in FORMS:
-        store = DeviceTileStore(windows, targets, 2.0, 28.0).set_filters(**kw)
+    for name, kw, padded in FORMS:
+        store = DeviceTileStore(padded_windows if padded else windows, targets, 2.0, 28.0).set_filters(**kw)
+        store.padded = padded
         dev = store.device_indices(perm)
         out = (torch.empty((a.batch, 20, 1, 224), device='cuda'), torch.empty((a.batch, 2), device='cuda'))
         stores[name] = (store, dev, out)
@@ -62,10 +72,10 @@ def main():
         graph.replay()
         torch.cuda.synchronize()
         graphs[name] = graph
-    host = {n: [] for n, _ in FORMS}
-    kern = {n: [] for n, _ in FORMS}
+    host = {f[0]: [] for f in FORMS}
+    kern = {f[0]: [] for f in FORMS}
     for _ in range(a.rounds):
-        for name, _ in FORMS:
+        for name in host:
             store, dev, out = stores[name]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -81,7 +91,7 @@ def main():
             e1.synchronize()
             kern[name].append(1e3 * e0.elapsed_time(e1) / a.calls)
     lines = []
-    for name, _ in FORMS:
+    for name in host:
         med = lambda v: round(statistics.median(v), 2)
         rec = dict(form=name, batch=a.batch, calls=a.calls, rounds=a.rounds,
                    us_per_batch=med(host[name]), us_per_batch_min=round(min(host[name]), 2), us_per_batch_max=round(max(host[name]), 2),
