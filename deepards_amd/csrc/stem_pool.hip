@@ -92,7 +92,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __r
 }
 
 // out[row][j][c] = pool_{l in {2j-1,2j,2j+1}} relu(bn(y[row][l][c]));  pool_mode 0 = max (-inf pad),
-// 1 = avg (count_include_pad, zeros).  One thread per (output position, channel quad).
+// 1 = avg (count_include_pad, zeros), 2 = max over {2j,2j+1,2j+2} clipped at Lin (MaxPool1d(3, 2, ceil_mode=True) without
+// padding: reference models/senet.py:245 -- mode 0's windows one position later).  One thread per (output position, channel quad).
 template <typename AT, int OX3 = 0>
 __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const AT* __restrict__ y, int ldy,
                                                                AT* __restrict__ out, int ldo, int rows, int R,
@@ -115,17 +116,18 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const AT* __restr
   f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0);
   f32x4 be = *reinterpret_cast<const f32x4*>(beta + c0);
   f32x4 o;
-  if (pool_mode == 0) o = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  if (pool_mode != 1) o = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   else o = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int sh = pool_mode == 2 ? 1 : 0;
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
-    int l = 2 * j - 1 + t;
+    int l = 2 * j - 1 + sh + t;
     if (l < 0 || l >= Lin) continue;
     f32x4 v = Act<AT>::ld4(y + ((size_t)row * Lin + l) * ldy + c0);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float z = fmaxf((v[e] - mu[e]) * is[e] * ga[e] + be[e], 0.f);
-      o[e] = pool_mode == 0 ? fmaxf(o[e], z) : o[e] + z;
+      o[e] = pool_mode != 1 ? fmaxf(o[e], z) : o[e] + z;
     }
   }
   if (pool_mode == 1) {
@@ -142,6 +144,10 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const AT* __restr
 // the previous step's last -- two new conv outputs per step from a 16-input register window that advances by ONE
 // ds_read_b128.  Values: stem_conv_fwd_kernel's and bn_relu_pool_fwd_kernel's, bit for bit (same fmaf chain, same
 // expression, max is order-free).  Lc = conv outputs per row, Lp = pooled outputs per row.
+// pool_mode 2 (windows {2j, 2j+1, 2j+2}) is mode 0 one conv position later: with sh = 1 the row is staged two samples further
+// right, so that the slot of conv position l' holds position l = l' - sh, and window j' = j + sh of mode 0's geometry --
+// positions 2j'-1, 2j', 2j'+1 of the shifted frame -- is output j; slot 0 (l = -1) sits in no window that is stored.
+// SH is a template parameter (the launcher sets it from pool_mode).
 #define STEM_XPAD 8                                  // zeros in front of a staged row: xs[STEM_XPAD + s] = x[s]
 
 __device__ __forceinline__ f32x4 stem_y4(const StemW4& sw, const float (&xw)[16], int o) {   // inputs xw[o .. o + 6]
@@ -182,7 +188,7 @@ struct StemBn4 {
   }
 };
 
-template <typename AT, int OX3>
+template <typename AT, int OX3, int SH>
 __global__ __launch_bounds__(256) void stem_bn_relu_pool_fwd_kernel(const float* __restrict__ xrows, const float* __restrict__ wt,
                                                                     AT* __restrict__ out, int ldo, int rows, int R, int Lin,
                                                                     int Lc, int Lp, int C, const float* __restrict__ mean,
@@ -199,12 +205,13 @@ __global__ __launch_bounds__(256) void stem_bn_relu_pool_fwd_kernel(const float*
   StemBn4 bn;
   bn.ga = *reinterpret_cast<const f32x4*>(gamma + c0);
   bn.be = *reinterpret_cast<const f32x4*>(beta + c0);
-  const int j0 = run * RJ, j1 = min(Lp, j0 + RJ);
+  constexpr int sh = SH;                               // (compile time: modes 0 / 1 are the code they always were)
+  const int j0 = sh + run * RJ, j1 = min(Lp + sh, j0 + RJ);
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const int w = row / R;
     __syncthreads();
     for (int i = threadIdx.x; i < XS; i += blockDim.x) {
-      const int sx = i - STEM_XPAD;
+      const int sx = i - STEM_XPAD - 2 * sh;
       xs[i] = (sx >= 0 && sx < Lin) ? xrows[(size_t)row * Lin + sx] : 0.f;
     }
     __syncthreads();
@@ -217,12 +224,12 @@ __global__ __launch_bounds__(256) void stem_bn_relu_pool_fwd_kernel(const float*
     if (j0 > 0) zm = bn.z(stem_y4(sw, xw, 3));
     for (int j = j0; j < j1; ++j) {
       if (j > j0) stem_xw_next(xw, xs, j);
-      const bool vm = j > 0, vp = 2 * j + 1 < Lc;
+      const bool vm = j > 0, vp = 2 * j + 1 < Lc + sh;
       const f32x4 z0 = bn.z(stem_y4(sw, xw, 5)), zp = bn.z(stem_y4(sw, xw, 7));
       f32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (pool_mode == 0) {
+        if (pool_mode != 1) {
           float m = vm ? fmaxf(-INFINITY, zm[e]) : -INFINITY;             // the order of bn_relu_pool_fwd_kernel: t = 0, 1, 2
           m = fmaxf(m, z0[e]);
           o[e] = vp ? fmaxf(m, zp[e]) : m;
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(256) void stem_bn_relu_pool_fwd_kernel(const float*
           o[e] = a * (1.0f / 3.0f);
         }
       }
-      const size_t po = (size_t)row * Lp + j;
+      const size_t po = (size_t)row * Lp + (j - sh);
       if constexpr (OX3) X3::st4(reinterpret_cast<__bf16*>(out) + po * (size_t)(3 * C), c0, o);
       else Act<AT>::st4(out + po * ldo + c0, o);
       zm = zp;
@@ -263,9 +270,10 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const AT* __restrict__ do
   int w = row / R;
   int c0 = q * 4;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  // windows containing l: j with 2j-1 <= l <= 2j+1
-  int j_lo = (l) / 2;            // ceil((l-1)/2) for l >= 0
-  int j_hi = (l + 1) / 2;        // floor((l+1)/2)
+  // windows containing l: j with 2j-1 <= l <= 2j+1 (pool_mode 2: 2j <= l <= 2j+2 -- the same in the frame l + sh, j + sh)
+  const int sh = pool_mode == 2 ? 1 : 0;
+  int j_lo = (l + sh) / 2 - sh;            // ceil((l-1)/2) for l >= 0
+  int j_hi = (l + sh + 1) / 2 - sh;        // floor((l+1)/2)
   if (pool_mode == 1) {
     for (int j = j_lo; j <= j_hi; ++j) {
       if (j >= Lout) continue;
@@ -279,13 +287,13 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const AT* __restrict__ do
     f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0);
     f32x4 be = *reinterpret_cast<const f32x4*>(beta + c0);
     for (int j = j_lo; j <= j_hi; ++j) {
-      if (j >= Lout) continue;
+      if (j < 0 || j >= Lout) continue;
       // argmax over t = 0..2 (position 2j-1+t), first max wins
       float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
       int barg[4] = {-1, -1, -1, -1};
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        int ll = 2 * j - 1 + t;
+        int ll = 2 * j - 1 + sh + t;
         if (ll < 0 || ll >= Lin) continue;
         f32x4 v = Act<AT>::ld4(y + ((size_t)row * Lin + ll) * ldy + c0);
 #pragma unroll
@@ -319,7 +327,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const AT* __restrict__ do
 // per step two new conv outputs (2j, 2j+1; 2j-1 is the previous step's last) from a register window of 11 inputs that
 // advances by one ds_read_b128; position 2j-1 is finished by the step of window j (it also sat in window j-1, whose choice
 // the step before left in a carry -- a run recomputes the window in front of its first one for it), position 2j by its own.
-template <typename AT, bool APPLY>
+template <typename AT, bool APPLY, int SH>
 __global__ __launch_bounds__(256) void stem_bwd_kernel(const AT* __restrict__ dout, int ldd, const float* __restrict__ xrows,
                                                        const float* __restrict__ wt, int rows, int R, int Lin, int Lc, int Lp,
                                                        int C, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -346,7 +354,10 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const AT* __restrict__ do
 #pragma unroll
     for (int k = 0; k < 7; ++k) wacc[e][k] = 0.f;
   const float inv_n = 1.0f / (float)(R * Lc);
-  const int j0 = run * RJ, j1 = min(Lp, j0 + RJ);
+  // pool_mode 2: mode 0's geometry one conv position later (stem_bn_relu_pool_fwd_kernel): windows j' = sh .. Lp + sh - 1
+  constexpr int sh = SH;
+  const int jend = Lp + sh;
+  const int j0 = sh + run * RJ, j1 = min(jend, j0 + RJ);
   // a block owns RPB consecutive rows of ONE window (RPB divides R): statistics, totals and taps are fetched once
   const int row_beg = blockIdx.x * RPB, w = row_beg / R;
   if (APPLY && (int)threadIdx.x < 2 * C) {            // the window's totals: its R row records in row order
@@ -363,7 +374,7 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const AT* __restrict__ do
     const int row = rb + rs;
     __syncthreads();
     for (int i = threadIdx.x; i < RS * XS; i += blockDim.x) {
-      const int r = i / XS, sx = i - r * XS - STEM_XPAD;
+      const int r = i / XS, sx = i - r * XS - STEM_XPAD - 2 * sh;
       sm[i] = (sx >= 0 && sx < Lin) ? xrows[(size_t)(rb + r) * Lin + sx] : 0.f;
     }
     __syncthreads();
@@ -426,7 +437,7 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const AT* __restrict__ do
     if (j0 < j1) {
       // the run starts one window early (when there is one): position 2 j0 - 1 also sits in window j0 - 1, whose choice
       // reaches it through the carry; that warm-up step finishes nothing
-      const int js = j0 > 0 ? j0 - 1 : 0;
+      const int js = j0 > sh ? j0 - 1 : j0;
       stem_xw_fill(xw, xs, js);
       f32x4 carry = {0.f, 0.f, 0.f, 0.f}, ym = carry, zm = carry;
       if (js > 0) {
@@ -435,10 +446,10 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const AT* __restrict__ do
       }
       for (int j = js; j < j1; ++j) {
         if (j > js) stem_xw_next(xw, xs, j);
-        const bool vm = j > 0, vp = 2 * j + 1 < Lc;
+        const bool vm = j > 0, vp = 2 * j + 1 < Lc + sh;
         const f32x4 y0 = stem_y4(sw, xw, 5), yp = stem_y4(sw, xw, 7);
         const f32x4 z0 = bn.z(y0), zp = bn.z(yp);
-        const f32x4 d = Act<AT>::ld4(drow + (size_t)j * ldd);
+        const f32x4 d = Act<AT>::ld4(drow + (size_t)(j - sh) * ldd);
         f32x4 gm, g0, gp;
         choose(zm, z0, zp, vm, vp, d, gm, g0, gp);
         if (j >= j0) {
@@ -448,7 +459,7 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const AT* __restrict__ do
             finish(gm, ym, 3);
           }
           finish(g0, y0, 5);
-          if (j == Lp - 1 && vp) finish(gp, yp, 7);    // the row's last position sits in no further window
+          if (j == jend - 1 && vp) finish(gp, yp, 7);    // the row's last position sits in no further window
         }
         carry = gp; ym = yp; zm = zp;
       }
@@ -582,6 +593,9 @@ __global__ __launch_bounds__(256) void avgpool_slide_bwd_kernel(const float* __r
 }
 
 static inline int grid1d(size_t total, int bs) { return (int)((total + bs - 1) / bs); }
+// pooled length of an Lc-long row: modes 0 / 1 pool(3, 2, 1); mode 2 ATen's ceil-mode rule for pool(3, 2, 0) -- ceil((Lc - 3) / 2)
+// + 1 windows, less the last one when it would start at or beyond Lc: Lc / 2 for Lc >= 2, none for Lc = 1
+static inline int pool_out_len(int Lc, int pool_mode) { return pool_mode == 2 ? Lc / 2 : (Lc - 1) / 2 + 1; }
 
 extern "C" {
 
@@ -621,9 +635,9 @@ int da_bn_relu_pool_fwd_x(const float* y, int ldy, void* out, int rows, int R, i
                           const float* invstd, const float* gamma, const float* beta, int pool_mode, hipStream_t stream) {
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;
-  if (!y || !out || C % 16 || ldy % 4 || R < 1 || rows % R) return DA_EINVAL;
-  if (rows == 0) return DA_OK;
-  int Lout = (Lin - 1) / 2 + 1;
+  if (!y || !out || C % 16 || ldy % 4 || R < 1 || rows % R || pool_mode < 0 || pool_mode > 2) return DA_EINVAL;
+  int Lout = pool_out_len(Lin, pool_mode);
+  if (rows == 0 || Lout == 0) return DA_OK;
   size_t total = (size_t)rows * Lout * (C / 4);
   hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<float, 1>), dim3(grid1d(total, 256)), dim3(256), 0, stream, y, ldy, (float*)out, 0,
                      rows, R, Lin, Lout, C, mean, invstd, gamma, beta, pool_mode);
@@ -669,9 +683,9 @@ int da_bn_relu_pool_fwd(const void* y, int ldy, void* out, int ldo, int rows, in
                         const float* mean, const float* invstd, const float* gamma, const float* beta, int pool_mode,
                         hipStream_t stream) {
   DA_ENTER();
-  if (!y || !out || C % 4 || ldy % 4 || ldo % 4 || R < 1 || rows % R) return DA_EINVAL;
-  if (rows == 0) return DA_OK;
-  int Lout = (Lin - 1) / 2 + 1;
+  if (!y || !out || C % 4 || ldy % 4 || ldo % 4 || R < 1 || rows % R || pool_mode < 0 || pool_mode > 2) return DA_EINVAL;
+  int Lout = pool_out_len(Lin, pool_mode);
+  if (rows == 0 || Lout == 0) return DA_OK;
   size_t total = (size_t)rows * Lout * (C / 4);
   DA_ACT_DISPATCH(hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<AT>, dim3(grid1d(total, 256)), dim3(256), 0, stream, (const AT*)y,
                                      ldy, (AT*)out, ldo, rows, R, Lin, Lout, C, mean, invstd, gamma, beta, pool_mode));
@@ -686,19 +700,26 @@ int da_stem_bn_relu_pool_fwd(const float* xrows, const float* wt, void* out, int
                              int out_x3, hipStream_t stream) {
   DA_ENTER();
   if (!xrows || !wt || !out || C % 4 || (out_x3 ? C % 16 : ldo % 4) || R < 1 || rows % R || Lin < 2 || (Lin & 1) ||
-      (g_act_bf16 && out_x3))
+      (g_act_bf16 && out_x3) || pool_mode < 0 || pool_mode > 2)
     return DA_EINVAL;
-  if (rows == 0) return DA_OK;
-  const int Lc = Lin / 2, Lp = (Lc - 1) / 2 + 1;
+  const int Lc = Lin / 2, Lp = pool_out_len(Lc, pool_mode);
+  if (rows == 0 || Lp == 0) return DA_OK;
   if (256 % (C / 4)) return DA_EINVAL;
   const size_t shm = (size_t)stem_xs_floats(Lin) * sizeof(float);
   const int nblk = rows < 1024 ? rows : 1024;
-  if (out_x3)
-    hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<float, 1>), dim3(nblk), dim3(256), shm, stream, xrows, wt, (float*)out, ldo,
-                       rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta, pool_mode);
-  else
-    DA_ACT_DISPATCH(hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<AT, 0>), dim3(nblk), dim3(256), shm, stream, xrows, wt,
-                                       (AT*)out, ldo, rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta, pool_mode));
+#define DA_STEM_FWD(SH_)                                                                                                      \
+  do {                                                                                                                        \
+    if (out_x3)                                                                                                               \
+      hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<float, 1, SH_>), dim3(nblk), dim3(256), shm, stream, xrows, wt,        \
+                         (float*)out, ldo, rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta, pool_mode);                     \
+    else                                                                                                                      \
+      DA_ACT_DISPATCH(hipLaunchKernelGGL((stem_bn_relu_pool_fwd_kernel<AT, 0, SH_>), dim3(nblk), dim3(256), shm, stream,      \
+                                         xrows, wt, (AT*)out, ldo, rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta,        \
+                                         pool_mode));                                                                         \
+  } while (0)
+  if (pool_mode == 2) DA_STEM_FWD(1);
+  else DA_STEM_FWD(0);
+#undef DA_STEM_FWD
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -739,10 +760,10 @@ int da_stem_bwd(const void* dout, int ldd, const float* xrows, const float* wt, 
                 float* dw, int accumulate, float* workspace, hipStream_t stream) {
   DA_ENTER();
   if (!dout || !xrows || !wt || !mean || !invstd || !gamma || !beta || !ds || !workspace || C % 4 || C < 4 ||
-      256 % (C / 4) || 2 * C > 256 || ldd % 4 || R < 1 || rows % R || Lin < 2 || (Lin & 1))
+      256 % (C / 4) || 2 * C > 256 || ldd % 4 || R < 1 || rows % R || Lin < 2 || (Lin & 1) || pool_mode < 0 || pool_mode > 2)
     return DA_EINVAL;
   if (rows == 0) return DA_OK;
-  const int Lc = Lin / 2, Lp = (Lc - 1) / 2 + 1, nruns = 256 / (C / 4);
+  const int Lc = Lin / 2, Lp = pool_out_len(Lc, pool_mode), nruns = 256 / (C / 4);
   float* rowpart = workspace;
   float* partial = workspace + (size_t)rows * 2 * C;
   const int NRUN = nruns < 8 ? nruns : 8, RS = nruns / NRUN;       // the kernel's slot split (rows side by side x runs)
@@ -755,12 +776,16 @@ int da_stem_bwd(const void* dout, int ldd, const float* xrows, const float* wt, 
   const size_t shm1 = (xsn + 2 * C + (size_t)nruns * 2 * C) * sizeof(float);
   const size_t shm2 = (xsn + 2 * C + (size_t)nruns * 7 * C) * sizeof(float);
   if (shm2 > 64 * 1024) return DA_EINVAL;
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((stem_bwd_kernel<AT, false>), dim3(nblk), dim3(256), shm1, stream, (const AT*)dout, ldd, xrows,
-                                     wt, rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta, pool_mode, RPB, rowpart,
-                                     (float*)nullptr, (float*)nullptr));
+#define DA_STEM_BWD(APPLY_, SH_, SHM_, DS_, PART_)                                                                             \
+  DA_ACT_DISPATCH(hipLaunchKernelGGL((stem_bwd_kernel<AT, APPLY_, SH_>), dim3(nblk), dim3(256), SHM_, stream, (const AT*)dout, \
+                                     ldd, xrows, wt, rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta, pool_mode, RPB,       \
+                                     rowpart, DS_, PART_))
+  if (pool_mode == 2) DA_STEM_BWD(false, 1, shm1, (float*)nullptr, (float*)nullptr);
+  else DA_STEM_BWD(false, 0, shm1, (float*)nullptr, (float*)nullptr);
   DA_CHECK_LAUNCH();
-  DA_ACT_DISPATCH(hipLaunchKernelGGL((stem_bwd_kernel<AT, true>), dim3(nblk), dim3(256), shm2, stream, (const AT*)dout, ldd, xrows,
-                                     wt, rows, R, Lin, Lc, Lp, C, mean, invstd, gamma, beta, pool_mode, RPB, rowpart, ds, partial));
+  if (pool_mode == 2) DA_STEM_BWD(true, 1, shm2, ds, partial);
+  else DA_STEM_BWD(true, 0, shm2, ds, partial);
+#undef DA_STEM_BWD
   DA_CHECK_LAUNCH();
   if (!dw) return DA_OK;       // the caller folds the partials later (da_step_tail_multi: da_stem_bwd_partials() says where they are)
   const int n = C * 7;
@@ -773,9 +798,10 @@ int da_pool_bwd(const void* dout, int ldd, const void* y, int ldy, void* dz, int
                 int C, const float* mean, const float* invstd, const float* gamma, const float* beta, int pool_mode,
                 hipStream_t stream) {
   DA_ENTER();
-  if (!dout || !y || !dz || C % 4 || ldd % 4 || ldy % 4 || lddz % 4 || R < 1 || rows % R) return DA_EINVAL;
+  if (!dout || !y || !dz || C % 4 || ldd % 4 || ldy % 4 || lddz % 4 || R < 1 || rows % R || pool_mode < 0 || pool_mode > 2)
+    return DA_EINVAL;
   if (rows == 0) return DA_OK;
-  int Lout = (Lin - 1) / 2 + 1;
+  int Lout = pool_out_len(Lin, pool_mode);
   size_t total = (size_t)rows * Lin * (C / 4);
   DA_ACT_DISPATCH(hipLaunchKernelGGL(pool_bwd_kernel<AT>, dim3(grid1d(total, 256)), dim3(256), 0, stream, (const AT*)dout, ldd,
                                      (const AT*)y, ldy, (AT*)dz, lddz, rows, R, Lin, Lout, C, mean, invstd, gamma, beta,

@@ -15,6 +15,7 @@ from torch.autograd import Function
 from . import hip_ops as H
 
 POOL_MAX, POOL_AVG = 0, 1
+POOL_MAX_CEIL = 2            # MaxPool1d(3, 2, ceil_mode=True) without padding: SENet.layer0 (H.pool_out_len)
 
 
 class BNState(object):
@@ -43,11 +44,13 @@ def training_step(model=None):
     _STEP.update(on=True, pack={}, running=[], pgrad=[], wgrad=[], wslab=[], stemred=None, dout2={})
     try:
         if model is not None:
+            # (the convs of a block that keeps off F(4,3): a class attribute ``precise_convs`` on the block, H._wino)
+            precise = {id(c) for b in model.modules() if getattr(b, 'precise_convs', False) for c in b.children()}
             ms = [m for m in model.modules()
                   if isinstance(m, torch.nn.Conv1d) and m.kernel_size[0] <= 3 and m.in_channels % 32 == 0
-                  and m.weight.is_cuda]
+                  and m.weight.is_cuda and m.bias is None]       # (with a bias: an SEModule's fc1 / fc2 -- no conv kernel reads them)
             ws = [m.weight for m in ms]
-            forms = [H.step_pack_form(*m.weight.shape, m.stride[0], m.padding[0]) for m in ms]
+            forms = [H.step_pack_form(*m.weight.shape, m.stride[0], m.padding[0], id(m) in precise) for m in ms]
             for w, c, e in zip(ws, forms, H.repack_multi(ws, forms)):
                 _STEP['pack'][(w.data_ptr(), int(c))] = e
         yield
@@ -88,7 +91,7 @@ def _launch_wgrads():
         return
     # the slab reductions chained: each launch of the call folds, as its first blocks, the slabs the launch before it wrote
     # (still in the Infinity Cache, and memory-bound blocks beside matrix-bound ones); the step's tail keeps the last launch's
-    specs = [j[:5] + (j[6],) for j in jobs]
+    specs = [j[:5] + (j[6], j[7]) for j in jobs]
     if _WGRAD_CHAIN:
         if len({j[5].data_ptr() for j in jobs}) != len(jobs):
             _plain_writer()
@@ -151,8 +154,8 @@ def _pack(w, code):
     return e
 
 
-def _conv_fwd(x, w, stride, pad):
-    kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(x), x.shape[1])
+def _conv_fwd(x, w, stride, pad, precise=False):
+    kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(x), x.shape[1], precise)
     if kern == H.DIRECT:
         return H.conv_fwd(x, _pack(w, kern)[0], stride, pad)
     pk = _pack(w, kern)[2]
@@ -162,8 +165,8 @@ def _conv_fwd(x, w, stride, pad):
     return fn(x, pk)
 
 
-def _conv_dgrad(dy, w, stride, pad, l_in, out=None, accumulate=False):
-    kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(dy), l_in)
+def _conv_dgrad(dy, w, stride, pad, l_in, out=None, accumulate=False, precise=False):
+    kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(dy), l_in, precise)
     if kern == H.DIRECT:
         return H.conv_dgrad(dy, _pack(w, kern)[1], stride, pad, l_in, out=out, accumulate=accumulate)
     pk = _pack(w, kern)[3]
@@ -443,18 +446,19 @@ def _bn_pgrad(ds, gamma, beta, tg, tb):
     return dg, db
 
 
-def _wgrad(dy, x, k, stride, pad, tw, extra=None):
+def _wgrad(dy, x, k, stride, pad, tw, extra=None, precise=False):
     """Weight gradient of a conv: queued for the step's batched launch (a trainer's gradient destination ``tw``), or run now.
+    precise: the job keeps off F(4,3) (H._wino; outside a step the plain call below runs on the direct kernels anyway).
     ``extra``: the dense-block operand forms of H.conv_wgrad_multi (x recomputed as relu(norm(x)), dy at half resolution);
     dy / x may then be channel slices of pitched buffers."""
     if tw is not None and _STEP['on']:
-        _STEP['wgrad'].append((dy, x, k, stride, pad, tw, extra))     # launched with all the others by flush_backward()
+        _STEP['wgrad'].append((dy, x, k, stride, pad, tw, extra, precise))     # launched with all the others by flush_backward()
         return None
     if tw is not None:
         _plain_writer()
     if H.WGRAD_BF16 or H.act_dtype() == 'bf16' or H.is_x3(dy) or extra or not (dy.is_contiguous() and x.is_contiguous()):
         # (the bf16-pipe kernels, the operand forms and pitched operands exist in the batched form only)
-        (slab,) = H.conv_wgrad_multi([(dy, x, k, stride, pad, extra)])
+        (slab,) = H.conv_wgrad_multi([(dy, x, k, stride, pad, extra, precise)])
         co, ci = (dy.shape[2] * 16, x.shape[2] * 16) if H.is_x3(dy) else (dy.shape[2], x.shape[2])
         dw = tw if tw is not None else torch.empty((co, ci, k), device=x.device, dtype=torch.float32)
         H.wgrad_reduce_multi([(slab, dw)], accumulate=tw is not None)
@@ -640,6 +644,84 @@ class BasicBlockFunction(Function):
             else:
                 dx = _conv_dgrad(dy1, w1, stride, 1, lin, out=g, accumulate=True)   # identity grad + conv path
         return dx, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd, None, None, None, None, None, None, None, None, None
+
+
+class SEBasicBlockFunction(Function):
+    """conv3(s) -> BN -> ReLU -> conv3 -> BN -> * gate (+ identity | BN(conv1x1(s))) -> ReLU with
+    gate = sigmoid(fc2(relu(fc1(mean_L(bn2(..)))))) per row and channel.
+    reference models/senet.py:52-68 (SEBasicBlock.forward), :27-34 (SEModule.forward), :295-300 (downsample).
+
+    The tail [stats -> gate -> scale + residual + ReLU] is H.se_stats / se_gate_fwd / se_scale_fwd: bn2's output z is never
+    stored (the kernels recompute it from y2); the backward is H.se_bwd_reduce -> se_gate_bwd -> se_bwd_scale in front of bn2's
+    plain BatchNorm backward.  fp32 conv arithmetic and float storage only (no x3 / bf16 / pooled-output forms).  Its k3 s1
+    convs keep off F(4,3) (``precise``, H._wino): at 512 channels they run on F(2,3), forward, data and weight gradients."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, f1w, f1b, f2w, f2b, wd, gd, bd, stride, R, st1, st2, std):
+        if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
+            raise NotImplementedError('the SE block runs with fp32 conv arithmetic and float activation storage only')
+        # conv1 and the downsample conv of a stride-2 entry in one launch (H.DIRECT), or None: separate convs
+        entry = H.s2_entry_kernel(w1.shape, None if wd is None else wd.shape, stride, x.shape[1], False)
+        ctx.entry = entry
+        if entry is not None:
+            y1, yd = _entry_fwd(entry, x, None, w1, wd, stride)
+        else:
+            y1 = _conv_fwd(x, w1, stride, 1, precise=True)
+        if wd is not None:
+            if entry is None:
+                yd = _conv_fwd(x, wd, stride, 0)
+            sd = _Stats()
+            res = _bn_apply(yd, R, sd, std, gd, bd, False)
+            md, idd = sd.mean, sd.invstd
+        else:
+            res = x
+        s1 = _Stats()
+        h1 = _bn_apply(y1, R, s1, st1, g1, b1, True)
+        _tap(h1)
+        y2 = _conv_fwd(h1, w2, 1, 1, precise=True)
+        s2 = _Stats()
+        s2.mean, s2.invstd = H.se_stats(y2, R, st2.eps)
+        _running(y2, R, s2, st2)
+        pool, hid, gate = H.se_gate_fwd(y2, R, s2.mean, s2.invstd, g2, b2, f1w, f1b, f2w, f2b)
+        out, mask = H.se_scale_fwd(y2, R, s2.mean, s2.invstd, g2, b2, gate, res)
+        _tap(out)
+        ctx.has_ds = wd is not None
+        ctx.stride, ctx.R, ctx.lin = stride, R, x.shape[1]
+        ctx.gt = _tgt(w1, g1, b1, w2, g2, b2, f1w, f1b, f2w, f2b, wd, gd, bd)
+        saved = [x, w1, g1, b1, w2, g2, b2, f1w, f2w, y1, s1.mean, s1.invstd, h1, y2, s2.mean, s2.invstd, pool, hid, gate, mask]
+        if ctx.has_ds:
+            saved += [wd, gd, bd, yd, md, idd]
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        s = ctx.saved_tensors
+        x, w1, g1, b1, w2, g2, b2, f1w, f2w, y1, m1, i1, h1, y2, m2, i2, pool, hid, gate, mask = s[:20]
+        tw1, tg1, tb1, tw2, tg2, tb2, tf1w, tf1b, tf2w, tf2b, twd, tgd, tbd = ctx.gt
+        R, stride, lin = ctx.R, ctx.stride, ctx.lin
+        # relu + residual add (g: the residual's gradient), the gate, then bn2 on dz
+        g, dsum = H.se_bwd_reduce(dout.contiguous(), mask, y2, R, m2, i2, g2, b2)
+        se_t = (tf1w, tf1b, tf2w, tf2b)
+        direct = all(t is not None for t in se_t)          # a trainer's destinations: written (or accumulated) in place
+        dpool, se_g = H.se_gate_bwd(dsum, gate, hid, pool, f1w, f2w, grads=se_t if direct else None, accumulate=direct and _acc())
+        df1w, df1b, df2w, df2b = (None,) * 4 if direct else se_g
+        dz = H.se_bwd_scale(g, gate, dpool)
+        dy2, dg2, db2 = _bn_bwd(dz, y2, R, m2, i2, g2, b2, 0, tg2, tb2, dx=dz)
+        if ctx.has_ds:        # the downsample BatchNorm's backward right away: g is still cache-resident
+            wd, gd, bd, yd, md, idd = s[20:]
+            dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, tgd, tbd, dx=g)
+        dw2 = _wgrad(dy2, h1, 3, 1, 1, tw2, precise=True)
+        dh1 = _conv_dgrad(dy2, w2, 1, 1, y1.shape[1], precise=True)
+        dy1, dg1, db1 = _bn_bwd(dh1, y1, R, m1, i1, g1, b1, 1, tg1, tb1, dx=dh1)
+        dw1 = _wgrad(dy1, x, 3, stride, 1, tw1, precise=True)
+        if ctx.has_ds:
+            dwd = _wgrad(dyd, x, 1, stride, 0, twd)
+            dx = _entry_dgrad(ctx.entry, dy1, w1, dyd, wd, stride, lin)
+        else:
+            dwd = dgd = dbd = None
+            dx = _conv_dgrad(dy1, w1, stride, 1, lin, out=g, accumulate=True, precise=True)       # identity grad + conv path
+        return dx, dw1, dg1, db1, dw2, dg2, db2, df1w, df1b, df2w, df2b, dwd, dgd, dbd, None, None, None, None, None
 
 
 _STEM_TAIL = True         # inside a training step the stem's last weight-gradient fold rides on the tail launch

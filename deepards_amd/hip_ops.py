@@ -577,24 +577,28 @@ def _x3_flow():
     return CONV_DTYPE == 'f32x3p' and ACT == torch.float32
 
 
-def _wino(co, ci):                                  # the fp32 kernel of a k3 s1 p1 conv on float operands
-    return DIRECT if not WINOGRAD_WGRAD else WINO4 if min(co, ci) >= WINO4_WGRAD_MIN_C else WINO2
+def _wino(co, ci, precise=False):                   # the fp32 kernel of a k3 s1 p1 conv on float operands
+    # precise (the SE blocks): never F(4,3) -- the rounding of its transforms (constants up to 1/24 against F(2,3)'s 1/2) takes
+    # the 512-channel SE block's parameter gradients to 2 ... 3e-6 rel-l2, past the 16 x 2^-23 the block is held to; F(2,3) stays
+    # at the direct kernels' level (DESIGN_APPENDIX.md, "se_resnet18")
+    return DIRECT if not WINOGRAD_WGRAD else WINO4 if min(co, ci) >= WINO4_WGRAD_MIN_C and not precise else WINO2
 
 
-def conv_kernel_wanted(co, ci, k, stride, pad):
-    """The kernel a conv's forward / data gradient asks for from its shape alone: what the block Functions compare."""
+def conv_kernel_wanted(co, ci, k, stride, pad, precise=False):
+    """The kernel a conv's forward / data gradient asks for from its shape alone: what the block Functions compare.
+    precise: the conv belongs to a block that keeps off F(4,3) (_wino)."""
     if CONV_DTYPE == 'bf16' and _mult(64, co, ci) and ((k, stride, pad) == (3, 1, 1) or _s2_entry(k, stride, pad)):
         return BF16
     if not ((k, stride, pad) == (3, 1, 1) and _mult(32, co, ci)):
         return DIRECT
-    return X3 if CONV_DTYPE == 'f32x3p' and _mult(64, co, ci) else _wino(co, ci)
+    return X3 if CONV_DTYPE == 'f32x3p' and _mult(64, co, ci) else _wino(co, ci, precise)
 
 
-def conv_kernel(co, ci, k, stride, pad, x3, l_in):
+def conv_kernel(co, ci, k, stride, pad, x3, l_in, precise=False):
     """The kernel ONE forward / data-gradient conv runs on (``x3``: its operand is in the x3 format; ``l_in``: its input side)."""
-    kern = conv_kernel_wanted(co, ci, k, stride, pad)
+    kern = conv_kernel_wanted(co, ci, k, stride, pad, precise)
     if kern == X3 and not x3:
-        kern = _wino(co, ci)                        # a float operand (a shape without x3 producers): the fp32 kernels
+        kern = _wino(co, ci, precise)               # a float operand (a shape without x3 producers): the fp32 kernels
     if kern == BF16 and stride == 2 and l_in % 2:
         kern = DIRECT                               # odd length: the fp32 kernel
     if kern not in (BF16, X3) and ACT == torch.bfloat16:
@@ -603,14 +607,14 @@ def conv_kernel(co, ci, k, stride, pad, x3, l_in):
     return kern
 
 
-def step_pack_form(co, ci, k, stride, pad):
+def step_pack_form(co, ci, k, stride, pad, precise=False):
     """The pack form the step's batched repack prepares for a conv module (another form: functional._pack, once a step)."""
     if _x3_flow() and _s2_entry(k, stride, pad) and _mult(64, co, ci):
         return X3                                   # the stride-2 block entries on x3 operands (s2_entry_kernel)
-    return conv_kernel_wanted(co, ci, k, stride, pad)
+    return conv_kernel_wanted(co, ci, k, stride, pad, precise)
 
 
-def wgrad_kernel(co, ci, k, stride, pad, l, x3=False, operand_form=False):
+def wgrad_kernel(co, ci, k, stride, pad, l, x3=False, operand_form=False, precise=False):
     """The kernel of one weight-gradient job on an input of length ``l`` (Winograd needs 64-multiple channel counts here, 32
     in the forward).  ``operand_form``: the dense-block operand forms, which run on the direct kernels."""
     fits = _mult(64, co, ci) and ((k, stride, pad) == (3, 1, 1) or (_s2_entry(k, stride, pad) and l % 2 == 0))
@@ -622,7 +626,7 @@ def wgrad_kernel(co, ci, k, stride, pad, l, x3=False, operand_form=False):
         return X3
     if WGRAD_BF16 and fits:
         return BF16
-    return _wino(co, ci) if fits and stride == 1 else DIRECT
+    return _wino(co, ci, precise) if fits and stride == 1 else DIRECT
 
 
 def s2_entry_kernel(w1, wd, stride, l_in, x3):
@@ -645,8 +649,8 @@ def x3_block_ok(rows, l, c, R):
 
 
 def conv_wgrad_multi(jobs, dws=None, accumulate=True):
-    """jobs: [(dy, x, k, stride, pad)] -> [(slab, splits, k, co, ci)]: every weight-gradient GEMM of the list in
-    one launch per tile shape (slabs only; reduce with wgrad_reduce_multi), each on its wgrad_kernel.
+    """jobs: [(dy, x, k, stride, pad[, operand forms[, precise]])] -> [(slab, splits, k, co, ci)]: every weight-gradient GEMM
+    of the list in one launch per tile shape (slabs only; reduce with wgrad_reduce_multi), each on its wgrad_kernel.
     dws (one (co, ci, k) gradient destination per job, or None entries): the slab reductions are chained
     (da_conv_wgrad_multi_reduce) -- every launch of the call carries, as its first blocks, the reduction of the slabs the
     launch before it wrote; -> (slabs, reduced) with reduced[i] False for the jobs whose reduction the caller still owes
@@ -683,7 +687,7 @@ def conv_wgrad_multi(jobs, dws=None, accumulate=True):
             lo = l
         if rows != rows2 or lo != conv_out_len(l, k, stride, pad) or k > 3 or ci % 32 or co % 32:
             raise ValueError('conv_wgrad_multi: unsupported shape')
-        kern = wgrad_kernel(co, ci, k, stride, pad, l, both_x3, bool(extra))
+        kern = wgrad_kernel(co, ci, k, stride, pad, l, both_x3, bool(extra), len(job) > 6 and bool(job[6]))
         d.dy, d.x = dy.data_ptr(), x.data_ptr()
         d.rows, d.Lm, d.Ldy, d.lddy, d.N, d.Lx, d.ldx, d.C = rows, lo, ldy_len, lddy, co, l, ldx, ci
         d.dy_stride, d.dy_off, d.src_stride, d.ntaps = 1, 0, stride, k
@@ -1285,7 +1289,7 @@ def conv1x1_bn(xv, w, R, mean_v, invstd_v, gamma, beta, out, pool=False, pend=No
 def bn_relu_pool_fwd(y, R, mean, invstd, gamma, beta, pool_mode, out_x3=False, out=None):
     _rlc(y, 'y')
     rows, lin, c = y.shape
-    lout = (lin - 1) // 2 + 1
+    lout = pool_out_len(lin, pool_mode)
     if out is not None:                                 # a channel slice of a dense block's pitched buffer (float storage)
         if out_x3 or tuple(out.shape) != (rows, lout, c) or ACT != torch.float32:
             raise ValueError('bn_relu_pool_fwd: bad out')
@@ -1336,7 +1340,7 @@ def stem_fused_fwd(x2d, w, R, gamma, beta, pool_mode, eps=1e-5, out_x3=False, ou
     c = w.shape[0]
     wn = rows // R
     lc = lin // 2
-    lp = (lc - 1) // 2 + 1
+    lp = pool_out_len(lc, pool_mode)
     L = _lib.lib()
     part = _bn_ws(wn, R * lc, c, x.device)
     _chk(L.da_stem_stats_partial(_p(x), _p(w), rows, R, lin, c, _p(part), _stream()), 'da_stem_stats_partial')
@@ -1365,8 +1369,8 @@ def stem_fused_bwd(dout, x2d, w, R, mean, invstd, gamma, beta, pool_mode, dw=Non
     x = x2d.reshape(x2d.shape[0], x2d.shape[-1])
     rows, lin = x.shape
     c = w.shape[0]
-    if dout.shape[2] != c:
-        raise ValueError('stem_fused_bwd: dout must have the stem\'s %d channels' % c)
+    if dout.shape[2] != c or tuple(dout.shape[:2]) != (rows, pool_out_len(lin // 2, pool_mode)):
+        raise ValueError('stem_fused_bwd: dout must be the pooled map\'s gradient with the stem\'s %d channels' % c)
     if dw is None and not defer:
         if accumulate:
             raise ValueError('accumulate needs dw')
@@ -1387,6 +1391,8 @@ def pool_bwd(dout, y, R, mean, invstd, gamma, beta, pool_mode):
     ldd = _pv(dout, 'dout') if ACT == torch.float32 else _rlc(dout, 'dout').shape[2]
     _rlc(y, 'y')
     rows, lin, c = y.shape
+    if tuple(dout.shape) != (rows, pool_out_len(lin, pool_mode), c):
+        raise ValueError('pool_bwd: dout %s is not the pooled map\'s gradient of y %s' % (tuple(dout.shape), tuple(y.shape)))
     dz = torch.empty_like(y)
     _chk(_lib.lib().da_pool_bwd(_p(dout), ldd, _p(y), c, _p(dz), c, rows, R, lin, c, _p(mean), _p(invstd), _p(gamma),
                                 _p(beta), pool_mode, _stream()), 'da_pool_bwd')
@@ -1749,3 +1755,5 @@ def vote_counts(logits, group, votes, want_pred=True):
 from .loss_ops import confidence_loss, vacillating_loss          # noqa: E402,F401
 from .transformer_ops import TFM_PARAMS, tfm_check_shape, tfm_block_fwd, tfm_block_bwd, tfm_block_pgrad   # noqa: E402,F401
 from .filter_ops import gather_normalize_filter, gather_normalize_chain, resample_operand   # noqa: E402,F401
+from .se_ops import (pool_out_len, se_stats, se_gate_fwd, se_scale_fwd, se_bwd_reduce, se_gate_bwd,   # noqa: E402,F401
+                     se_bwd_scale)

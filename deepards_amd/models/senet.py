@@ -1,0 +1,160 @@
+"""1-D SE-ResNet-18 breath block on MI355X.
+
+Operator surface of reference ``deepards/models/senet.py`` (SEModule :15-34, SEBasicBlock :37-68, SENet :171-328,
+se_resnet18 :343-348): same constructor arguments, sub-module / parameter names and their order (so ``state_dict`` keys
+match), ``n_out_filters`` and ``network_name``.  As in ``resnet.py`` the torch.nn leaf modules are only parameter containers:
+``forward`` runs the HIP kernels through ``deepards_amd.functional`` on a whole batch of windows.
+
+Built: the BasicBlock variant on the k7 stem (``se_resnet18`` and other ``layers`` lists).  The grouped-conv / 3x3-stem
+nets (``senet18``, ``senet154``) and the Bottleneck / ResNeXt blocks are refused in the constructor.  Initialisation is
+torch's defaults: the reference's SENet has no init loop.
+"""
+from collections import OrderedDict
+
+import torch.nn as nn
+
+from .. import functional as F_
+from .resnet import _require_cuda
+
+
+class SEModule(nn.Module):
+    """Parameter container of the gate sigmoid(fc2(relu(fc1(avg_pool(x))))) (senet.py:17-25); fc1 / fc2 are k1 convs WITH bias."""
+
+    def __init__(self, channels, reduction):
+        super(SEModule, self).__init__()
+        self.avg_pool = nn.AdaptiveAvgPool1d(1)
+        self.fc1 = nn.Conv1d(channels, channels // reduction, kernel_size=1, padding=0)
+        self.relu = nn.ReLU(inplace=True)
+        self.fc2 = nn.Conv1d(channels // reduction, channels, kernel_size=1, padding=0)
+        self.sigmoid = nn.Sigmoid()
+
+
+class SEBasicBlock(nn.Module):
+    """Parameter container of one SE residual block; child names and their order are the state_dict contract
+    (conv1, bn1, relu, conv2, se_module, bn2, downsample -- senet.py:43-49)."""
+    expansion = 1
+    precise_convs = True      # functional.training_step: the block's convs are packed for F(2,3) at every width (H._wino)
+
+    def __init__(self, inplanes, planes, groups, reduction, stride=1, downsample=None):
+        super(SEBasicBlock, self).__init__()
+        if groups != 1:
+            raise NotImplementedError('grouped convolutions (senet18 / senet154, the ResNeXt nets) are not on the accelerated path')
+        cr = planes // reduction if reduction >= 1 else 0
+        if planes % 64 or planes > 512 or planes & (planes - 1) or cr < 16 or cr % 16 or 256 % cr or planes * cr < 1024:
+            raise NotImplementedError('the SE gate kernels take 64 / 128 / 256 / 512 planes with a hidden width that is a '
+                                      'multiple of 16 dividing 256 (reduction 4 on the four stages)')
+        self.conv1 = nn.Conv1d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm1d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv1d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
+        self.se_module = SEModule(planes, reduction=reduction)
+        self.bn2 = nn.BatchNorm1d(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward_rlc(self, x, R):
+        """x: (rows, L, C) channels-last; R rows per BatchNorm window."""
+        ds, se = self.downsample, self.se_module
+        dsw = (None, None, None, None) if ds is None else (ds[0].weight, ds[1].weight, ds[1].bias, F_.BNState(ds[1]))
+        return F_.SEBasicBlockFunction.apply(
+            x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias,
+            se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias, dsw[0], dsw[1], dsw[2], self.stride, R,
+            F_.BNState(self.bn1), F_.BNState(self.bn2), dsw[3])
+
+
+class SENet(nn.Module):
+    """Four stages of SEBasicBlocks behind layer0 = conv k7 s2 -> BN -> ReLU -> MaxPool1d(3, 2, ceil_mode=True).  The module
+    tree (names, order, shapes) is the reference's (senet.py:219-289)."""
+
+    fused_tail = True     # forward_windows(pooled='fused'): the 7-position map, which the head pools
+
+    def __init__(self, block, layers, groups, reduction, dropout_p=0.2, inplanes=128, input_3x3=True, downsample_kernel_size=3,
+                 downsample_padding=1):
+        super(SENet, self).__init__()
+        if block is not SEBasicBlock:
+            raise NotImplementedError('only SEBasicBlock (se_resnet18 style) is on the accelerated path')
+        if groups != 1:
+            raise NotImplementedError('grouped convolutions (senet18 / senet154, the ResNeXt nets) are not on the accelerated path')
+        if input_3x3:
+            raise NotImplementedError('the three-conv 3x3 stem (senet18 / senet154) is not on the accelerated path')
+        if dropout_p is not None:
+            raise NotImplementedError('dropout behind the pooled features (senet18 / senet154) is not on the accelerated path')
+        if (downsample_kernel_size, downsample_padding) != (1, 0):
+            raise NotImplementedError('downsample convolutions other than k1 p0 (senet154) are not on the accelerated path')
+        if inplanes != 64:
+            raise NotImplementedError('inplanes must be 64 (the SE-ResNets) on the accelerated path')
+        self.inplanes = inplanes
+        self.layer0 = nn.Sequential(OrderedDict([
+            ('conv1', nn.Conv1d(1, inplanes, kernel_size=7, stride=2, padding=3, bias=False)),
+            ('bn1', nn.BatchNorm1d(inplanes)),
+            ('relu1', nn.ReLU(inplace=True)),
+            # (ceil_mode instead of padding=1, senet.py:243-246: windows {2j, 2j+1, 2j+2} clipped at the end)
+            ('pool', nn.MaxPool1d(3, stride=2, ceil_mode=True))]))
+        for i, n_blocks in enumerate(layers):
+            self.add_module('layer%d' % (i + 1), self._make_layer(block, 64 << i, n_blocks, groups, reduction, 1 if i == 0 else 2))
+        self.avg_pool = nn.AvgPool1d(7, stride=1)
+        self.dropout = None
+        self.n_out_filters = 512 * block.expansion
+
+    def _make_layer(self, block, planes, blocks, groups, reduction, stride=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(nn.Conv1d(self.inplanes, planes * block.expansion, kernel_size=1, stride=stride, padding=0,
+                                                 bias=False),
+                                       nn.BatchNorm1d(planes * block.expansion))
+        stage = [block(self.inplanes, planes, groups, reduction, stride, downsample)]
+        self.inplanes = planes * block.expansion
+        stage += [block(self.inplanes, planes, groups, reduction) for _ in range(1, blocks)]
+        return nn.Sequential(*stage)
+
+    def _map(self, x, rows_per_window):
+        """The last block's map (rows, L / 32, 512) channels-last."""
+        if F_.conv_dtype() != 'f32' or F_.storage_dtype() != 'f32':
+            raise NotImplementedError("the SE-ResNets run with conv arithmetic 'f32' and float storage only (got %s / %s): the SE "
+                                      'tail has no bf16 / f32x3p forms' % (F_.conv_dtype(), F_.storage_dtype()))
+        _require_cuda(x, 'SENet')
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError('expected (rows, 1, L) input, got %s' % (tuple(x.shape),))
+        rows, _, l = x.shape
+        if rows % rows_per_window:
+            raise ValueError('rows not a multiple of rows_per_window')
+        l0 = self.layer0
+        h = F_.StemFunction.apply(x.contiguous().float().view(rows, l), l0.conv1.weight, l0.bn1.weight, l0.bn1.bias,
+                                  rows_per_window, F_.POOL_MAX_CEIL, F_.BNState(l0.bn1), False)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                h = blk.forward_rlc(h, rows_per_window)
+        return h
+
+    def forward_windows(self, x, rows_per_window, pooled=True):
+        """x: (rows, 1, L) with rows = windows * rows_per_window; BatchNorm statistics are taken per window, exactly as when
+        the reference feeds one (NB, 1, L) window at a time.  pooled=False or 'fused': the last map (rows, 7, C) itself, for a
+        head that pools it in its own kernel; pooled=True: the pooled features."""
+        h = self._map(x, rows_per_window)
+        if h.shape[1] < 7:
+            raise ValueError('AvgPool1d(7, stride=1) needs a final length >= 7 (seq_len >= 224); got %d' % h.shape[1])
+        if pooled == 'fused' or not pooled:
+            if h.shape[1] != 7:
+                raise TypeError('the un-pooled map is only handed out at the 7-position length the fused head pools')
+            return h
+        return F_.GlobalAvgPoolFunction.apply(h)
+
+    def features(self, x):
+        """layer0 .. layer4 of one BatchNorm batch: the last map in the reference's (N, C, L) layout (senet.py:311-317)."""
+        return self._map(x, x.shape[0]).permute(0, 2, 1)
+
+    def logits(self, x):
+        """AvgPool1d(7, stride=1) of an (N, C, L) map (senet.py:319-323; there is no dropout on this path)."""
+        n, c, _ = x.shape
+        return F_.GlobalAvgPoolFunction.apply(x.permute(0, 2, 1).contiguous()).view(n, c, -1)
+
+    def forward(self, x):
+        # one call == one BatchNorm batch, like the reference's breath_block(x[i]) (senet.py:325-328: logits(features(x)).squeeze())
+        return self.forward_windows(x, x.shape[0])
+
+
+def se_resnet18():
+    model = SENet(SEBasicBlock, [2, 2, 2, 2], groups=1, reduction=4, dropout_p=None, inplanes=64, input_3x3=False,
+                  downsample_kernel_size=1, downsample_padding=0)
+    model.network_name = 'se_resnet18'
+    return model

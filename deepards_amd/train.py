@@ -276,7 +276,8 @@ class HotPathTrainer(object):
             else float(loss_param)
         self._plain_bce = loss == 'bce' and loss_calc == 'all_breaths' and not carry_state
         self._carry = self._flag = None    # (2, 2H): row 0 zeros, row 1 the carried [hx | cx]; the step's row index
-        if self.eval_test and str(getattr(getattr(model, 'breath_block', None), 'network_name', '')).startswith('resnet'):
+        bb_name = str(getattr(getattr(model, 'breath_block', None), 'network_name', ''))
+        if self.eval_test and bb_name.startswith(('resnet', 'se_resnet')):     # (BatchNorm with running statistics)
             raise NotImplementedError('eval_test on a ResNet breath block means inference on running statistics, which this '
                                       'package does not have')
         self.model = model

@@ -160,7 +160,12 @@ class BaseTraining(object):
     def get_base_network(self):
         """:380-414 for the backbones this package builds.  ``--load-base-network`` takes the ``breath_block`` of a
         saved model -- a whole module pickled by this package, by the reference (read without unpickling) or a
-        state_dict (``deepards_amd.checkpoint``)."""
+        state_dict (``deepards_amd.checkpoint``).
+
+        A deliberate deviation: ``se_*`` names are built with NO keyword arguments.  The reference's driver falls into its
+        DenseNet branch for them (:409-414) and passes ``with_fft`` / ``only_fft`` / ``fft_real_only`` to ``se_resnet18()``,
+        which takes none and raises ``TypeError`` -- although its experiment scripts sweep that network.  Here the network
+        those scripts ask for is built."""
         a = self.args
         kw = self._base_network_kwargs()
         if a.load_base_network:
@@ -168,6 +173,8 @@ class BaseTraining(object):
             base_network = load_base_network(a.load_base_network, base_networks, kw)
         elif a.base_network.startswith('resnet'):
             base_network = base_networks[a.base_network](**kw['resnet_kwargs'])
+        elif a.base_network.startswith('se_'):
+            base_network = base_networks[a.base_network]()
         else:
             base_network = base_networks[a.base_network](**kw['densenet_kwargs'])
         if _flag(a, 'freeze_base_network'):
@@ -629,7 +636,7 @@ class CNNLSTMModel(PerBreathClassifierMixin, BaseTraining, PatientClassifierMixi
     carries_lstm_state = True
 
     def __init__(self, args):
-        if str(args.base_network).startswith('resnet'):
+        if str(args.base_network).startswith(('resnet', 'se_resnet')):
             raise NotImplementedError('cnn_lstm with a ResNet base network: its test epoch runs under model.eval() '
                                       '(train_ards_detector.py:861), i.e. BatchNorm inference on running statistics, which '
                                       'is not implemented here; use a DenseNet base network')

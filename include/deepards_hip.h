@@ -365,7 +365,11 @@ int da_bn_bwd_x(const float* dout, int ldd, const float* x, int ldx, void* dx, i
                 float* ds, const unsigned long long* mask, int dx_x3, da_stream_t stream);
 
 /* ---- pools ------------------------------------------------------------------------------
- * stem BN+ReLU+{Max,Avg}Pool1d(3,2,1): resnet.py:100-104,152-153 ; densenet.py:120-123 */
+ * stem BN+ReLU+{Max,Avg}Pool1d(3,2,1): resnet.py:100-104,152-153 ; densenet.py:120-123
+ * pool_mode 0: max over {2j-1, 2j, 2j+1}, 1: avg (count_include_pad), out length (Lin - 1) / 2 + 1;
+ * pool_mode 2: MaxPool1d(3, stride 2, ceil_mode=True) without padding (senet.py:245): max over {2j, 2j+1, 2j+2} clipped at
+ * Lin, out length by ATen's ceil-mode rule = Lin / 2 (Lin >= 2).  The backward gives a window's gradient to its FIRST maximum
+ * in every max mode, as ATen does.  Every pool entry point below (stored-map and recomputing stem) takes the three modes. */
 int da_bn_relu_pool_fwd(const da_act_t* y, int ldy, da_act_t* out, int ldo, int rows, int R, int Lin, int C,
                         const float* mean, const float* invstd, const float* gamma, const float* beta,
                         int pool_mode, da_stream_t stream);
@@ -531,6 +535,33 @@ int da_tfm_block_pgrad(const float* dy, const float* x, const float* const* para
 
 /* out[n] (+)= column sums of m [rows][n] in a fixed order */
 int da_reduce_rows(const float* m, int rows, int n, float* out, int accumulate, da_stream_t stream);
+
+/* ---- Squeeze-and-Excitation tail of an SE-ResNet BasicBlock (senet.py:15-34 SEModule, :52-68 SEBasicBlock.forward) --------
+ *     out = relu(z * s + res),  z = bn2(y2),  s = sigmoid(fc2(relu(fc1(mean_L z))))  per (row, channel)
+ * float activations (rows, L, C); BatchNorm windows of R rows, mean / invstd (rows / R, C) from da_bn_stats_fused or
+ * da_bn_stats_partial + da_bn_stats_merge.  z = fmaf(y2, gamma invstd, beta - mean gamma invstd) is never stored: forward and
+ * backward recompute it from y2 with the same fused multiply-add.  w1 (Cr, C), b1 (Cr), w2 (C, Cr), b2 (C): fc1 / fc2 of the
+ * module.  Shapes: C in {64, 128, 256, 512}, Cr a multiple of 16 dividing 256 with C Cr >= 1024 (C / 4 for the four
+ * stages), any L >= 1, any rows, R dividing rows; anything else -> DA_EINVAL.  float storage only.  Every sum runs in an
+ * order fixed by the shape (no atomics): the same bits every call.
+ *   da_se_gate_fwd    one launch: pool (rows, C) = the affine of mean_L(y2), hid (rows, Cr), s (rows, C), kept for the backward
+ *   da_se_scale_fwd   out = max(fmaf(z, s, res), 0); mask: rows L C / 8 bytes, bit (i % 8) of byte i / 8 = out[i] > 0
+ *   da_se_bwd_reduce  g = dout . mask (written: the residual's gradient) and dsum[row][c] = sum_l g z
+ *   da_se_gate_bwd    dpool (rows, C) and the parameter gradients dw1 / db1 / dw2 / db2 (+= when accumulate): partials over
+ *                     chunks of C / 2 rows summed in row order, folded in chunk order; workspace da_se_gate_bwd_workspace() bytes
+ *   da_se_bwd_scale   dz = fmaf(g, s, dpool / L): what da_bn_bwd (mask_mode 0) of bn2 takes */
+int da_se_gate_fwd(const float* y2, int rows, int R, int L, int C, int Cr, const float* mean, const float* invstd,
+                   const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2, const float* b2,
+                   float* pool, float* hid, float* s, da_stream_t stream);
+int da_se_scale_fwd(const float* y2, const float* res, float* out, void* mask, int rows, int R, int L, int C, const float* mean,
+                    const float* invstd, const float* gamma, const float* beta, const float* s, da_stream_t stream);
+int da_se_bwd_reduce(const float* dout, const void* mask, const float* y2, float* g, float* dsum, int rows, int R, int L, int C,
+                     const float* mean, const float* invstd, const float* gamma, const float* beta, da_stream_t stream);
+size_t da_se_gate_bwd_workspace(int rows, int C, int Cr);
+int da_se_gate_bwd(const float* dsum, const float* s, const float* hid, const float* pool, const float* w1, const float* w2,
+                   float* dpool, float* dw1, float* db1, float* dw2, float* db2, int accumulate, float* workspace, int rows, int C,
+                   int Cr, da_stream_t stream);
+int da_se_bwd_scale(const float* g, const float* s, const float* dpool, float* dz, int rows, int L, int C, da_stream_t stream);
 
 int da_gather_rows(const float* src, const int64_t* idx, float* out, int B, int width, da_stream_t stream);
 
