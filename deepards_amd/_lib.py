@@ -121,6 +121,7 @@ SIGNATURES = {
     'da_stat_records_floats': (_Z, [ctypes.c_long, _I]),
     'da_conv3_winograd_bn': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _U, _F, _P, _P]),
     'da_conv_wgrad_splits': (_I, [_I] * 5),
+    'da_conv_wgrad_padded_n': (_I, [_I, _I]),
     'da_conv_gemm_multi': (_I, [ctypes.POINTER(ConvJob), _I, _P]),
     'da_conv3_winograd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'da_conv3_winograd4': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
@@ -174,6 +175,7 @@ SIGNATURES = {
     'da_window_median_bwd': (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     'da_lstm_fwd': (_I, [_P] * 11 + [_I, _I, _I, _P]),
     'da_lstm_bwd': (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    'da_tfm_block_form': (_I, [_I, _I, _I, _IP, _IP, ctypes.POINTER(_Z), ctypes.POINTER(_Z)]),
     'da_tfm_block_fwd': (_I, [_P] * 9 + [_I] * 4 + [_P, _U, _U, _F, _P]),
     'da_tfm_block_bwd': (_I, [_P] * 17 + [_I] * 4 + [_P, _U, _U, _F, _P]),
     'da_tfm_block_pgrad': (_I, [_P] * 13 + [_I] * 5 + [_P, _U, _U, _F, _P]),

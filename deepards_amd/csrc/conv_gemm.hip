@@ -1489,6 +1489,15 @@ int da_conv_wgrad_plan(const da_wgrad_job* jobs, int n, int chained, int* slabs)
   return rc;
 }
 
+// the smallest N' >= N (a multiple of 32) at which wgrad_plan has an output tile against C input channels: N itself where
+// da_conv_wgrad takes the shape, else the width a caller zero-pads dy's channels to (hip_ops.conv_wgrad); -1: none
+int da_conv_wgrad_padded_n(int N, int C) {
+  if (N < 32 || N % 32 || C < 32 || C % 32) return -1;
+  for (int n = N; n < N + 128; n += 32)
+    if (wgrad_plan(128, n, C, 1).tn) return n;
+  return -1;
+}
+
 // number of slabs da_conv_wgrad writes for this shape (workspace = splits * ntaps*N*C floats)
 int da_conv_wgrad_splits(int rows, int Lm, int N, int C, int ntaps) {
   return wgrad_plan(rows * Lm, N, C, ntaps).splits;

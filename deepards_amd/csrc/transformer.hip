@@ -678,8 +678,20 @@ static bool tfm_ptrs_ok(const void* const* ptrs, int n) {
     if (!ptrs[i] || ((uintptr_t)ptrs[i] & 15)) return false;        // float4 loads of the weight rows
   return true;
 }
+#define TFM_FWD_TPW 5
+#define TFM_BWD_TPW 3
+
 // tokens a wave works on per pass: the weights it streams are shared by all of them; 1 where the rows would not fit LDS
 static bool tfm_multi(int T, int D, int H) { return D <= 512 && T * H <= 1024; }
+static int tfm_fwd_tokens(int T, int D, int H) { return tfm_multi(T, D, H) ? TFM_FWD_TPW : 1; }
+static int tfm_bwd_tokens(int T, int D, int H) { return tfm_multi(T, D, H) ? TFM_BWD_TPW : 1; }
+// dynamic LDS of the two kernels (their layouts are above each kernel), tpw = tokens per wave and pass
+static size_t tfm_fwd_lds(int T, int D, int H, int tpw) {
+  return ((size_t)3 * T * H + (size_t)TFM_NW * tpw * D) * sizeof(float);
+}
+static size_t tfm_bwd_lds(int T, int D, int H, int tpw) {
+  return ((size_t)5 * T * H + 4 * T + (size_t)TFM_NW * tpw * 2 * D) * sizeof(float);
+}
 
 // dynamic LDS above the 64 KB default needs the attribute once per kernel AND device (the flag is a hint only: two threads
 // racing here both set the same value)
@@ -698,10 +710,16 @@ static int tfm_lds_attr(K kernel, size_t bytes, bool* done) {
   return DA_OK;
 }
 
-#define TFM_FWD_TPW 5
-#define TFM_BWD_TPW 3
-
 extern "C" {
+
+int da_tfm_block_form(int T, int D, int H, int* tokens_fwd, int* tokens_bwd, size_t* lds_fwd, size_t* lds_bwd) {
+  if (!tfm_shape_ok(0, T, D, H, 0.f) || !tokens_fwd || !tokens_bwd || !lds_fwd || !lds_bwd) return DA_EINVAL;
+  *tokens_fwd = tfm_fwd_tokens(T, D, H);
+  *tokens_bwd = tfm_bwd_tokens(T, D, H);
+  *lds_fwd = tfm_fwd_lds(T, D, H, *tokens_fwd);
+  *lds_bwd = tfm_bwd_lds(T, D, H, *tokens_bwd);
+  return DA_OK;
+}
 
 int da_tfm_block_fwd(const float* x, const float* const* params, float* y, float* q, float* k, float* v, float* aw, float* hid,
                      float* stats, int B, int T, int D, int H, const int64_t* seed, unsigned salt1, unsigned salt2, float p,
@@ -716,12 +734,12 @@ int da_tfm_block_fwd(const float* x, const float* const* params, float* y, float
   a.y = y; a.q = q; a.k = k; a.v = v; a.aw = aw; a.hid = hid; a.stats = stats;
   a.T = T; a.D = D; a.H = H; a.seed = seed; a.salt1 = salt1; a.salt2 = salt2; a.drop_p = p;
   static bool attr[2][TFM_MAX_DEVICES];
-  if (tfm_multi(T, D, H)) {
-    const size_t lds = ((size_t)3 * T * H + (size_t)TFM_NW * TFM_FWD_TPW * D) * sizeof(float);
+  const int tpw = tfm_fwd_tokens(T, D, H);
+  const size_t lds = tfm_fwd_lds(T, D, H, tpw);
+  if (tpw == TFM_FWD_TPW) {
     if (tfm_lds_attr(tfm_fwd_kernel<TFM_FWD_TPW>, lds, attr[0]) != DA_OK) return DA_EINVAL;
     hipLaunchKernelGGL(tfm_fwd_kernel<TFM_FWD_TPW>, dim3(B), dim3(256), lds, stream, a);
   } else {
-    const size_t lds = ((size_t)3 * T * H + (size_t)TFM_NW * D) * sizeof(float);
     if (tfm_lds_attr(tfm_fwd_kernel<1>, lds, attr[1]) != DA_OK) return DA_EINVAL;
     hipLaunchKernelGGL(tfm_fwd_kernel<1>, dim3(B), dim3(256), lds, stream, a);
   }
@@ -746,13 +764,12 @@ int da_tfm_block_bwd(const float* dy, const float* x, const float* const* params
   a.dx = dx; a.dq = dq; a.dk = dk; a.dv = dv; a.dhid = dhid; a.da1 = da1; a.da2 = da2; a.wv = wv;
   a.T = T; a.D = D; a.H = H; a.seed = seed; a.salt1 = salt1; a.salt2 = salt2; a.drop_p = p;
   static bool attr[2][TFM_MAX_DEVICES];
-  const size_t small = (size_t)5 * T * H + 4 * T;
-  if (tfm_multi(T, D, H)) {
-    const size_t lds = (small + (size_t)TFM_NW * TFM_BWD_TPW * 2 * D) * sizeof(float);
+  const int tpw = tfm_bwd_tokens(T, D, H);
+  const size_t lds = tfm_bwd_lds(T, D, H, tpw);
+  if (tpw == TFM_BWD_TPW) {
     if (tfm_lds_attr(tfm_bwd_kernel<TFM_BWD_TPW>, lds, attr[0]) != DA_OK) return DA_EINVAL;
     hipLaunchKernelGGL(tfm_bwd_kernel<TFM_BWD_TPW>, dim3(B), dim3(256), lds, stream, a);
   } else {
-    const size_t lds = (small + (size_t)TFM_NW * 2 * D) * sizeof(float);
     if (tfm_lds_attr(tfm_bwd_kernel<1>, lds, attr[1]) != DA_OK) return DA_EINVAL;
     hipLaunchKernelGGL(tfm_bwd_kernel<1>, dim3(B), dim3(256), lds, stream, a);
   }

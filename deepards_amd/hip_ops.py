@@ -513,13 +513,35 @@ def conv_dgrad_s2_pair(dy1, wd1, dyd, wdd, l_in):
 
 def conv_wgrad(dy, x, k, stride, pad, out=None, accumulate=False, defer=False):
     """dW (Co,Ci,K) torch layout = sum_positions dy (x) x.  defer=True: only the split-K slabs are produced;
-    returns (slab, splits, k, co, ci) for wgrad_reduce_multi."""
+    returns (slab, splits, k, co, ci) for wgrad_reduce_multi.  A Co no output tile of da_conv_wgrad divides (the LSTM head's
+    4 H = 96 gate units against 64 features; ``da_conv_wgrad_padded_n`` asks the kernel's own plan) is zero-padded to the next
+    one that does: the padded rows of dW are left out, one more launch copies or adds the others into ``out``.  A correctness
+    path, not a tuned one: a zero fill, a concat and a one-row reduce_rows on top of the weight gradient, a second copy of
+    dy, and up to 4 x the arithmetic ((Co, Ci) = (32, 32) runs as 128 output channels).  The deferred form of such a shape
+    raises."""
     _rlc(dy, 'dy')
     _rlc(x, 'x')
     rows, lo, co = dy.shape
     rows2, l, ci = x.shape
     if rows != rows2 or lo != conv_out_len(l, k, stride, pad) or ci % 32 or co % 32 or (k > 3 and defer):
         raise ValueError('conv_wgrad: unsupported shape')
+    cop = _lib.lib().da_conv_wgrad_padded_n(co, ci)
+    if cop < co:
+        raise ValueError('conv_wgrad: no output tile for (Co, Ci) = (%d, %d)' % (co, ci))
+    padc = cop - co
+    if padc:
+        if defer:
+            raise ValueError('conv_wgrad: no deferred form for (Co, Ci) = (%d, %d): the next Co with an output tile is %d' %
+                             (co, ci, cop))
+        full = conv_wgrad(concat2(dy, torch.zeros((rows, lo, padc), device=dy.device, dtype=torch.float32)), x, k, stride, pad)
+        if out is None:
+            if accumulate:
+                raise ValueError('conv_wgrad: accumulate needs out')
+            return full[:co]
+        if tuple(out.shape) != (co, ci, k):
+            raise ValueError('conv_wgrad: bad out %s, expected %s' % (tuple(out.shape), (co, ci, k)))
+        reduce_rows(full[:co].view(1, co * ci * k), out=out, accumulate=accumulate)
+        return out
     so = [t - pad for t in range(k)]
     if defer:
         return _conv_wgrad_taps(dy, x, so, stride, defer=True), _lib.lib().da_conv_wgrad_splits(rows, lo, co, ci, k), k, co, ci
@@ -1753,7 +1775,7 @@ def vote_counts(logits, group, votes, want_pred=True):
 
 
 from .loss_ops import confidence_loss, vacillating_loss          # noqa: E402,F401
-from .transformer_ops import TFM_PARAMS, tfm_check_shape, tfm_block_fwd, tfm_block_bwd, tfm_block_pgrad   # noqa: E402,F401
+from .transformer_ops import TFM_PARAMS, tfm_check_shape, tfm_block_form, tfm_block_fwd, tfm_block_bwd, tfm_block_pgrad   # noqa: E402,F401
 from .filter_ops import gather_normalize_filter, gather_normalize_chain, resample_operand   # noqa: E402,F401
 from .se_ops import (pool_out_len, se_stats, se_gate_fwd, se_scale_fwd, se_bwd_reduce, se_gate_bwd,   # noqa: E402,F401
                      se_bwd_scale)

@@ -18,6 +18,16 @@ def tfm_check_shape(t, d, h, who='transformer block'):
                          'to 2048, H a multiple of 8 in [8, 64] (4 heads)' % (who, t, d, h))
 
 
+def tfm_block_form(t, d, h):
+    """-> (tokens_fwd, tokens_bwd, lds_fwd, lds_bwd): tokens a wave takes per pass and bytes of dynamic LDS of the forward
+    and the data backward at (T, D, H), from the expressions the launches use (``da_tfm_block_form``); launches nothing."""
+    tfm_check_shape(t, d, h)
+    tf, tb, lf, lb = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+    _H._chk(_H._lib.lib().da_tfm_block_form(t, d, h, ctypes.byref(tf), ctypes.byref(tb), ctypes.byref(lf), ctypes.byref(lb)),
+            'da_tfm_block_form')
+    return tf.value, tb.value, lf.value, lb.value
+
+
 def _tfm_args(x, params, drop):
     _H._f32(x, 'x')
     if x.dim() != 3 or len(params) != TFM_PARAMS:

@@ -166,6 +166,9 @@ int da_conv_wgrad_multi_reduce(const da_wgrad_job* jobs, int n, float* const* dw
    depends on the whole array (the dense-block jobs of a call with 8 or more of them share one launch and are planned as
    a batch; the winograd == 1 jobs of the launch's last, partly filled round run with half the pairs per split). */
 int da_conv_wgrad_plan(const da_wgrad_job* jobs, int n, int chained, int* slabs);
+/* the smallest N' >= N (a multiple of 32) for which da_conv_wgrad has an output tile against C input channels (host only,
+ * from the plan the launch uses): N where the shape is taken, else the width to zero-pad dy's channels to; -1: none */
+int da_conv_wgrad_padded_n(int N, int C);
 /* deferred slab reduction: da_conv_wgrad with dw == NULL leaves da_conv_wgrad_splits() slabs in the workspace */
 int da_conv_wgrad_splits(int rows, int Lm, int N, int C, int ntaps);
 typedef struct { const float* slab; float* dw; int splits, ntaps, N, C; } da_wgrad_reduce_desc;
@@ -521,6 +524,9 @@ int da_lstm_bwd(const float* dh_all, const float* whh, const float* hs, const fl
 int da_tfm_block_fwd(const float* x, const float* const* params, float* y, float* q, float* k, float* v, float* aw, float* hid,
                      float* stats, int B, int T, int D, int H, const int64_t* seed, unsigned salt1, unsigned salt2, float p,
                      da_stream_t stream);
+/* the form the forward and the data backward take at (T, D, H), by the expressions their launches use: tokens a wave works
+ * on per pass and bytes of dynamic LDS (at most 160 KB for every accepted shape); launches nothing; -1 for a refused shape */
+int da_tfm_block_form(int T, int D, int H, int* tokens_fwd, int* tokens_bwd, size_t* lds_fwd, size_t* lds_bwd);
 /* data backward: dy -> dx, and what da_tfm_block_pgrad reads: the gradients at the q / k / v / ff.0 outputs (dq, dk, dv, dhid
  * [B][T][H], dhid behind the ReLU), at the two LayerNorm inputs (da1, da2 [B][T][D]) and the re-joined heads wv [B][T][H] */
 int da_tfm_block_bwd(const float* dy, const float* x, const float* const* params, const float* q, const float* k, const float* v,

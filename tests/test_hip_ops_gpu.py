@@ -284,6 +284,36 @@ def test_conv_fwd_dgrad_wgrad(H, ci, co, k, stride, pad, L, rows):
     assert torch.equal(wf2, wf) and torch.equal(wd2, wd) and uf2 is None and ud2 is None
 
 
+@pytest.mark.parametrize('ci,co,k,L,rows', [(64, 96, 1, 1, 35), (64, 224, 1, 1, 18), (64, 32, 3, 9, 5), (32, 160, 1, 3, 7), (96, 64, 1, 1, 20)])
+def test_conv_wgrad_where_no_tile_divides_co(H, ci, co, k, L, rows):
+    """(Co, Ci) without an output tile of da_conv_wgrad (32 output channels go with 128 input channels only, 64 with 64 or
+    128): conv_wgrad pads dy's channels with zeros and leaves the padded rows of dW out.  The LSTM head's input weight
+    gradient at 4 H = 96 or 224 gate units against 64 features is such a shape; the ABI alone refuses it, and
+    da_conv_wgrad_padded_n (the plan's own answer) names the padded width.  Against the oracle
+    at test_conv_fwd_dgrad_wgrad's bound, overwriting a NaN-filled destination and accumulating; the deferred form raises."""
+    rng = np.random.default_rng(ci * 1000 + co + k + L)
+    x, dy = rng.standard_normal((rows, ci, L)), rng.standard_normal((rows, co, L))
+    dw_ref = np_ref.conv1d_bwd(x, np.zeros((co, ci, k)), dy, 1, k // 2)[1]
+    xt, dyt = rlc(x), rlc(dy)
+    cop = H._lib.lib().da_conv_wgrad_padded_n(co, ci)
+    assert cop > co and cop % 32 == 0
+    with pytest.raises(H.HipError):                                    # the ABI alone refuses the unpadded shape, before a launch
+        H._conv_wgrad_taps(dyt, xt, [t - k // 2 for t in range(k)], 1)
+    dw = H.conv_wgrad(dyt, xt, k, 1, k // 2)
+    assert tuple(dw.shape) == (co, ci, k) and dw.is_contiguous()
+    close(dw.cpu().numpy(), dw_ref, tol=3e-6, name='wgrad')
+    over = torch.full((co, ci, k), float('nan'), device='cuda')
+    assert H.conv_wgrad(dyt, xt, k, 1, k // 2, out=over) is over and torch.equal(over, dw)
+    base = rng.standard_normal(dw_ref.shape)
+    acc = cu(base)
+    H.conv_wgrad(dyt, xt, k, 1, k // 2, out=acc, accumulate=True)
+    assert torch.equal(acc, cu(base) + dw)
+    with pytest.raises(ValueError):
+        H.conv_wgrad(dyt, xt, k, 1, k // 2, defer=True)
+    with pytest.raises(ValueError):
+        H.conv_wgrad(dyt, xt, k, 1, k // 2, accumulate=True)
+
+
 @pytest.mark.parametrize('ci,co,L,rows', [(64, 64, 56, 40), (128, 128, 28, 23), (256, 256, 14, 40), (512, 512, 7, 40),
                                           (128, 32, 56, 20), (64, 64, 56, 1), (128, 32, 9, 5), (32, 32, 1, 7),
                                           (64, 64, 56, 300), (32, 64, 2, 33), (128, 128, 28, 300), (64, 64, 57, 300),
@@ -798,7 +828,10 @@ def test_window_median(H, B, NB, F):
     assert np.array_equal(dx, dref)
 
 
-@pytest.mark.parametrize('B,T,F,Hd', [(3, 20, 128, 16), (64, 20, 512, 16), (2, 5, 128, 8), (4, 7, 64, 64)])
+# Hd = 24, 40, 56: 4 Hd is no multiple of a wave, the tanh gate's range [2 Hd, 3 Hd) and the j < Hd sections straddle waves;
+# T = 1: the backward reads only the initial state
+@pytest.mark.parametrize('B,T,F,Hd', [(3, 20, 128, 16), (64, 20, 512, 16), (2, 5, 128, 8), (4, 7, 64, 64),
+                                      (5, 7, 64, 24), (3, 20, 128, 40), (2, 9, 64, 56), (4, 1, 64, 16)])
 def test_lstm_recurrence(H, B, T, F, Hd):
     """da_lstm_fwd / da_lstm_bwd (+ the GEMMs around them, as LSTMFunction composes them) vs the numpy LSTM of the
     oracle (pinned to nn.LSTM through the reference goldens): states, outputs, all gradients; with and without an
@@ -818,15 +851,42 @@ def test_lstm_recurrence(H, B, T, F, Hd):
         feat = cu(x.reshape(B * T, F)).requires_grad_(True)
         ps = [cu(a).requires_grad_(True) for a in (w_ih, w_hh, b_ih, b_hh)]
         hs, ht, ct = LSTMFunction.apply(feat, *ps, T, None if h0 is None else cu(h0), None if c0 is None else cu(c0))
-        close(hs.detach().cpu().numpy(), hs_ref, tol=3e-6, name='lstm hs')
-        close(ht.detach().cpu().numpy()[0], ht_ref, tol=3e-6, name='lstm hT')
-        close(ct.detach().cpu().numpy()[0], ct_ref, tol=3e-6, name='lstm cT')
         hs.backward(cu(dh))
-        close(feat.grad.cpu().numpy().reshape(B, T, F), dx_ref, tol=5e-6, name='lstm dx')
-        close(ps[0].grad.cpu().numpy(), dwi_ref, tol=5e-6, name='lstm dW_ih')
-        close(ps[1].grad.cpu().numpy(), dwh_ref, tol=5e-6, name='lstm dW_hh')
-        close(ps[2].grad.cpu().numpy(), db_ref, tol=5e-6, name='lstm db_ih')
-        close(ps[3].grad.cpu().numpy(), db_ref, tol=5e-6, name='lstm db_hh')
+        for name, got, ref, tol in (('hs', hs.detach(), hs_ref, 3e-6), ('hT', ht.detach()[0], ht_ref, 3e-6), ('cT', ct.detach()[0], ct_ref, 3e-6),
+                                    ('dx', feat.grad.view(B, T, F), dx_ref, 5e-6), ('dW_ih', ps[0].grad, dwi_ref, 5e-6),
+                                    ('dW_hh', ps[1].grad, dwh_ref, 5e-6), ('db_ih', ps[2].grad, db_ref, 5e-6), ('db_hh', ps[3].grad, db_ref, 5e-6)):
+            err = close(got.cpu().numpy(), ref, tol=tol, name='lstm ' + name)
+            print('lstm %dx%dx%dx%d init=%s %-6s max err %.3e  bound %.3e' % (B, T, F, Hd, init, name, err, tol * (1 + np.abs(ref).max())))
+
+
+def test_lstm_forward_at_the_launch_bound_and_the_backward_refusal(H):
+    """da_lstm_fwd at Hd = 256 (1024 threads, the kernel's launch bound), forward only: hs, cs, hT, cT against the oracle on
+    the same float32 operands (gx given, so the oracle's input projection is the identity); the forward tolerance of
+    test_lstm_recurrence (the oracle's own float32 error here is 2e-7).  da_lstm_bwd keeps Hd <= 64: Hd = 72 is refused by
+    the host check, before a launch."""
+    B, T, Hd = 2, 3, 256
+    rng = np.random.default_rng(B + T + Hd)
+    k = 1.0 / np.sqrt(Hd)
+    f32 = lambda a: a.astype(np.float32)
+    gx, whh = f32(rng.standard_normal((B, T, 4 * Hd))), f32(rng.uniform(-k, k, (4 * Hd, Hd)))
+    bih, bhh = f32(rng.uniform(-k, k, 4 * Hd)), f32(rng.uniform(-k, k, 4 * Hd))
+    for init in (False, True):
+        h0 = f32(rng.standard_normal((B, Hd))) if init else None
+        c0 = f32(rng.standard_normal((B, Hd))) if init else None
+        d = lambda a: None if a is None else a.astype(np.float64)
+        hs_ref, (ht_ref, ct_ref), tape = np_ref.lstm_fwd(d(gx), np.eye(4 * Hd), d(whh), d(bih), d(bhh), d(h0), d(c0))
+        cs_ref = np.stack([tp[1] for tp in tape[1:]] + [ct_ref], axis=1)
+        hs, cs, gates, ht, ct = H.lstm_fwd(cu(gx), cu(whh), cu(bih), cu(bhh), None if h0 is None else cu(h0),
+                                           None if c0 is None else cu(c0))
+        for name, got, ref in (('hs', hs, hs_ref), ('cs', cs, cs_ref), ('hT', ht, ht_ref), ('cT', ct, ct_ref)):
+            err = close(got.cpu().numpy(), ref, tol=3e-6, name='lstm Hd=256 ' + name)
+            print('lstm forward Hd=256 init=%s %s: max err %.3e (bound %.3e)' % (init, name, err, 3e-6 * (1 + np.abs(ref).max())))
+        gref = np.stack([np.concatenate(tp[2:6], axis=1) for tp in tape], axis=1)
+        close(gates.cpu().numpy(), gref, tol=3e-6, name='lstm Hd=256 gates')
+    Hb = 72
+    z = lambda *shape: torch.zeros(*shape, device='cuda')
+    with pytest.raises(H.HipError):
+        H.lstm_bwd(z(2, 3, Hb), z(4 * Hb, Hb), z(2, 3, Hb), z(2, 3, Hb), z(2, 3, 4 * Hb))
 
 
 def test_bad_arguments_are_refused(H):

@@ -941,3 +941,23 @@ def test_conv_wrappers_refuse_what_they_refused():
         with pytest.raises(ValueError):
             call()
             pytest.fail('case %d was accepted' % n)
+
+
+def test_wgrad_padded_width_follows_the_instantiated_tile_pairs():
+    """da_conv_wgrad_padded_n(N, C) -- the width hip_ops.conv_wgrad zero-pads dy's channels to -- asks wgrad_plan itself.
+    Pinned here to the (output, input) tile pairs conv_wgrad_kernel is instantiated for (da_conv_wgrad's dispatch): the
+    smallest multiple of 32 from N on that one of them divides together with C.  A pair added to or taken from the kernels
+    fails this sweep instead of silently padding more, or refusing again."""
+    from deepards_amd import _lib
+    q = _lib.lib().da_conv_wgrad_padded_n
+    pairs = [(128, 128), (128, 64), (64, 128), (64, 64), (128, 32), (32, 128)]
+    padded = 0
+    for n in range(32, 545, 32):
+        for c in range(32, 545, 32):
+            want = next(m for m in range(n, n + 129, 32) if any(m % tn == 0 and c % tc == 0 for tn, tc in pairs))
+            assert q(n, c) == want, (n, c, q(n, c), want)
+            assert q(want, c) == want
+            padded += want != n
+    assert 0 < padded < 17 * 17
+    assert (q(96, 64), q(224, 64), q(32, 32), q(160, 128), q(64, 96), q(512, 512)) == (128, 256, 128, 160, 128, 512)
+    assert q(48, 64) == -1 and q(64, 48) == -1 and q(0, 64) == -1

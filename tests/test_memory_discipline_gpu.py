@@ -864,17 +864,32 @@ def test_the_patch_reaches_the_wrappers():
 # ================================================================================================================================
 # the whole step
 # ================================================================================================================================
-def _build_model(backbone, seed, drop):
+def _build_model(backbone, seed, drop, head='cnn_linear'):
+    """The seeded models of the suites that own them: oracle.weights.seeded_params (test_model_gpu, with head='lstm'
+    test_lstm_losses_trainer_gpu), se_ref.seeded_se_params (test_se_gpu); the transformer's own parameters keep torch's
+    default initialisation under the torch seed the caller set (1234 for the clean and the poisoned run alike; as
+    test_transformer_gpu.build_model without a golden does under its seed 11), over the seeded backbone."""
     import deepards_amd.models as M
     from oracle.weights import seeded_params
-    bb = M.resnet18() if backbone == 'resnet18' else M.densenet18(drop_rate=drop)
-    model = M.CNNLinearNetwork(bb, 20, 0)
-    sd = {k: torch.from_numpy(v) for k, v in seeded_params(backbone, seed).items()}
+    if backbone == 'se_resnet18':
+        from tools import se_ref
+        bb, params = M.se_resnet18(), se_ref.seeded_se_params(seed, 20)
+    else:
+        bb = M.resnet18() if backbone == 'resnet18' else M.densenet18(drop_rate=drop)
+        params = seeded_params(backbone, seed, head={'cnn_linear': 'linear', 'cnn_lstm': 'lstm', 'cnn_transformer': 'single_breath'}[head])
+    if head == 'cnn_linear':
+        model = M.CNNLinearNetwork(bb, 20, 0)
+    elif head == 'cnn_lstm':
+        model = M.CNNLSTMNetwork(bb, 0, False, 16)
+    else:
+        model = M.CNNTransformerNetwork(bb, 0, False, 16, 2)
+        params = {k: v for k, v in params.items() if k.startswith('breath_block.')}
+    sd = {k: torch.from_numpy(v) for k, v in params.items()}
     assert not model.load_state_dict(sd, strict=False).unexpected_keys
     return model.cuda().train()
 
 
-def _step_results(backbone, drop, batch, use_graph, steps, patched):
+def _step_results(backbone, drop, batch, use_graph, steps, patched, head='cnn_linear'):
     """Model construction, ``steps`` training steps and one forward-only step -> every tensor the step leaves behind."""
     from deepards_amd.train import HotPathTrainer
     g = torch.Generator().manual_seed(batch * 7 + 1)
@@ -886,7 +901,7 @@ def _step_results(backbone, drop, batch, use_graph, steps, patched):
     torch.cuda.manual_seed(1234)
     ctx = P.poisoned_allocations() if patched else contextlib.nullcontext()
     with ctx as stats:
-        model = _build_model(backbone, 3, drop)
+        model = _build_model(backbone, 3, drop, head)
         tr = HotPathTrainer(model, use_graph=use_graph)
         out = {}
         for n in range(steps):
@@ -919,18 +934,30 @@ def _config(conv, storage):
         F_.set_storage_dtype('f32')
 
 
-@pytest.mark.parametrize('use_graph', [False, True], ids=['eager', 'graph'])
-@pytest.mark.parametrize('batch', [2, 64])
-@pytest.mark.parametrize('backbone,drop,conv,storage', [('resnet18', 0.0, 'f32', 'f32'), ('densenet18', 0.2, 'f32', 'f32'),
-                                                        ('resnet18', 0.0, 'bf16', 'bf16'), ('resnet18', 0.0, 'f32x3p', 'f32')])
-def test_whole_step_under_poisoned_allocations(backbone, drop, conv, storage, batch, use_graph):
-    """Loss, logits, gradient bucket, parameters and momentum after the update, the forward-only step and every BatchNorm
+# (backbone, head, drop, conv, storage, batch, use_graph): the linear head at batch 2 and 64 (ids without the head: the rows'
+# ids from before the other heads were added), then se_resnet18 and the cnn_lstm / cnn_transformer heads at batch 2
+_WHOLE_STEP = [(bb, 'cnn_linear', drop, conv, storage, batch, graph)
+               for graph in (False, True) for batch in (2, 64)
+               for bb, drop, conv, storage in (('resnet18', 0.0, 'f32', 'f32'), ('densenet18', 0.2, 'f32', 'f32'),
+                                               ('resnet18', 0.0, 'bf16', 'bf16'), ('resnet18', 0.0, 'f32x3p', 'f32'))]
+_WHOLE_STEP += [(bb, head, 0.0, 'f32', 'f32', 2, graph) for graph in (False, True)
+                for bb, head in (('se_resnet18', 'cnn_linear'), ('resnet18', 'cnn_lstm'), ('resnet18', 'cnn_transformer'))]
+
+
+def _whole_step_id(row):
+    bb, head, drop, conv, storage, batch, graph = row
+    return '%s-%s-%s-%s-%d-%s' % (bb if head == 'cnn_linear' else bb + '+' + head, drop, conv, storage, batch, 'graph' if graph else 'eager')
+
+
+@pytest.mark.parametrize('backbone,head,drop,conv,storage,batch,use_graph', _WHOLE_STEP, ids=[_whole_step_id(r) for r in _WHOLE_STEP])
+def test_whole_step_under_poisoned_allocations(backbone, head, drop, conv, storage, batch, use_graph):
+    """Loss, logits, gradient bucket, parameters and momentum after the update, the forward-only step and every module
     buffer: bit for bit those of the clean run, none holding the pattern.  With use_graph the patch is active during warm-up
     and capture, so the captured fills poison the step's buffers again on every one of the three replayed steps."""
     steps = 3 if use_graph else 1
     with _config(conv, storage):
-        clean = _step_results(backbone, drop, batch, use_graph, steps, False)
-        dirty = _step_results(backbone, drop, batch, use_graph, steps, True)
+        clean = _step_results(backbone, drop, batch, use_graph, steps, False, head)
+        dirty = _step_results(backbone, drop, batch, use_graph, steps, True, head)
     problems = []
     for k in clean:
         msg = P.diff_report(dirty[k], clean[k])

@@ -26,6 +26,14 @@ GOLD = os.path.join(ROOT, 'tests', 'golden')
 FLOOR, CEIL = 16 * 2.0 ** -23, 1e-4
 # (rows, R, L, C): the four stage shapes at two windows, an odd R, an odd L below 7, rows that the gate's row tile (4) does not divide
 SHAPES = [(6, 3, 7, 64), (4, 2, 56, 64), (6, 3, 28, 128), (4, 2, 14, 256), (5, 5, 7, 512), (4, 2, 5, 512)]
+# the gate's row tile with 3 rows left over; then rows beyond one chunk (C / 2 rows) of the gate backward's parameter-gradient
+# partials: 32 + 1, 32 + 8 (the whole model's 40 rows), 32 + 32 + 2 (17 row tiles), 64 + 2 and 64 + 64 + 1 at L = 1
+SHAPES += [(7, 7, 3, 64), (33, 3, 3, 64), (40, 20, 5, 64), (66, 3, 3, 64), (66, 2, 3, 128), (129, 3, 1, 128)]
+# (rows, R, L, C, Cr): reductions other than 4 -- C / Cr = 1; Cr = 256 (one thread per hidden unit, tpo = 256 / Cr = 1);
+# Cr = 16 (tpo = 16) at C = 512 (8 strides of a part over the 128 channel quads) and at C = 256
+SHAPES += [(6, 3, 7, 64, 64), (5, 5, 7, 512, 256), (6, 3, 7, 512, 16), (4, 2, 14, 256, 16)]
+MULTI_CHUNK = (66, 3, 3, 64)
+GRID_CAP = 16384 * 256                # threads of a capped elementwise launch (se_grid, csrc/se.hip)
 
 
 def log(*a):
@@ -83,7 +91,7 @@ def mask_bits(mask, shape):
 @functools.lru_cache(maxsize=None)
 def tail_ref(shape):
     """(case, float64 oracle, err32 per tensor) of one kernel shape, computed once."""
-    case = R.tail_case(*shape)
+    case = R.tail_case(*shape[:4], cr=shape[4] if len(shape) > 4 else None)
     r64 = {k: v.numpy() for k, v in R.se_tail(R=shape[1], **case).items()}
     r32 = R.se_tail(R=shape[1], dtype=torch.float32, **case)
     err = {k: R.rel_l2(r32[k].double().numpy(), r64[k]) for k in r64 if k != 'mask'}
@@ -93,8 +101,9 @@ def tail_ref(shape):
 @pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'x'.join(map(str, s)))
 def test_each_kernel_alone_against_the_oracle(H, shape):
     """Every kernel on the ORACLE's operands (rounded to float32), so that one kernel's error is not another's input."""
-    rows, R_, l, c = shape
+    rows, R_, l, c = shape[:4]
     case, ref, err = tail_ref(shape)
+    assert case['w1'].shape == (shape[4] if len(shape) > 4 else c // R.REDUCTION, c, 1)
     hm, om = R.tail_margins(case, R_)
     assert hm >= R.MARGIN and om >= R.MARGIN, (hm, om)
     tag = 'x'.join(map(str, shape))
@@ -126,8 +135,9 @@ def test_each_kernel_alone_against_the_oracle(H, shape):
     assert not bad, '\n'.join(bad)
 
 
-@pytest.mark.parametrize('shape', [SHAPES[0], SHAPES[4]], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', [SHAPES[0], SHAPES[4], MULTI_CHUNK], ids=lambda s: 'x'.join(map(str, s)))
 def test_gate_bwd_accumulates_and_is_deterministic(H, shape):
+    """(66, 3, 3, 64): three chunks of parameter-gradient partials, the last of two rows."""
     rows, R_, l, c = shape
     case, ref, _ = tail_ref(shape)
     g = {k: cu(v) for k, v in case.items()}
@@ -154,6 +164,65 @@ def test_gate_bwd_accumulates_and_is_deterministic(H, shape):
     assert all(torch.equal(a, b) for a, b in zip(after, fresh))
     with pytest.raises(ValueError):
         run(accumulate=True)
+
+
+def _sampled(tag, name, got, idx, ref64, ref32, problems):
+    """`got` at the flat positions `idx` against the float64 formula there, under the file's bound (err32: the same formula in
+    float32 on the CPU)."""
+    check(tag, name, got.reshape(-1)[idx], ref64, R.rel_l2(ref32.astype(np.float64), ref64), problems)
+
+
+def test_elementwise_kernels_beyond_the_grid_cap(H):
+    """se_scale_fwd and se_bwd_scale where the capped grid's stride loop runs a second iteration: 4 x 16400 x 512 = 33.6 M
+    elements, 4 198 400 (8 channels each) and 8 396 800 (4 channels each) threads of work against 4 194 304 launched.  The full call
+    against the same wrapper on slices below the cap (a window of 2 rows, one row), bit for bit, outputs and mask words; and
+    a few hundred positions, the last element among them, against the float64 formula."""
+    rows, R_, l, c = 4, 2, 16400, 512
+    assert rows * l * (c // 8) > GRID_CAP >= R_ * l * (c // 8) and rows * l * (c // 4) > GRID_CAP >= l * (c // 4)
+    gen = torch.Generator(device='cuda').manual_seed(5)
+    rnd = lambda *shape: torch.randn(*shape, device='cuda', generator=gen)
+    uni = lambda *shape: torch.rand(*shape, device='cuda', generator=gen)
+    w = rows // R_
+    y2, res = rnd(rows, l, c) * 1.5 + 0.3, rnd(rows, l, c)
+    mean, invstd, gamma, beta = rnd(w, c) * 0.2 + 0.3, uni(w, c) + 0.5, uni(c) + 0.5, rnd(c) * 0.1
+    gamma[3] = -0.7
+    s, dpool = uni(rows, c) * 0.98 + 0.01, rnd(rows, c)
+    n = rows * l * c
+    rng = np.random.default_rng(5)
+    # the last element, the first, the two sides of the first element beyond each capped grid, 300 anywhere
+    idx_np = np.unique(np.concatenate([[n - 1, 0, GRID_CAP * 8 - 1, GRID_CAP * 8, GRID_CAP * 4 - 1, GRID_CAP * 4], rng.integers(0, n, 300)]))
+    idx = torch.from_numpy(idx_np).cuda()
+    row, ch, win = idx_np // (l * c), idx_np % c, idx_np // (R_ * l * c)
+    at = lambda t: t.reshape(-1)[idx].cpu().numpy()
+    rc = lambda t, r: t.cpu().numpy()[r, ch]
+    bad = []
+
+    out, mask = H.se_scale_fwd(y2, R_, mean, invstd, gamma, beta, s, res)
+    parts = [H.se_scale_fwd(y2[k * R_:(k + 1) * R_], R_, mean[k:k + 1], invstd[k:k + 1], gamma, beta, s[k * R_:(k + 1) * R_],
+                            res[k * R_:(k + 1) * R_]) for k in range(w)]
+    assert torch.equal(out, torch.cat([p[0] for p in parts])), 'se_scale_fwd: the full call differs from its windows'
+    assert torch.equal(mask, torch.cat([p[1] for p in parts])), 'se_scale_fwd: mask words differ from the windows\''
+    del parts
+
+    def pre(dt):
+        v = lambda a: a.astype(dt)
+        z = (v(at(y2)) - v(rc(mean, win))) * v(rc(invstd, win)) * v(gamma.cpu().numpy()[ch]) + v(beta.cpu().numpy()[ch])
+        return z * v(rc(s, row)) + v(at(res))
+    p64 = pre(np.float64)
+    _sampled('grid cap', 'out', out, idx, np.maximum(p64, 0), np.maximum(pre(np.float32), 0), bad)
+    bits = ((mask.view(torch.uint8)[idx // 8].cpu().numpy() >> (idx_np % 8)) & 1).astype(bool)
+    assert np.array_equal(bits, at(out) > 0)
+    sure = np.abs(p64) >= R.MARGIN
+    assert sure.sum() > 250 and np.array_equal(bits[sure], p64[sure] > 0), 'ReLU mask differs from the formula\'s'
+    del out, mask, y2
+
+    dz = H.se_bwd_scale(res, s, dpool)                                 # (res stands for g: any float activation)
+    rowsl = [H.se_bwd_scale(res[r:r + 1], s[r:r + 1], dpool[r:r + 1]) for r in range(rows)]
+    assert torch.equal(dz, torch.cat(rowsl)), 'se_bwd_scale: the full call differs from its rows'
+    del rowsl
+    f = lambda dt: at(res).astype(dt) * rc(s, row).astype(dt) + rc(dpool, row).astype(dt) / dt(l)
+    _sampled('grid cap', 'dz', dz, idx, f(np.float64), f(np.float32), bad)
+    assert not bad, '\n'.join(bad)
 
 
 def test_unsupported_shapes_are_refused(H):
@@ -257,7 +326,7 @@ def _tail_inputs(shape):
 
 
 def _op_cases(H):
-    cases = []
+    cases, last = [], []              # (last: rows added behind the first eleven, whose indices are test ids)
     for shape in (SHAPES[0], SHAPES[5]):
         rows, R_, l, c = shape
         tag = 'x'.join(map(str, shape))
@@ -299,6 +368,17 @@ def _op_cases(H):
             return dict(g=o['g'], s=o['s'], dpool=o['dpool'], out=torch.zeros_like(o['g']))
         cases.append(P.OpCase('se_bwd_scale_' + tag, 'se', b_bsc, lambda g, s, dpool, out: H.se_bwd_scale(g, s, dpool, out=out),
                               dests=('out',), rows=dict(inputs=('g', 's', 'dpool'), R=1, axis={})))
+    shape = MULTI_CHUNK                # three chunks of partials: every partial written and folded, none twice
+
+    def b_gbw3():
+        g, o = _tail_inputs(MULTI_CHUNK)
+        return dict(dsum=o['dsum'], s=o['s'], hid=o['hid'], pool=o['pool'], w1=g['w1'], w2=g['w2'],
+                    grads=[torch.zeros_like(g['w1']), torch.zeros_like(g['b1']), torch.zeros_like(g['w2']), torch.zeros_like(g['b2'])])
+    last.append(P.OpCase('se_gate_bwd_' + 'x'.join(map(str, shape)), 'se', b_gbw3,
+                         lambda dsum, s, hid, pool, w1, w2, grads: H.se_gate_bwd(dsum, s, hid, pool, w1, w2, grads=grads),
+                         dests=('grads',),
+                         rows=dict(inputs=('dsum', 's', 'hid', 'pool'), R=1,
+                                   axis={'[1][0]': None, '[1][1]': None, '[1][2]': None, '[1][3]': None})))
     for tag, rows, R_, lin in (('224', 4, 2, 224), ('30', 6, 2, 30), ('16', 4, 2, 16)):
         def b_stem(rows=rows, R_=R_, lin=lin):
             x, w, gamma, beta, dout = R.stem_inputs(rows, R_, lin, 64, 3)
@@ -315,11 +395,11 @@ def _op_cases(H):
         # dw sums over all rows; ds is (2, W, C): its window axis is 1
         cases.append(P.OpCase('stem_pool_mode2_' + tag, 'stem', b_stem, c_stem,
                               rows=dict(inputs=('x', 'dout'), R=R_, axis={'dw': None, 'ds': 1})))
-    return cases
+    return cases + last
 
 
 CHECKS = {'uninitialised': P.check_uninitialised, 'guards': P.check_guards, 'dirty_out': P.check_dirty_out, 'isolation': P.check_isolation}
-N_OP_CASES = 11
+N_OP_CASES = 12
 
 
 @pytest.mark.parametrize('check', sorted(CHECKS))

@@ -114,3 +114,27 @@ def test_network_map_is_untouched():
     assert sorted(T.network_map) == ['cnn_double_linear', 'cnn_linear', 'cnn_linear_compr_to_rf', 'cnn_linear_to_mean',
                                      'cnn_lstm', 'cnn_single_breath_linear']
     assert T.CNNTransformerModel not in T.network_map.values()
+
+
+def test_block_form_of_every_accepted_shape_fits_the_lds():
+    """da_tfm_block_form (host only: the expressions the launches use) over every accepted (T, D, H): both kernels' dynamic
+    LDS stays within the 160 KB a workgroup has, so no accepted shape is refused at launch; the largest need is the
+    backward's at (64, 2048, 64); the multi-token form is taken where D <= 512 and T H <= 1024, the one-token form elsewhere;
+    and the sizes are the layouts' (csrc/transformer.hip, above each kernel)."""
+    from deepards_amd import hip_ops as H
+    worst_f, worst_b, multi = (0, None), (0, None), 0
+    for t in range(1, 65):
+        for d in range(64, 2049, 64):
+            for h in range(8, 65, 8):
+                tf, tb, lf, lb = H.tfm_block_form(t, d, h)
+                assert (tf, tb) == ((5, 3) if d <= 512 and t * h <= 1024 else (1, 1)), (t, d, h)
+                assert lf == 4 * (3 * t * h + 4 * tf * d) and lb == 4 * (5 * t * h + 4 * t + 4 * tb * 2 * d), (t, d, h)
+                assert lf <= 160 * 1024 and lb <= 160 * 1024, (t, d, h, lf, lb)
+                multi += tf > 1
+                worst_f, worst_b = max(worst_f, (lf, (t, d, h))), max(worst_b, (lb, (t, d, h)))
+    assert worst_b == (148480, (64, 2048, 64)) and worst_f[1] == (64, 2048, 64) and worst_b[0] >= worst_f[0]
+    assert 0 < multi < 64 * 32 * 8
+    assert H.tfm_block_form(64, 512, 16)[3] == 70656                      # above the 64 KB a kernel gets without the attribute
+    for bad in ((0, 128, 16), (65, 128, 16), (20, 96, 16), (20, 2112, 16), (20, 128, 12), (20, 128, 72)):
+        with pytest.raises(ValueError):
+            H.tfm_block_form(*bad)

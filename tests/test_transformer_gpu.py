@@ -5,7 +5,9 @@ against the reference's goldens, the trainer, checkpoints and the driver class.
 Bound (per tensor): rel-l2 against float64 <= 4 x the reference's own fp32-vs-fp64 rel-l2 of that tensor (two fp32
 evaluations each within e of the exact value differ by up to 2 e, a factor 2 more for the summation order), not below
 16 * 2^-23 and not above the project's gradient criterion 1e-4.  The reference figure comes from the golden where the
-shape has one (``err32/<tensor>``), else from the oracle evaluated in float32 on the CPU.  Figures: pytest -s."""
+shape has one (``err32/<tensor>``), else from the oracle evaluated in float32 on the CPU.  Where the float32 oracle is at hand
+``y`` and ``dx`` are judged per token row as well, by the same rule with err32 of that row: one wrong token among 63 moves the
+tensor's rel-l2 by an eighth of its own error only.  Figures: pytest -s."""
 import os
 import sys
 
@@ -113,7 +115,29 @@ def run_gpu(M, c, p=0.0, seed=None):
     return {k: v.detach().double().cpu().numpy() for k, v in out.items()}, tfm
 
 
-def compare(tag, got, ref64, err32):
+def form(t, d, h):
+    """(tokens per wave and pass of the forward, of the backward, LDS bytes of the forward, of the backward) at (T, D, H)."""
+    from deepards_amd import hip_ops as H
+    return H.tfm_block_form(t, d, h)
+
+
+def compare_rows(tag, got, ref64, ref32):
+    """``y`` and ``dx`` token by token: rel-l2 of row (b, t) against the bound of that row's own float32 error."""
+    bad = []
+    for k in ('y', 'dx'):
+        worst = (0.0, None, 0.0, 0.0)
+        for idx in np.ndindex(*ref64[k].shape[:2]):
+            e, bd = rel_l2(got[k][idx], ref64[k][idx]), bound(R.rel_l2(ref32[k][idx], ref64[k][idx]))
+            if not e / bd < worst[0]:                                   # (a NaN ratio is kept, and fails below)
+                worst = (e / bd, idx, e, bd)
+        log('%s %-42s worst token row (b, t) = %s: rel-l2 %.3e  bound %.3e  ratio %.3f' % (tag, k + ' per token', worst[1], worst[2],
+                                                                                      worst[3], worst[0]))
+        if not worst[0] <= 1:
+            bad.append((k, 'token row', worst[1], worst[2], worst[3]))
+    return bad
+
+
+def compare(tag, got, ref64, err32, ref32=None):
     bad = []
     for k in sorted(ref64):
         # (k_linear.bias: a constant added to every key's score leaves the softmax unchanged, so its gradient is zero in
@@ -123,24 +147,50 @@ def compare(tag, got, ref64, err32):
         assert np.isfinite(got[k]).all(), (tag, k)
         if not e <= bd:
             bad.append((k, e, bd))
+    if ref32 is not None:
+        bad += compare_rows(tag, got, ref64, ref32)
     assert not bad, bad
 
 
 SHAPES = [(1, 20, 128, 16), (3, 20, 128, 16), (2, 5, 128, 8), (2, 1, 128, 16), (1, 64, 128, 64), (2, 20, 512, 16)]
+# (B, T, D, H) -> tokens per wave and pass (forward, backward): the form each corner means to reach, asserted through
+# tfm_block_form so that a moved threshold fails here instead of moving the case to the other form
+CORNERS = {(2, 23, 128, 16): (5, 3),      # forward: two passes, the second with 3 of its 20 slots filled; backward 2 passes, 11 of 12
+           (2, 7, 1024, 16): (1, 1),      # one token through D > 512; T % 4 = 3: the clamped tail of the second pass
+           (1, 63, 64, 64): (1, 1),       # one token through T H > 1024; T % 4 = 3; the smallest D (one lane stride)
+           (2, 33, 256, 40): (1, 1),      # T % 4 = 1; head size 10
+           (3, 9, 192, 24): (5, 3),       # D of three lane strides, no power of two; head size 6
+           (2, 13, 576, 56): (1, 1),      # D = 9 x 64; head size 14
+           (1, 64, 512, 16): (5, 3),      # T H = 1024 at D = 512: the backward above 64 KB of LDS
+           (1, 64, 2048, 64): (1, 1)}     # the largest shape taken
+SHAPES += list(CORNERS)
 GOLDENS = {(2, 5, 128, 8): 'tfm_block_2x5x128x8.npz', (2, 20, 512, 16): 'tfm_block_2x20x512x16.npz'}
 
 
 @pytest.mark.parametrize('shape', SHAPES, ids=['x'.join(map(str, s)) for s in SHAPES])
 def test_block_kernels_against_the_fp64_oracle(M, shape):
+    r32 = None
     if shape in GOLDENS:
         c, err32 = golden_case(GOLDENS[shape])
+        ref = oracle(c)
     else:
         c = make_case(*shape, seed=1)
         r32 = oracle(c, np.float32)
         ref = oracle(c)
         err32 = {k: R.rel_l2(r32[k], ref[k]) for k in ref}
+    if shape in CORNERS:
+        b, t, d, h = shape
+        tf, tb, lf, lb = form(t, d, h)
+        log('x'.join(map(str, shape)), 'form: tokens per wave (%d, %d), LDS bytes (%d, %d)' % (tf, tb, lf, lb))
+        assert (tf, tb) == CORNERS[shape]
+        if shape == (2, 23, 128, 16):
+            assert -(-(-(-t // 4)) // tf) == 2 and t - 4 * tf == 3
+        if shape == (1, 64, 512, 16):
+            assert lb > 64 * 1024 >= lf
+        if shape == (1, 64, 2048, 64):
+            assert lb == 148480
     got, _ = run_gpu(M, c)
-    compare('x'.join(map(str, shape)), got, oracle(c), err32)
+    compare('x'.join(map(str, shape)), got, ref, err32, r32)
 
 
 @pytest.mark.parametrize('kind', ['golden', 'saturated_softmax', 'shifted_input'])
@@ -168,15 +218,29 @@ def device_masks(tfm, b, t, d, p):
             for i in range(len(tfm.blocks))]
 
 
-def test_dropout_masks_are_the_generators_and_the_block_follows_the_oracle(M):
-    p = 0.2
-    c = make_case(2, 20, 128, 16, seed=2)
+def _dropout_against_the_oracle(M, shape, p, tag, rows=False):
+    """The block with dropout: the device's masks (H.dropout with the block's seed and salts) given to the oracle."""
+    b, t, d, h = shape
+    c = make_case(b, t, d, h, seed=2)
     got, tfm = run_gpu(M, c, p=p, seed=12345)
     assert int(tfm._drop_seed) == 12345 + SEED_STEP                    # bumped once, then used
-    masks = device_masks(tfm, 2, 20, 128, p)
+    masks = device_masks(tfm, b, t, d, p)
     assert all(0.7 < m.mean() < 0.9 for pair in masks for m in pair)
     ref, r32 = oracle(c, masks=masks, p=p), oracle(c, np.float32, masks=masks, p=p)
-    compare('dropout', got, ref, {k: R.rel_l2(r32[k], ref[k]) for k in ref})
+    compare(tag, got, ref, {k: R.rel_l2(r32[k], ref[k]) for k in ref}, r32 if rows else None)
+    return tfm
+
+
+def test_dropout_on_the_one_token_form(M):
+    """(2, 7, 1024, 16): one token per wave, the second pass with a clamped token whose mask index is its neighbour's."""
+    assert form(7, 1024, 16)[:2] == (1, 1)
+    _dropout_against_the_oracle(M, (2, 7, 1024, 16), 0.2, 'dropout 2x7x1024x16', rows=True)
+
+
+def test_dropout_masks_are_the_generators_and_the_block_follows_the_oracle(M):
+    p = 0.2
+    assert form(20, 128, 16)[:2] == (5, 3)
+    tfm = _dropout_against_the_oracle(M, (2, 20, 128, 16), p, 'dropout')
     # the generator's rate: a (20 * 64, 512) mask keeps 0.8 within 5 sigma
     from deepards_amd import hip_ops as H
     n = 20 * 64 * 512
@@ -195,11 +259,14 @@ def _op_inputs(shape, seed=3, p=0.2):
     return x, params, dy, drop
 
 
-@pytest.mark.parametrize('shape', [(3, 20, 128, 16), (2, 5, 128, 8), (1, 64, 128, 64)], ids=['3x20x128x16', '2x5x128x8', '1x64x128x64'])
+@pytest.mark.parametrize('shape', [(3, 20, 128, 16), (2, 5, 128, 8), (1, 64, 128, 64), (2, 7, 1024, 16), (1, 63, 64, 64), (2, 23, 128, 16)],
+                         ids=lambda s: 'x'.join(map(str, s)))
 def test_memory_discipline_of_the_three_launches(M, shape):
     """Every output and saved tensor fully written from NaN-poisoned allocations with the bits of the clean run; operands
     inside guard bands: same bits, guards intact, inputs unchanged; accumulate adds exactly once."""
     from deepards_amd import hip_ops as H
+    if shape in CORNERS:
+        assert form(*shape[1:])[:2] == CORNERS[shape]
 
     def run(x, params, dy, drop, grads=None, accumulate=False):
         y, saved = H.tfm_block_fwd(x, params, drop)

@@ -286,13 +286,14 @@ def model_case(x, target, params, dtype=torch.float64, want_grads=True):
 MARGIN = 1e-3
 
 
-def tail_case(rows, R, l, c, seed=0, margin=MARGIN):
+def tail_case(rows, R, l, c, seed=0, margin=MARGIN, cr=None):
     """Inputs of the SE tail at (rows, R, L, C), float32 arrays, built so that no ReLU pre-activation of the float64 oracle
     (the gate's hidden units, the block output) lies within ``margin`` of zero.  Hidden units: an offender's fc1 bias is
     nudged by 4 margin away from zero (that moves the unit's whole column: repeated until none is left).  Outputs: pre =
-    z s + res is moved to +-2 margin through res, element by element (res enters nothing else)."""
+    z s + res is moved to +-2 margin through res, element by element (res enters nothing else).  ``cr``: the gate's hidden
+    width, c // REDUCTION unless given (the draws before fc1 do not depend on it)."""
     rng = np.random.default_rng([seed, rows, R, l, c])
-    cr = c // REDUCTION
+    cr = c // REDUCTION if cr is None else cr
     f = np.float32
     case = dict(y2=rng.standard_normal((rows, l, c)).astype(f) * 1.5 + 0.3, res=rng.standard_normal((rows, l, c)).astype(f),
                 gamma=rng.uniform(0.5, 1.5, c).astype(f), beta=(rng.standard_normal(c) * 0.1).astype(f),
