@@ -518,6 +518,7 @@ bool wino_wgrad_eligible(const da_wgrad_job& j);
 void wino_wgrad_plan_jobs(const da_wgrad_job* jobs, int n, int chained, WgradPlan* plan);       // the winograd == 1 jobs of a call
 int wino_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hipStream_t stream, WgradChain* chain);
 void wino4_wgrad_plan(int rows, int L, int* splits, int* qchunk);               // winograd == 6: the F(4,3) form (quads)
+extern int g_wino4_skip5;              // conv_wino.hip; da_debug_set(key 11)
 int wino4_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hipStream_t stream, WgradChain* chain);
 
 // conv_bf16.hip: jobs with winograd == 16 (the same eligibility; bf16 operands, padded-position K)

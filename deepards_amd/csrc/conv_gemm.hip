@@ -1329,10 +1329,12 @@ extern "C" {
 
 // Comparison forms the tests flip.  key 3: 0 = no half-tile tail round in the 64x64 conv launches.  key 7: 0 = the
 // dense-block weight gradients as one launch per tile shape instead of one launch for all shapes (conv_wgrad_any_kernel).
+// key 11: 0 = the F(4,3) conv and weight-gradient kernels compute all six products for every quad (conv_wino.hip skip5).
 // Any other key: DA_EINVAL.
 int da_debug_set(int key, int value) {
   if (key == 3) g_use_tail = value;
   else if (key == 7) g_wgrad_any = value;
+  else if (key == 11) g_wino4_skip5 = value;
   else return DA_EINVAL;
   return DA_OK;
 }

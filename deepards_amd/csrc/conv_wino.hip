@@ -404,6 +404,8 @@ __global__ __launch_bounds__(256, 4) void conv3_wino_stats_kernel(WinoArgs a, in
 // staging keeps the four position phases in four quad-indexed LDS panels, so d0 = Ph3[Q-1], d1..d4 = Ph0..Ph3[Q],
 // d5 = Ph0[Q+1] are unit-row-stride reads with the F(2,3) kernel's conflict-free lane geometry.
 // Block = 64 quads x 32 output channels, 4 waves of 16 quads: 12 accumulator tiles = 48 VGPRs; 64.8 KB of LDS.
+// L = 5, 6, 7 (two quads a row, the second without its fourth output): conv3_wino4k_skip5_body leaves out the second
+// quads' m5, which only y3 would read -- 11 contractions per row instead of 12 (da_debug_set key 11 = 0: all six everywhere).
 // ---------------------------------------------------------------------------------------------
 // B^T d as whole-vector fp32 arithmetic (the compiler pairs it into v_pk_fma_f32 / v_pk_add_f32 where it can)
 __device__ __forceinline__ void wino4_input_transform(const f32x4& d0, const f32x4& d1, const f32x4& d2,
@@ -595,11 +597,12 @@ __device__ __forceinline__ void conv3_wino4_body(const WinoArgs& a, const int ti
 // slot residues like pitch 36; the lane groups of ds_read_b128 pair k groups (0,1) and (2,3), so k group g sits in slot
 // {0,2,1,3}[g]).
 #define W4K_PITCH 20
-#define W4K_LDS_FLOATS ((4 * 64 + 2) * W4K_PITCH + 6 * 32 * W4K_PITCH)
+#define W4K_TILE_QUADS 64
+#define W4K_LDS_FLOATS ((4 * W4K_TILE_QUADS + 2) * W4K_PITCH + 6 * 32 * W4K_PITCH)
 
 template <bool MINI>
 __device__ __forceinline__ void conv3_wino4k_body(const WinoArgs& a, const int tile, const int sub, float* lds) {
-  constexpr int PITCH = W4K_PITCH, QUADS = MINI ? 32 : 64;
+  constexpr int PITCH = W4K_PITCH, QUADS = MINI ? W4K_TILE_QUADS / 2 : W4K_TILE_QUADS;
   float* Ph0 = lds;
   float* Ph1 = Ph0 + (QUADS + 1) * PITCH;
   float* Ph2 = Ph1 + QUADS * PITCH;
@@ -608,7 +611,7 @@ __device__ __forceinline__ void conv3_wino4k_body(const WinoArgs& a, const int t
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntn = a.N >> 5;
-  const int Q0 = (tile / ntn) * 64 + (MINI ? 32 * sub : 0), n_blk = (tile % ntn) * 32;
+  const int Q0 = (tile / ntn) * W4K_TILE_QUADS + (MINI ? W4K_TILE_QUADS / 2 * sub : 0), n_blk = (tile % ntn) * 32;
   // loader rows: ds_write_b128 is served 8 lanes at a time on 32 banks, and with 5 slots a row two NEIGHBOURING rows
   // overlap in one bank group; rows 4 apart do not, so lanes 4..7 of every 8 take the row 4 below lanes 0..3
   const int lm = tid >> 3;
@@ -765,13 +768,192 @@ __device__ __forceinline__ void conv3_wino4k_body(const WinoArgs& a, const int t
   }
 }
 
+// skip5: rows of exactly two quads whose second quad lacks its fourth output (L = 5, 6, 7; tile bases are even, so an even
+// quad is a row's first, an odd one its second).  y3 of a second quad is never stored, so its m5 = D5 . U5 is not computed:
+// 11 products per row instead of 12.  A wave owns 32 quads x 16 output channels here -- the 16 first quads and the 16
+// second quads of 16 rows as two MFMA row tiles, points 0..5 for the first, 0..4 for the second: 11 accumulator tiles,
+// 44 MFMAs per K step, the same on every wave.  The loader stores first quads in the front half of every phase panel and
+// second quads in the back half (panel row e <- quad 2e / 2(e - HALF) + 1), so both tiles read unit-stride rows with the
+// lane geometry above, and a row's two quads share their fragments: d0 of the second quad is d4 of the first, d5 of the
+// first is d1 of the second, the sequence edges are constant zeros.  8 input + 6 tap fragment reads per K step instead of
+// 6 + 12.  Every output element sees the chain of (K step, e, k group) contributions of the six-product form: same bits.
+template <bool MINI>
+__device__ __forceinline__ void conv3_wino4k_skip5_body(const WinoArgs& a, const int tile, const int sub, float* lds) {
+  constexpr int PITCH = W4K_PITCH, QUADS = MINI ? W4K_TILE_QUADS / 2 : W4K_TILE_QUADS, HALF = QUADS / 2;
+  float* Ph0 = lds;                              // [QUADS][PITCH] each: rows 0 .. HALF-1 first quads, HALF .. second quads
+  float* Ph1 = Ph0 + QUADS * PITCH;
+  float* Ph2 = Ph1 + QUADS * PITCH;
+  float* Ph3 = Ph2 + QUADS * PITCH;
+  float* Us = Ph3 + QUADS * PITCH;               // [6][32][PITCH]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ntn = a.N >> 5;
+  const int Q0 = (tile / ntn) * W4K_TILE_QUADS + (MINI ? W4K_TILE_QUADS / 2 * sub : 0), n_blk = (tile % ntn) * 32;
+  const int lm = tid >> 3;                       // loader rows as in conv3_wino4k_body
+  const int lr = (lm >> 2) * 8 + (lm & 3) + 4 * ((tid >> 2) & 1), lq = tid & 3;
+
+  constexpr int NP = MINI ? 2 : 4;
+  int aoff[NP];
+  bool aok[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int idx = p * 64 + lr;
+    const int phase = idx / QUADS, e = idx % QUADS;
+    const int second = e >= HALF ? 1 : 0;
+    const int Q = Q0 + 2 * (e - second * HALF) + second;
+    const int pos = 4 * second + phase;
+    const bool ok = Q < a.MP && pos < a.L;
+    aoff[p] = ok ? ((Q >> 1) * a.L + pos) * a.ldx + lq * 4 : 0;        // two quads a row: row = Q / 2
+    aok[p] = ok;
+  }
+  const float* ub[3];
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    const int idx = p * 64 + lr;
+    const int nrow = n_blk + (idx & 31);
+    ub[p] = a.u + (size_t)(idx >> 5) * a.N * a.C + (size_t)nrow * a.C + lq * 4;
+  }
+
+  f32x4 ra[NP], rb[3];
+  auto gload_a = [&](int ks) {
+    const int c0 = ks << 4;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (aok[p]) v = *reinterpret_cast<const f32x4*>(a.x + aoff[p] + c0);
+      ra[p] = v;
+    }
+  };
+  auto gload_b = [&](int ks) {
+    const int c0 = ks << 4;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) rb[p] = *reinterpret_cast<const f32x4*>(ub[p] + c0);
+  };
+
+  const int prow = wino_row(lane & 15), g = lane >> 4;
+  const int col = (((g & 1) << 1) | (g >> 1)) * 4;       // slot {0,2,1,3}[g]
+  const int nh = wave & 1;                               // the wave's 16-channel half
+  const int qh = MINI ? 0 : wave >> 1, khalf = wave >> 1;  // its 16 rows (MINI: the block's 16 rows, one K half)
+  const int rF = (qh * 16 + prow) * PITCH + col, rS = rF + HALF * PITCH;
+
+  f32x4 accF[6], accS[5];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) accF[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 5; ++j) accS[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int kc = a.C >> 4;
+  gload_a(0);
+  gload_b(0);
+  for (int ks = 0; ks < kc; ++ks) {
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int idx = p * 64 + lr;
+      const int phase = idx / QUADS, e = idx % QUADS;
+      float* panel = phase == 0 ? Ph0 : (phase == 1 ? Ph1 : (phase == 2 ? Ph2 : Ph3));
+      *reinterpret_cast<f32x4*>(&panel[e * PITCH + lq * 4]) = ra[p];
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<f32x4*>(&Us[(p * 64 + lr) * PITCH + lq * 4]) = rb[p];
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    if (ks + 1 < kc) {
+      gload_b(ks + 1);
+      gload_a(ks + 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (MINI && (ks & 1) != khalf) continue;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 f1 = *reinterpret_cast<const f32x4*>(&Ph0[rF]), f2 = *reinterpret_cast<const f32x4*>(&Ph1[rF]);
+    const f32x4 f3 = *reinterpret_cast<const f32x4*>(&Ph2[rF]), f4 = *reinterpret_cast<const f32x4*>(&Ph3[rF]);
+    const f32x4 s1 = *reinterpret_cast<const f32x4*>(&Ph0[rS]), s2 = *reinterpret_cast<const f32x4*>(&Ph1[rS]);
+    const f32x4 s3 = *reinterpret_cast<const f32x4*>(&Ph2[rS]), s4 = *reinterpret_cast<const f32x4*>(&Ph3[rS]);
+    f32x4 DF[6], DS[6];
+    wino4_input_transform(z, f1, f2, f3, f4, s1, DF);    // first quad: d0 outside the sequence, d5 = the second quad's d1
+    wino4_input_transform(f4, s1, s2, s3, s4, z, DS);    // second quad: d0 = the first quad's d4; DS[5] is not used
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const f32x4 uf = *reinterpret_cast<const f32x4*>(&Us[(j * 32 + nh * 16 + prow) * PITCH + col]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        accF[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(DF[j][e], uf[e], accF[j], 0, 0, 0);
+        if (j < 5) accS[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(DS[j][e], uf[e], accS[j], 0, 0, 0);
+      }
+    }
+  }
+
+  if (MINI) {   // K half 1 hands its partial sums to K half 0
+    __syncthreads();
+    f32x4* red = reinterpret_cast<f32x4*>(lds);          // [2 channel halves][11 tiles][64 lanes] = 22.5 KB
+    if (khalf == 1) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) red[(nh * 11 + j) * 64 + lane] = accF[j];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) red[(nh * 11 + 6 + j) * 64 + lane] = accS[j];
+    }
+    __syncthreads();
+    if (khalf == 1) return;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const f32x4 o = red[(nh * 11 + j) * 64 + lane];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) accF[j][e] += o[e];
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const f32x4 o = red[(nh * 11 + 6 + j) * 64 + lane];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) accS[j][e] += o[e];
+    }
+  }
+
+  const int nS = a.L - 4;                                 // outputs of a second quad: 1 .. 3
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int Q = Q0 + 2 * (qh * 16 + wino_row(g * 4 + r));   // the row's first quad
+    if (Q >= a.MP) continue;
+    float* yp = a.y + (size_t)(Q >> 1) * a.L * a.ldy + n_blk + nh * 16 + prow;
+    {
+      const float m0 = accF[0][r], m1 = accF[1][r], m2 = accF[2][r], m3 = accF[3][r], m4 = accF[4][r], m5 = accF[5][r];
+      const float sa = m1 + m2, da = m1 - m2, sb = m3 + m4, db = m3 - m4;
+      const float yv[4] = {m0 + sa + sb, fmaf(2.f, db, da), fmaf(4.f, sb, sa), fmaf(8.f, db, da) + m5};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        float v = yv[s];
+        if (a.accumulate) v += yp[(size_t)s * a.ldy];
+        yp[(size_t)s * a.ldy] = v;
+      }
+    }
+    {
+      const float m0 = accS[0][r], m1 = accS[1][r], m2 = accS[2][r], m3 = accS[3][r], m4 = accS[4][r];
+      const float sa = m1 + m2, da = m1 - m2, sb = m3 + m4, db = m3 - m4;
+      const float yv[3] = {m0 + sa + sb, fmaf(2.f, db, da), fmaf(4.f, sb, sa)};
+      float* q1 = yp + (size_t)4 * a.ldy;
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        if (s < nS) {
+          float v = yv[s];
+          if (a.accumulate) v += q1[(size_t)s * a.ldy];
+          q1[(size_t)s * a.ldy] = v;
+        }
+      }
+    }
+  }
+}
+
+template <bool SKIP5>
 __global__ __launch_bounds__(256, 3) void conv3_wino4k_kernel(WinoArgs a, int nmini, int nmini_pad, int full) {
   __shared__ float lds[W4K_LDS_FLOATS];
   if ((int)blockIdx.x < nmini_pad) {
-    if ((int)blockIdx.x < nmini) conv3_wino4k_body<true>(a, full + ((int)blockIdx.x >> 1), blockIdx.x & 1, lds);
+    if ((int)blockIdx.x < nmini) {
+      if (SKIP5) conv3_wino4k_skip5_body<true>(a, full + ((int)blockIdx.x >> 1), blockIdx.x & 1, lds);
+      else conv3_wino4k_body<true>(a, full + ((int)blockIdx.x >> 1), blockIdx.x & 1, lds);
+    }
     return;
   }
-  conv3_wino4k_body<false>(a, xcd_chunked(blockIdx.x - nmini_pad, full), 0, lds);
+  if (SKIP5) conv3_wino4k_skip5_body<false>(a, xcd_chunked(blockIdx.x - nmini_pad, full), 0, lds);
+  else conv3_wino4k_body<false>(a, xcd_chunked(blockIdx.x - nmini_pad, full), 0, lds);
 }
 
 __global__ __launch_bounds__(256) void conv3_wino4_kernel(WinoArgs a, int nmini, int nmini_pad, int full) {
@@ -785,6 +967,11 @@ __global__ __launch_bounds__(256) void conv3_wino4_kernel(WinoArgs a, int nmini,
 
 static int g_wino_tail = 1;
 static int g_wino4_k16 = 1;
+int g_wino4_skip5 = 1;          // da_debug_set(key 11): 0 = six products for every quad (the form the tests compare with)
+
+// skip5 (conv3_wino4k_skip5_body, wino4_wgrad_body<true>): a row of exactly two quads whose second quad lacks its fourth output,
+// L = 5, 6, 7.  Every tile / split / K-step base is even, so an even quad index is a row's first quad, an odd one its second.
+static bool wino4_skip5_applies(int L, int QL) { return g_wino4_skip5 && QL == 2 && (L & 3) != 0; }
 
 // ---------------------------------------------------------------------------------------------
 // Weight gradient of the same convolution, Winograd form.  With dm = A dy = (dy0, dy0 + dy1, dy0 - dy1, -dy1) per
@@ -925,6 +1112,7 @@ struct WinoWgradTable {
   WinoWgradArgs d[24];
   int first_block[25];
   int n;
+  int skip5;        // wino4_wgrad_multi_kernel: jobs with two quads a row and L % 4 != 0 skip the dead half of point 5
 };
 static_assert(sizeof(WinoWgradTable) + sizeof(WgradPreTable) <= 4096, "kernel arguments: 4 KB");
 
@@ -994,6 +1182,7 @@ int wino_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hi
   auto flush = [&]() -> int {
     if (!cnt) return DA_OK;
     t.n = cnt;
+    t.skip5 = 0;
     t.first_block[cnt] = blocks;
     WgradPreTable pre = wgrad_chain_take(chain);
     hipLaunchKernelGGL(wino_wgrad_multi_kernel, dim3(wgrad_pre_grid(pre, blocks)), dim3(256), 0, s, t, pre);
@@ -1031,6 +1220,9 @@ int wino_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hi
 // X in four ([quad - 1 ..] for phase 3, [.. quad + 1] for phase 0: d0 = X3[q-1], d1..d4 = X0..X3[q], d5 = X0[q+1]); sequence
 // edges (d0 of a row's first quad, d5 of its last) from two 16-bit masks per K step, positions past L are zeros of the
 // loader.  Slabs in the direct kernel's layout, shared reduction.
+// skip5 (L = 5, 6, 7: two quads a row, dm5 = dy3 = 0 in every second quad): the M5 MFMA, whose two K slices are a first and a
+// second quad, runs on even kk only, with the first quads 2kk and 2kk + 2 as its slices: 11 MFMAs per two kk instead of 12,
+// for four more LDS reads.  The accumulator sees the same first quads in the same order; the steps left out added 0 * D5.
 // ---------------------------------------------------------------------------------------------
 #ifndef WW4_KQ
 #define WW4_KQ 16         // quads per K step (16 or 32)
@@ -1041,8 +1233,12 @@ int wino_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, hi
 #ifndef WW4_UNROLL
 #define WW4_UNROLL 4      // (8: 39 spilled registers at 3 waves/SIMD, 346 us for the three 512-channel jobs at B = 64 against 280)
 #endif
+#ifndef WW4_SKIP5_UNROLL
+#define WW4_SKIP5_UNROLL 2   // the skip5 K loop (4: 23 spilled registers, 36 bytes of scratch; 2: 6 and 16, the six-product form's 16)
+#endif
 #define WW4_LDS_FLOATS ((4 * WW4_KQ + 4 * WW4_KQ + 2) * 64)
 
+template <bool SKIP5>
 __device__ __forceinline__ void wino4_wgrad_body(const WinoWgradArgs& a, const int block_id, const int nblocks, float* lds) {
   constexpr int KQ = WW4_KQ, NRB = KQ / 16;
   float* Y = lds;                         // [4 phases][KQ][64]
@@ -1119,9 +1315,14 @@ __device__ __forceinline__ void wino4_wgrad_body(const WinoWgradArgs& a, const i
     const uint32_t fmask = (uint32_t)__ballot(Qm < a.MP && im == 0);          // (bits >= KQ repeat the low ones: never read)
     const uint32_t lmask = (uint32_t)__ballot(Qm < a.MP && im == QL - 1);
     __syncthreads();
-#pragma unroll WW4_UNROLL
-    for (int kk = 0; kk < KQ / 2; ++kk) {
-      if (kk == KQ / 4) {
+    constexpr int UNR = SKIP5 ? WW4_SKIP5_UNROLL : WW4_UNROLL, UNR2 = UNR / 2;
+    static_assert(UNR % 2 == 0 && KQ % 8 == 0, "the K loop is unrolled in whole pairs of kk");
+#pragma unroll UNR2
+    for (int k2 = 0; k2 < KQ / 4; ++k2)          // kk = 2 k2 + u: the parity of kk is a compile-time constant
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int kk = 2 * k2 + u;
+      if (u == 0 && k2 == KQ / 8) {
         __builtin_amdgcn_sched_barrier(0);
         if (k0 + KQ < k_end) gload(k0 + KQ);
         __builtin_amdgcn_sched_barrier(0);
@@ -1141,7 +1342,17 @@ __device__ __forceinline__ void wino4_wgrad_body(const WinoWgradArgs& a, const i
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(ya - yb, e1 - e2, acc[2], 0, 0, 0);
       acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(yc + yd, fmaf(2.f, f2, f1), acc[3], 0, 0, 0);
       acc[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(yc - yd, fmaf(-2.f, f2, f1), acc[4], 0, 0, 0);
-      acc[5] = __builtin_amdgcn_mfma_f32_32x32x2f32(y3, fmaf(4.f, d1, fmaf(-5.f, d3, d5)), acc[5], 0, 0, 0);
+      if (!SKIP5) {
+        acc[5] = __builtin_amdgcn_mfma_f32_32x32x2f32(y3, fmaf(4.f, d1, fmaf(-5.f, d3, d5)), acc[5], 0, 0, 0);
+      } else if (u == 0) {
+        // dm5 = dy3 is zero in every second quad: one MFMA per two kk, its K slices the first quads 2kk and 2kk + 2
+        // (the same quads in the same order as the six-product chain, whose other steps add 0 * D5)
+        const int p5 = 2 * kk + 2 * fh;
+        const int y5o = p5 * 64 + wm * 32 + frow, x5o = p5 * 64 + wn * 32 + frow;
+        const float g3 = Y[3 * KQ * 64 + y5o];
+        const float g1 = X0[x5o], g2 = X2[x5o], g5 = X0[x5o + 64];       // (a first quad is never its row's last: no mask)
+        acc[5] = __builtin_amdgcn_mfma_f32_32x32x2f32(g3, fmaf(4.f, g1, fmaf(-5.f, g2, g5)), acc[5], 0, 0, 0);
+      }
     }
   }
 
@@ -1165,7 +1376,9 @@ __global__ __launch_bounds__(256, WW4_MIN_WAVES) void wino4_wgrad_multi_kernel(W
   if (b < 0 || b >= t.first_block[t.n]) return;
   int i = 0;
   while (i + 1 < t.n && b >= t.first_block[i + 1]) ++i;      // wave-uniform
-  wino4_wgrad_body(t.d[i], b - t.first_block[i], t.first_block[i + 1] - t.first_block[i], lds);
+  const bool skip5 = t.skip5 && t.d[i].PL == 2 && (t.d[i].L & 3) != 0;                 // wave-uniform, outside the K loop
+  if (skip5) wino4_wgrad_body<true>(t.d[i], b - t.first_block[i], t.first_block[i + 1] - t.first_block[i], lds);
+  else wino4_wgrad_body<false>(t.d[i], b - t.first_block[i], t.first_block[i + 1] - t.first_block[i], lds);
 }
 
 #ifndef WW4_QCHUNK
@@ -1191,6 +1404,7 @@ int wino4_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, h
     t.n = cnt;
     t.first_block[cnt] = blocks;
     WgradPreTable pre = wgrad_chain_take(chain);
+    t.skip5 = g_wino4_skip5 != 0;
     hipLaunchKernelGGL(wino4_wgrad_multi_kernel, dim3(wgrad_pre_grid(pre, blocks)), dim3(256), 0, s, t, pre);
     DA_CHECK_LAUNCH();
     cnt = 0;
@@ -1204,6 +1418,8 @@ int wino4_wgrad_launch(const da_wgrad_job* jobs, const WgradPlan* plan, int n, h
     a.dy = j.dy; a.x = j.x; a.slab = j.workspace;
     a.L = j.Lm; a.PL = (j.Lm + 3) / 4; a.MP = j.rows * a.PL;
     a.lddy = j.lddy; a.N = j.N; a.ldx = j.ldx; a.C = j.C; a.pchunk = plan[i].kchunk;
+    static_assert(WW4_KQ % 8 == 0, "skip5: K steps start at even quads");
+    if (a.pchunk % WW4_KQ) return DA_EINVAL;            // split bases are multiples of the K step (skip5: even)
     a.divPL = make_fastdiv((uint32_t)a.PL);
     t.first_block[cnt] = blocks;
     blocks += (j.N / 64) * (j.C / 64) * plan[i].splits;
@@ -1301,8 +1517,11 @@ static int conv3_winograd_impl(const float* x, const float* u, float* y, int row
     full = tiles - R;
   }
   const int nmini_pad = (nmini + 7) / 8 * 8;
-  if (outs == 4 && g_wino4_k16)
-    hipLaunchKernelGGL(conv3_wino4k_kernel, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
+  static_assert(W4K_TILE_QUADS == 64, "skip5: a wave owns 16 rows = 32 quads; full and half tiles start at even quads");
+  if (outs == 4 && g_wino4_k16 && wino4_skip5_applies(L, a.PL))
+    hipLaunchKernelGGL(conv3_wino4k_kernel<true>, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
+  else if (outs == 4 && g_wino4_k16)
+    hipLaunchKernelGGL(conv3_wino4k_kernel<false>, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
   else if (outs == 4)
     hipLaunchKernelGGL(conv3_wino4_kernel, dim3(nmini_pad + full), dim3(256), 0, stream, a, nmini, nmini_pad, full);
   else if (bn && stat_part) hipLaunchKernelGGL(conv3_wino_bn_kernel<true>, dim3(full), dim3(256), 0, stream, a, full);

@@ -66,7 +66,8 @@ int da_conv_wgrad(const float* dy, const float* x, float* dw, float* workspace, 
                   const int* src_off, int accumulate, da_stream_t stream);
 
 /* comparison forms for tests: key 3 = 0: no half-tile tail round in the 64x64 conv launches; key 7 = 0: the dense-block
-   weight gradients as one launch per tile shape.  Any other key returns DA_EINVAL. */
+   weight gradients as one launch per tile shape; key 11 = 0: the F(4,3) conv / weight-gradient kernels compute the sixth
+   product for every quad, also where L = 5, 6, 7 leaves it unused.  Any other key returns DA_EINVAL. */
 int da_debug_set(int key, int value);
 
 /* n <= 4 independent da_conv_gemm problems (jobs: HOST array, N % 64 == 0, disjoint outputs) in ONE launch: the
