@@ -251,9 +251,9 @@ def _own_module_classes():
     deepards_amd.models.* and torch.nn's own module classes (containers, Conv1d / BatchNorm1d / Linear / LSTM ... that
     the models hold as parameter containers)."""
     import inspect
-    from .models import densenet, resnet, senet, torch_cnn_linear_network, transformer
+    from .models import densenet, resnet, senet, torch_cnn_linear_network, transformer, vgg
     allow = []
-    for mod in (resnet, densenet, senet, torch_cnn_linear_network, transformer):
+    for mod in (resnet, densenet, senet, vgg, torch_cnn_linear_network, transformer):
         allow += [c for c in vars(mod).values()
                   if inspect.isclass(c) and issubclass(c, torch.nn.Module) and c.__module__ == mod.__name__]
     allow += [c for c in vars(torch.nn).values() if inspect.isclass(c) and issubclass(c, torch.nn.Module)]
@@ -293,7 +293,8 @@ def load_base_network(path, base_networks, build_args=None):
     """``--load-base-network`` (train_ards_detector.py:383-388): the ``breath_block`` of a saved model.  Foreign
     files: a fresh base network of the architecture the file names (``breath_block.network_name``) receives the
     ``breath_block.*`` weights -- a ResNet / DenseNet built with the configured keywords, an SE-ResNet (reference classes
-    ``deepards.models.senet.{SENet, SEBasicBlock, SEModule}``) with none, as ``get_base_network`` builds them."""
+    ``deepards.models.senet.{SENet, SEBasicBlock, SEModule}``) or a VGG net (``deepards.models.vgg.VGG``, which carries no
+    ``network_name``: the configured ``base_network`` names it) with none, as ``get_base_network`` builds them."""
     kind = checkpoint_kind(path)
     if kind == 'own':
         saved = load_own_module(path)
@@ -313,7 +314,7 @@ def load_base_network(path, base_networks, build_args=None):
     name = name or build_args.get('base_network')
     if name not in base_networks:
         raise ValueError('base network %r of %s is not built by this package' % (name, path))
-    kwargs = build_args.get('resnet_kwargs', {}) if name.startswith('resnet') else {} if name.startswith('se_') else \
+    kwargs = build_args.get('resnet_kwargs', {}) if name.startswith('resnet') else {} if name.startswith(('se_', 'vgg')) else \
         build_args.get('densenet_kwargs', {})
     net = base_networks[name](**kwargs)
     net.load_state_dict(bb, strict=True)

@@ -48,9 +48,12 @@ def training_step(model=None):
             precise = {id(c) for b in model.modules() if getattr(b, 'precise_convs', False) for c in b.children()}
             ms = [m for m in model.modules()
                   if isinstance(m, torch.nn.Conv1d) and m.kernel_size[0] <= 3 and m.in_channels % 32 == 0
-                  and m.weight.is_cuda and m.bias is None]       # (with a bias: an SEModule's fc1 / fc2 -- no conv kernel reads them)
+                  and m.weight.is_cuda and (m.bias is None or m.kernel_size[0] == 3)]
+            # (k1 with a bias: an SEModule's fc1 / fc2 -- no conv kernel reads them; k3 with a bias: the VGG stages, whose
+            # kernels never read the bias either, VGGStageFunction)
             ws = [m.weight for m in ms]
-            forms = [H.step_pack_form(*m.weight.shape, m.stride[0], m.padding[0], id(m) in precise) for m in ms]
+            forms = [H.step_pack_form(*m.weight.shape, m.stride[0], m.padding[0], id(m) in precise or getattr(m, 'precise_conv', False))
+                     for m in ms]                      # (``precise_conv`` on the conv itself: the VGG stages, models/vgg.py)
             for w, c, e in zip(ws, forms, H.repack_multi(ws, forms)):
                 _STEP['pack'][(w.data_ptr(), int(c))] = e
         yield
@@ -722,6 +725,85 @@ class SEBasicBlockFunction(Function):
             dwd = dgd = dbd = None
             dx = _conv_dgrad(dy1, w1, stride, 1, lin, out=g, accumulate=True, precise=True)       # identity grad + conv path
         return dx, dw1, dg1, db1, dw2, dg2, db2, df1w, df1b, df2w, df2b, dwd, dgd, dbd, None, None, None, None, None
+
+
+class VGGStageFunction(Function):
+    """One stage of a VGG backbone: Conv1d(k3, p1, WITH bias) -> BatchNorm1d -> ReLU [-> MaxPool1d(2, 2)].
+    reference models/vgg.py:37-50 (make_layers).
+
+    The bias is never added to the stored conv output y: BN(conv + b) and BN(conv) are the same function.  What
+    remains of it: the running mean is that of conv + b (H.bn_mean_bias in front of the running update), and its gradient is
+    exactly 0 -- returned as zeros, left alone in a trainer's zero-filled bucket, written as 0 by the bn_mean_bias launch in a
+    step captured without the zero-fill (_OV).  With the pool the tail is H.bn_relu_maxpool2_fwd / _bwd: relu(bn(y)) and its
+    gradient are never stored; without, the plain BatchNorm forward / backward with the ReLU bit mask.  ``first``: the
+    one-channel stage on the raw rows x (rows, L) (the (1, 3, 1) stem conv kernels).  fp32 conv arithmetic and float storage only."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, gamma, beta, R, st, pool, first, precise=False):
+        if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
+            raise NotImplementedError('the VGG stages run with fp32 conv arithmetic and float activation storage only')
+        y = H.stem_conv_fwd(x, w, stride=1) if first else _conv_fwd(x, w, 1, 1, precise=precise)
+        out_keep = mask = None
+        if pool:
+            mean, invstd = H.vgg_stats(y, R, st.eps)
+            out = H.bn_relu_maxpool2_fwd(y, R, mean, invstd, gamma, beta)
+        else:
+            out, mean, invstd, mask = H.bn_fwd(y, R, gamma, beta, relu=True, eps=st.eps, want_mask=True)
+            _tap(out)
+            if mask is None:                            # (two-stage geometry: the backward reads the sign of ``out``)
+                out_keep = out
+        tw, tb, tg, tbe = _tgt(w, bias, gamma, beta)
+        zero_bias = tb is not None and _OV['on']        # no zero-fill in this step: the bias gradient's 0 is written here
+        if st.running_mean is not None or zero_bias:
+            mean_b = H.bn_mean_bias(mean, bias, dbias=tb if zero_bias else None)
+            if st.running_mean is not None:
+                s_ = _Stats()
+                s_.mean, s_.invstd = mean_b, invstd
+                _running(y, R, s_, st)
+        ctx.R, ctx.pool, ctx.first, ctx.precise = R, bool(pool), bool(first), bool(precise)
+        ctx.has_mask, ctx.has_out = mask is not None, out_keep is not None
+        ctx.gt = (tw, tb, tg, tbe)
+        saved = [x, w, bias, gamma, beta, y, mean, invstd]
+        saved += [mask] if mask is not None else [out_keep] if out_keep is not None else []
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        s = ctx.saved_tensors
+        x, w, bias, gamma, beta, y, mean, invstd = s[:8]
+        tw, tb, tg, tbe = ctx.gt
+        R = ctx.R
+        dout = dout.contiguous()
+        if ctx.pool:
+            dy, ds = H.bn_relu_maxpool2_bwd(dout, y, R, mean, invstd, gamma, beta)
+            dg, dbe = _bn_pgrad(ds, gamma, beta, tg, tbe)
+        elif ctx.has_mask:
+            dy, dg, dbe = _bn_bwd(dout, y, R, mean, invstd, gamma, beta, 2, tg, tbe, mask=s[8])
+        else:
+            dy, dg, dbe = _bn_bwd(dout, y, R, mean, invstd, gamma, beta, 2, tg, tbe, out=s[8])
+        dbias = None if tb is not None else torch.zeros_like(bias)
+        if ctx.first:
+            direct = tw is not None
+            dw = H.stem_conv_wgrad(dy, x, out=tw, accumulate=direct and _acc(), k=3, stride=1)
+            return None, None if direct else dw, dbias, dg, dbe, None, None, None, None, None
+        dw = _wgrad(dy, x, 3, 1, 1, tw, precise=ctx.precise)
+        dx = _conv_dgrad(dy, w, 1, 1, x.shape[1], precise=ctx.precise)
+        return dx, dw, dbias, dg, dbe, None, None, None, None, None
+
+
+class AdaptiveAvgPoolFlatFunction(Function):
+    """AdaptiveAvgPool1d(lout) + ``view(N, -1)`` of a channels-last map (reference models/vgg.py:15,22-23):
+    (rows, L, C) -> (rows, C * lout), feature c * lout + i."""
+
+    @staticmethod
+    def forward(ctx, x, lout):
+        ctx.lin, ctx.lout = x.shape[1], lout
+        return H.adaptive_avgpool_flat_fwd(x.contiguous(), lout)
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        return H.adaptive_avgpool_flat_bwd(dfeat.contiguous(), ctx.lin, ctx.lout), None
 
 
 _STEM_TAIL = True         # inside a training step the stem's last weight-gradient fold rides on the tail launch

@@ -1779,3 +1779,5 @@ from .transformer_ops import TFM_PARAMS, tfm_check_shape, tfm_block_form, tfm_bl
 from .filter_ops import gather_normalize_filter, gather_normalize_chain, resample_operand   # noqa: E402,F401
 from .se_ops import (pool_out_len, se_stats, se_gate_fwd, se_scale_fwd, se_bwd_reduce, se_gate_bwd,   # noqa: E402,F401
                      se_bwd_scale)
+from .vgg_ops import (vgg_stats, bn_relu_maxpool2_fwd, bn_relu_maxpool2_bwd, bn_mean_bias,   # noqa: E402,F401
+                      adaptive_avgpool_flat_fwd, adaptive_avgpool_flat_bwd)

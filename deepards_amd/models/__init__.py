@@ -6,10 +6,13 @@ from .torch_cnn_linear_network import (CNNLinearNetwork, CNNLinearToMean, CNNLin
                                        CNNSingleBreathLinearNetwork, CNNDoubleLinearNetwork, CNNLSTMNetwork,
                                        BreathBlockLinear)
 from .senet import SENet, SEBasicBlock, SEModule, se_resnet18     # noqa: F401
+from .vgg import VGG, make_layers, vgg11_bn, vgg13_bn     # noqa: F401
 from .transformer import MultiHeadAttention, Block, Transformer, CNNTransformerNetwork           # noqa: F401
 
 # the 1-D BasicBlock / growth-32 entries of the reference's base_networks (train_ards_detector.py:45-69); resnet34 is in
-# its models/resnet.py (:178) though not in that dict; se_resnet18 is the SE net its experiment scripts sweep; densenet161
-# (growth 48), the Bottleneck nets, the grouped / 3x3-stem SE nets (senet18, senet154) and the VGG nets are not built
+# its models/resnet.py (:178) though not in that dict; se_resnet18 is the SE net its experiment scripts sweep; vgg11 / vgg13
+# are its vgg11_bn / vgg13_bn (:67-68); densenet161 (growth 48), the Bottleneck nets, the grouped / 3x3-stem SE nets (senet18,
+# senet154), the VGG nets without BatchNorm and vgg16 / vgg19 are not built
 base_networks = {'resnet18': resnet18, 'resnet34': resnet34, 'densenet18': densenet18, 'densenet121': densenet121,
-                 'densenet169': densenet169, 'densenet201': densenet201, 'se_resnet18': se_resnet18}
+                 'densenet169': densenet169, 'densenet201': densenet201, 'se_resnet18': se_resnet18,
+                 'vgg11': vgg11_bn, 'vgg13': vgg13_bn}

@@ -277,8 +277,8 @@ class HotPathTrainer(object):
         self._plain_bce = loss == 'bce' and loss_calc == 'all_breaths' and not carry_state
         self._carry = self._flag = None    # (2, 2H): row 0 zeros, row 1 the carried [hx | cx]; the step's row index
         bb_name = str(getattr(getattr(model, 'breath_block', None), 'network_name', ''))
-        if self.eval_test and bb_name.startswith(('resnet', 'se_resnet')):     # (BatchNorm with running statistics)
-            raise NotImplementedError('eval_test on a ResNet breath block means inference on running statistics, which this '
+        if self.eval_test and bb_name.startswith(('resnet', 'se_resnet', 'vgg')):     # (BatchNorm with running statistics)
+            raise NotImplementedError('eval_test on a ResNet / VGG breath block means inference on running statistics, which this '
                                       'package does not have')
         self.model = model
         self.optimizer = optimizer

@@ -570,6 +570,30 @@ int da_se_gate_bwd(const float* dsum, const float* s, const float* hid, const fl
                    int Cr, da_stream_t stream);
 int da_se_bwd_scale(const float* g, const float* s, const float* dpool, float* dz, int rows, int L, int C, da_stream_t stream);
 
+/* ---- the pooled stages and the feature layout of the VGG backbones (vgg.py:37-50 make_layers, :15,20-24) --------------------
+ *     out[row][j][c] = max(relu(z[2j]), relu(z[2j + 1])),  z = bn(y) = fmaf(y, gamma invstd, beta - mean gamma invstd),  j < Lin / 2
+ * float activations, y [rows][Lin][ldy] the stored conv output (WITHOUT the conv bias: BN(conv + b) == BN(conv)), BatchNorm
+ * windows of R rows, mean / invstd (rows / R, C).  relu(z) and its gradient dz are never stored.  MaxPool1d(2, 2) floors: the
+ * last position of an odd row belongs to no pair -- dz = 0 there, but dy is not (n = R Lin is the full window).  The pool gives
+ * a pair's gradient to its first maximum.  Shapes: C a multiple of 32, Lin >= 2, R dividing rows, ldy >= C a multiple of 4,
+ * rows Lin ldy < 2^32; anything else -> DA_EINVAL.  float storage only.  Sums in an order fixed by the shape (no atomics).
+ *   da_bn_relu_maxpool2_fwd   one pass
+ *   da_bn_relu_maxpool2_bwd   dout [rows][Lin / 2][C] -> dy [rows][Lin][C], ds [2][W][C] (sum dz, sum dz xhat per window, for
+ *                             da_bn_param_grad_multi); workspace: da_bn_relu_maxpool2_bwd_workspace() bytes
+ *   da_bn_mean_bias           mean_b[w][c] = mean[w][c] + bias[c]: the batch mean of conv + b, which da_bn_running_multi takes so
+ *                             that running_mean is the reference's; dbias (or NULL): C floats set to 0, the conv bias's gradient
+ *   da_adaptive_avgpool_flat_fwd / _bwd   AdaptiveAvgPool1d(Lout) + view(N, -1): feat[row][c Lout + i] = mean of
+ *                             x[row][floor(i Lin / Lout) : ceil((i + 1) Lin / Lout)][c]; any Lin, Lout >= 1 (Lin < Lout repeats) */
+int da_bn_relu_maxpool2_fwd(const float* y, int ldy, float* out, int rows, int R, int Lin, int C, const float* mean,
+                            const float* invstd, const float* gamma, const float* beta, da_stream_t stream);
+size_t da_bn_relu_maxpool2_bwd_workspace(int rows, int R, int Lin, int C);
+int da_bn_relu_maxpool2_bwd(const float* dout, const float* y, int ldy, float* dy, float* ds, float* workspace, int rows, int R,
+                            int Lin, int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                            da_stream_t stream);
+int da_bn_mean_bias(const float* mean, const float* bias, float* mean_b, int W, int C, float* dbias, da_stream_t stream);
+int da_adaptive_avgpool_flat_fwd(const float* x, float* feat, int rows, int Lin, int Lout, int C, da_stream_t stream);
+int da_adaptive_avgpool_flat_bwd(const float* dfeat, float* dx, int rows, int Lin, int Lout, int C, da_stream_t stream);
+
 int da_gather_rows(const float* src, const int64_t* idx, float* out, int B, int width, da_stream_t stream);
 
 /* ---- test epoch on the device: window predictions + per-patient vote table --------------------------------
