@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip.so')   # (override: A/B builds, scripts/)
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
-           'filters.hip', 'se.hip', 'vgg.hip']
+           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -186,6 +186,15 @@ SIGNATURES = {
     'da_se_gate_bwd_workspace': (_Z, [_I] * 3),
     'da_se_gate_bwd': (_I, [_P] * 11 + [_I, _P, _I, _I, _I, _P]),
     'da_se_bwd_scale': (_I, [_P] * 4 + [_I] * 3 + [_P]),
+    'da_se_wide_shape_ok': (_I, [_I, _I]),
+    'da_se_wide_stats': (_I, [_P] + [_I] * 4 + [_F] + [_P] * 5),
+    'da_se_wide_gate_fwd': (_I, [_P] + [_I] * 5 + [_P] * 12),
+    'da_se_wide_scale_fwd': (_I, [_P] * 4 + [_I] * 4 + [_P] * 6),
+    'da_se_wide_bwd_reduce': (_I, [_P] * 5 + [_I] * 4 + [_P] * 5),
+    'da_se_wide_chunk_rows': (_I, []),
+    'da_se_wide_gate_bwd_workspace': (_Z, [_I] * 3),
+    'da_se_wide_gate_bwd': (_I, [_P] * 11 + [_I, _P, _I, _I, _I, _P]),
+    'da_se_wide_bwd_scale': (_I, [_P] * 4 + [_I] * 3 + [_P]),
     'da_bn_relu_maxpool2_fwd': (_I, [_P, _I, _P] + [_I] * 4 + [_P] * 5),
     'da_bn_relu_maxpool2_bwd_workspace': (_Z, [_I] * 4),
     'da_bn_relu_maxpool2_bwd': (_I, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P] * 5),
@@ -212,7 +221,7 @@ def header_symbols():
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 every csrc/*.hip into deepards_amd/libdeepards_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, 'common.h')]
+    deps = srcs + [os.path.join(CSRC, h) for h in ('common.h', 'se_tail.h')]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

@@ -15,6 +15,7 @@
 // Every sum runs in an order fixed by the shape alone (thread-private chains, LDS folds in slot order, partials folded in
 // chunk order): no atomics, the same bits every call.
 #include "common.h"
+#include "se_tail.h"      // SeBn4, the elementwise scale kernels and the partials' fold: shared with se_wide.hip
 
 #define SE_TR 4                       // rows per workgroup of the gate kernels: W1 / W2 are read once for all of them (8 rows a
                                       // workgroup measured slower at every stage but the last: too few workgroups at B = 64)
@@ -114,61 +115,6 @@ __global__ __launch_bounds__(256) void se_gate_fwd_kernel(const float* __restric
 #pragma unroll
     for (int r = 0; r < SE_TR; ++r)
       if (r < nr) s[(size_t)(row0 + r) * C + c] = 1.0f / (1.0f + expf(-(acc[r] + bias)));
-  }
-}
-
-// the scale / shift of 4 channels of window w
-struct SeBn4 {
-  f32x4 sc, sh;
-  __device__ __forceinline__ void load(const float* __restrict__ mean, const float* __restrict__ invstd,
-                                       const float* __restrict__ gamma, const float* __restrict__ beta, size_t w, int C, int c0) {
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + w * C + c0), is = *reinterpret_cast<const f32x4*>(invstd + w * C + c0);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0), be = *reinterpret_cast<const f32x4*>(beta + c0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a, b;
-      bn_scale_shift(mu[e], is[e], ga[e], be[e], a, b);
-      sc[e] = a;
-      sh[e] = b;
-    }
-  }
-  __device__ __forceinline__ f32x4 z(const f32x4& y) const {
-    f32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = fmaf(y[e], sc[e], sh[e]);
-    return r;
-  }
-};
-
-// thread = 8 channels of one position: out and one byte of ReLU decisions (bit e = channel c0 + e; byte index = element / 8)
-__global__ __launch_bounds__(256) void se_scale_fwd_kernel(const float* __restrict__ y2, const float* __restrict__ res,
-                                                           float* __restrict__ out, unsigned char* __restrict__ mask, size_t npos,
-                                                           int L, int Wn, int C, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ s) {
-  const int no = C >> 3;
-  const size_t total = npos * no;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int o8 = (int)(idx % no);
-    const size_t pos = idx / no, row = pos / L, w = pos / Wn;
-    unsigned bits = 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c0 = o8 * 8 + h * 4;
-      SeBn4 bn;
-      bn.load(mean, invstd, gamma, beta, w, C, c0);
-      const f32x4 z = bn.z(*reinterpret_cast<const f32x4*>(y2 + pos * C + c0));
-      const f32x4 sv = *reinterpret_cast<const f32x4*>(s + row * C + c0);
-      const f32x4 rv = *reinterpret_cast<const f32x4*>(res + pos * C + c0);
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = fmaxf(fmaf(z[e], sv[e], rv[e]), 0.f);
-        bits |= (o[e] > 0.f ? 1u : 0u) << (h * 4 + e);
-      }
-      *reinterpret_cast<f32x4*>(out + pos * C + c0) = o;
-    }
-    mask[idx] = (unsigned char)bits;
   }
 }
 
@@ -312,51 +258,11 @@ __global__ __launch_bounds__(256) void se_pgrad_partial_kernel(const float* __re
   *reinterpret_cast<f32x4*>(part + (size_t)blockIdx.y * P + i) = acc;
 }
 
-// the chunks folded in chunk order into the four destinations
-__global__ __launch_bounds__(256) void se_pgrad_fold_kernel(const float* __restrict__ part, int nchunks, int C, int Cr,
-                                                            float* __restrict__ dw2, float* __restrict__ db2,
-                                                            float* __restrict__ dw1, float* __restrict__ db1, int accumulate) {
-  const int P = 2 * C * Cr + C + Cr;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  float t = 0.f;
-  for (int k = 0; k < nchunks; ++k) t += part[(size_t)k * P + i];
-  float* o;
-  if (i < C * Cr) o = dw2 + i;
-  else if (i < C * Cr + C) o = db2 + (i - C * Cr);
-  else if (i < 2 * C * Cr + C) o = dw1 + (i - C * Cr - C);
-  else o = db1 + (i - 2 * C * Cr - C);
-  *o = accumulate ? *o + t : t;
-}
-
-__global__ __launch_bounds__(256) void se_bwd_scale_kernel(const float* __restrict__ g, const float* __restrict__ s,
-                                                           const float* __restrict__ dpool, float* __restrict__ dz, size_t npos,
-                                                           int L, int C) {
-  const int nq = C >> 2;
-  const size_t total = npos * nq;
-  const float fl = (float)L;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int c0 = (int)(idx % nq) * 4;
-    const size_t pos = idx / nq, row = pos / L;
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + pos * C + c0);
-    const f32x4 sv = *reinterpret_cast<const f32x4*>(s + row * C + c0);
-    const f32x4 dv = *reinterpret_cast<const f32x4*>(dpool + row * C + c0);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = fmaf(gv[e], sv[e], dv[e] / fl);
-    *reinterpret_cast<f32x4*>(dz + pos * C + c0) = o;
-  }
-}
-
 // shapes the kernels tile: C a multiple of 64 up to 512 (the four stages) whose quads divide a block, Cr a multiple of 16 that
 // divides 256
 static bool se_shape_ok(int rows, int L, int C, int Cr) {
   return rows >= 0 && L >= 1 && C >= 64 && C <= 512 && C % 64 == 0 && 256 % (C / 4) == 0 && Cr >= 16 && Cr % 16 == 0 &&
          Cr <= 256 && 256 % Cr == 0 && (C / 4) % (256 / Cr) == 0 && (size_t)rows * L < 0x7fffffffull;
-}
-static inline unsigned se_grid(size_t total) {
-  size_t g = (total + 255) / 256;
-  return (unsigned)(g > 16384 ? 16384 : g);
 }
 // rows per chunk of the parameter-gradient partials: C / 2, so that a call's partials hold about rows x C floats
 static inline int se_chunk_rows(int C) { return C / 2; }

@@ -727,6 +727,110 @@ class SEBasicBlockFunction(Function):
         return dx, dw1, dg1, db1, dw2, dg2, db2, df1w, df1b, df2w, df2b, dwd, dgd, dbd, None, None, None, None, None
 
 
+def _se_tail_fwd(y, R, st, gamma, beta, f1w, f1b, f2w, f2b, res):
+    """[statistics -> gate -> scale + residual + ReLU] behind a block's last conv on the kernel family H.se_gate_family names
+    for the gate's (C, Cr).  Wide: one kernel over the map gives the statistics and the row sums, the gate never reads the map.
+    -> out, mask, (mean, invstd, pool, hid, gate), family."""
+    fam = H.se_gate_family(y.shape[2], f1w.shape[0])
+    s = _Stats()
+    if fam == H.SE_WIDE:
+        s.mean, s.invstd, rowsum = H.se_wide_stats(y, R, st.eps)
+        _running(y, R, s, st)
+        pool, hid, gate = H.se_wide_gate_fwd(rowsum, R, y.shape[1], s.mean, s.invstd, gamma, beta, f1w, f1b, f2w, f2b)
+        out, mask = H.se_wide_scale_fwd(y, R, s.mean, s.invstd, gamma, beta, gate, res)
+    else:
+        s.mean, s.invstd = H.se_stats(y, R, st.eps)
+        _running(y, R, s, st)
+        pool, hid, gate = H.se_gate_fwd(y, R, s.mean, s.invstd, gamma, beta, f1w, f1b, f2w, f2b)
+        out, mask = H.se_scale_fwd(y, R, s.mean, s.invstd, gamma, beta, gate, res)
+    return out, mask, (s.mean, s.invstd, pool, hid, gate), fam
+
+
+def _se_tail_bwd(fam, dout, mask, y, R, mean, invstd, gamma, beta, pool, hid, gate, f1w, f2w, se_t):
+    """The tail's backward on the family the forward ran on: -> g (the residual's gradient), dz (what the BatchNorm backward
+    with mask_mode 0 takes), the four gate gradients (None each where ``se_t``, a trainer's destinations, took them)."""
+    wide = fam == H.SE_WIDE
+    g, dsum = (H.se_wide_bwd_reduce if wide else H.se_bwd_reduce)(dout, mask, y, R, mean, invstd, gamma, beta)
+    direct = all(t is not None for t in se_t)              # a trainer's destinations: written (or accumulated) in place
+    dpool, se_g = (H.se_wide_gate_bwd if wide else H.se_gate_bwd)(dsum, gate, hid, pool, f1w, f2w, grads=se_t if direct else None,
+                                                                 accumulate=direct and _acc())
+    dz = (H.se_wide_bwd_scale if wide else H.se_bwd_scale)(g, gate, dpool)
+    return g, dz, (None,) * 4 if direct else se_g
+
+
+class SEBottleneckFunction(Function):
+    """conv1(k1, s) -> BN -> ReLU -> conv3 -> BN -> ReLU -> conv1 -> BN -> * gate (+ identity | BN(conv1x1(s))) -> ReLU with
+    gate = sigmoid(fc2(relu(fc1(mean_L(bn3(..)))))) per row and channel.
+    reference models/senet.py:75-95 (Bottleneck.forward), :122-144 (SEResNetBottleneck: the stride sits on conv1), :27-34
+    (SEModule.forward), :295-300 (downsample; layer1.0 has one with stride 1).
+
+    The k1 convs run on the direct kernels, the two that read a block entry's input in one launch where H.conv_fwd_multi takes
+    them; conv2 (always k3 s1 p1) keeps off F(4,3) as in SEBasicBlockFunction (``precise``).  The tail is _se_tail_fwd /
+    _se_tail_bwd: bn3's output z is never stored, and on the wide family the map y3 is read twice forward (statistics with
+    row sums, scale) and the narrow activations h1, h2 are the only stored post-ReLU maps.  fp32 conv arithmetic and float
+    storage only."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f1b, f2w, f2b, wd, gd, bd, stride, R, st1, st2, st3, std):
+        if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
+            raise NotImplementedError('the SE bottleneck runs with fp32 conv arithmetic and float activation storage only')
+        if wd is not None:          # conv1 and the downsample conv read the same input: one launch
+            y1, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 0), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
+            sd = _Stats()
+            res = _bn_apply(yd, R, sd, std, gd, bd, False)
+        else:
+            y1 = _conv_fwd(x, w1, stride, 0)
+            res = x
+        s1 = _Stats()
+        h1 = _bn_apply(y1, R, s1, st1, g1, b1, True)
+        _tap(h1)
+        y2 = _conv_fwd(h1, w2, 1, 1, precise=True)
+        s2 = _Stats()
+        h2 = _bn_apply(y2, R, s2, st2, g2, b2, True)
+        _tap(h2)
+        y3 = _conv_fwd(h2, w3, 1, 0)
+        out, mask, tail, ctx.family = _se_tail_fwd(y3, R, st3, g3, b3, f1w, f1b, f2w, f2b, res)
+        _tap(out)
+        ctx.has_ds = wd is not None
+        ctx.stride, ctx.R, ctx.lin = stride, R, x.shape[1]
+        ctx.gt = _tgt(w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f1b, f2w, f2b, wd, gd, bd)
+        saved = [x, w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f2w, y1, s1.mean, s1.invstd, h1, y2, s2.mean, s2.invstd, h2, y3,
+                 *tail, mask]
+        if ctx.has_ds:
+            saved += [wd, gd, bd, yd, sd.mean, sd.invstd]
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        s = ctx.saved_tensors
+        x, w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f2w, y1, m1, i1, h1, y2, m2, i2, h2, y3, m3, i3, pool, hid, gate, mask = s[:27]
+        tw1, tg1, tb1, tw2, tg2, tb2, tw3, tg3, tb3, tf1w, tf1b, tf2w, tf2b, twd, tgd, tbd = ctx.gt
+        R, stride, lin = ctx.R, ctx.stride, ctx.lin
+        # relu + residual add (g: the residual's gradient), the gate, then bn3 on dz
+        g, dz, (df1w, df1b, df2w, df2b) = _se_tail_bwd(ctx.family, dout.contiguous(), mask, y3, R, m3, i3, g3, b3, pool, hid, gate,
+                                                       f1w, f2w, (tf1w, tf1b, tf2w, tf2b))
+        dy3, dg3, db3 = _bn_bwd(dz, y3, R, m3, i3, g3, b3, 0, tg3, tb3, dx=dz)
+        if ctx.has_ds:        # the downsample BatchNorm's backward right away: g is still cache-resident
+            wd, gd, bd, yd, md, idd = s[27:]
+            dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, tgd, tbd, dx=g)
+        dw3 = _wgrad(dy3, h2, 1, 1, 0, tw3)
+        dh2 = _conv_dgrad(dy3, w3, 1, 0, y2.shape[1])
+        dy2, dg2, db2 = _bn_bwd(dh2, y2, R, m2, i2, g2, b2, 1, tg2, tb2, dx=dh2)
+        dw2 = _wgrad(dy2, h1, 3, 1, 1, tw2, precise=True)
+        dh1 = _conv_dgrad(dy2, w2, 1, 1, y1.shape[1], precise=True)
+        dy1, dg1, db1 = _bn_bwd(dh1, y1, R, m1, i1, g1, b1, 1, tg1, tb1, dx=dh1)
+        dw1 = _wgrad(dy1, x, 1, stride, 0, tw1)
+        if ctx.has_ds:        # both k1 data gradients land on the same (every stride-th) positions: the second launch accumulates
+            dwd = _wgrad(dyd, x, 1, stride, 0, twd)
+            dx = _conv_dgrad(dyd, wd, stride, 0, lin)
+            dx = _conv_dgrad(dy1, w1, stride, 0, lin, out=dx, accumulate=True)
+        else:
+            dwd = dgd = dbd = None
+            dx = _conv_dgrad(dy1, w1, 1, 0, lin, out=g, accumulate=True)                         # identity grad + conv path
+        return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3, df1w, df1b, df2w, df2b, dwd, dgd, dbd) + (None,) * 6
+
+
 class VGGStageFunction(Function):
     """One stage of a VGG backbone: Conv1d(k3, p1, WITH bias) -> BatchNorm1d -> ReLU [-> MaxPool1d(2, 2)].
     reference models/vgg.py:37-50 (make_layers).

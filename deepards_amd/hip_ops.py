@@ -1778,6 +1778,8 @@ from .loss_ops import confidence_loss, vacillating_loss          # noqa: E402,F4
 from .transformer_ops import TFM_PARAMS, tfm_check_shape, tfm_block_form, tfm_block_fwd, tfm_block_bwd, tfm_block_pgrad   # noqa: E402,F401
 from .filter_ops import gather_normalize_filter, gather_normalize_chain, resample_operand   # noqa: E402,F401
 from .se_ops import (pool_out_len, se_stats, se_gate_fwd, se_scale_fwd, se_bwd_reduce, se_gate_bwd,   # noqa: E402,F401
-                     se_bwd_scale)
+                     se_bwd_scale, se_gate_family, se_narrow_ok, se_wide_ok, se_wide_stats, se_wide_gate_fwd, se_wide_scale_fwd,
+                     se_wide_bwd_reduce, se_wide_chunk_rows, se_wide_gate_bwd, se_wide_bwd_scale)
+from .se_ops import NARROW as SE_NARROW, WIDE as SE_WIDE        # noqa: E402,F401
 from .vgg_ops import (vgg_stats, bn_relu_maxpool2_fwd, bn_relu_maxpool2_bwd, bn_mean_bias,   # noqa: E402,F401
                       adaptive_avgpool_flat_fwd, adaptive_avgpool_flat_bwd)

@@ -5,14 +5,18 @@ from .densenet import DenseNet, densenet18, densenet121, densenet169, densenet20
 from .torch_cnn_linear_network import (CNNLinearNetwork, CNNLinearToMean, CNNLinearComprToRF,      # noqa: F401
                                        CNNSingleBreathLinearNetwork, CNNDoubleLinearNetwork, CNNLSTMNetwork,
                                        BreathBlockLinear)
-from .senet import SENet, SEBasicBlock, SEModule, se_resnet18     # noqa: F401
+from .senet import (SENet, SEBasicBlock, SEResNetBottleneck, SEModule, se_resnet18, se_resnet50, se_resnet101,      # noqa: F401
+                    se_resnet152)
 from .vgg import VGG, make_layers, vgg11_bn, vgg13_bn     # noqa: F401
 from .transformer import MultiHeadAttention, Block, Transformer, CNNTransformerNetwork           # noqa: F401
 
 # the 1-D BasicBlock / growth-32 entries of the reference's base_networks (train_ards_detector.py:45-69); resnet34 is in
-# its models/resnet.py (:178) though not in that dict; se_resnet18 is the SE net its experiment scripts sweep; vgg11 / vgg13
-# are its vgg11_bn / vgg13_bn (:67-68); densenet161 (growth 48), the Bottleneck nets, the grouped / 3x3-stem SE nets (senet18,
-# senet154), the VGG nets without BatchNorm and vgg16 / vgg19 are not built
+# its models/resnet.py (:178) though not in that dict; se_resnet18 is the SE net its experiment scripts sweep; se_resnet50 /
+# 101 / 152 are the bottleneck nets of that dict the reference itself can run (its plain resnet50 / 101 / 152 build their head
+# for 8192 features and raise a shape error on the first forward); vgg11 / vgg13 are its vgg11_bn / vgg13_bn (:67-68);
+# densenet161 (growth 48), the plain Bottleneck ResNets, the grouped / 3x3-stem SE nets (senet18, senet154, se_resnext*), the
+# VGG nets without BatchNorm and vgg16 / vgg19 are not built
 base_networks = {'resnet18': resnet18, 'resnet34': resnet34, 'densenet18': densenet18, 'densenet121': densenet121,
                  'densenet169': densenet169, 'densenet201': densenet201, 'se_resnet18': se_resnet18,
+                 'se_resnet50': se_resnet50, 'se_resnet101': se_resnet101, 'se_resnet152': se_resnet152,
                  'vgg11': vgg11_bn, 'vgg13': vgg13_bn}

@@ -1,12 +1,13 @@
-"""1-D SE-ResNet-18 breath block on MI355X.
+"""1-D SE-ResNet breath blocks (se_resnet18 / 50 / 101 / 152) on MI355X.
 
-Operator surface of reference ``deepards/models/senet.py`` (SEModule :15-34, SEBasicBlock :37-68, SENet :171-328,
-se_resnet18 :343-348): same constructor arguments, sub-module / parameter names and their order (so ``state_dict`` keys
+Operator surface of reference ``deepards/models/senet.py`` (SEModule :15-34, SEBasicBlock :37-68, Bottleneck :71-95,
+SEResNetBottleneck :122-144, SENet :171-328, se_resnet18 :343-348, se_resnet50 / 101 / 152 :351-372): same constructor arguments, sub-module / parameter names and their order (so ``state_dict`` keys
 match), ``n_out_filters`` and ``network_name``.  As in ``resnet.py`` the torch.nn leaf modules are only parameter containers:
 ``forward`` runs the HIP kernels through ``deepards_amd.functional`` on a whole batch of windows.
 
-Built: the BasicBlock variant on the k7 stem (``se_resnet18`` and other ``layers`` lists).  The grouped-conv / 3x3-stem
-nets (``senet18``, ``senet154``) and the Bottleneck / ResNeXt blocks are refused in the constructor.  Initialisation is
+Built: the BasicBlock and the SE-ResNet Bottleneck variants on the k7 stem (``se_resnet18``, ``se_resnet50`` / ``101`` /
+``152`` and other ``layers`` lists).  The grouped-conv / 3x3-stem nets (``senet18``, ``senet154``) and the SENet-154 /
+ResNeXt bottlenecks (``SEBottleneck``, ``SEResNeXtBottleneck``) are refused in the constructor.  Initialisation is
 torch's defaults: the reference's SENet has no init loop.
 """
 from collections import OrderedDict
@@ -62,8 +63,45 @@ class SEBasicBlock(nn.Module):
             F_.BNState(self.bn1), F_.BNState(self.bn2), dsw[3])
 
 
+class SEResNetBottleneck(nn.Module):
+    """Parameter container of one SE-ResNet bottleneck block: conv1 (k1, carries the stride) -> conv2 (k3) -> conv3 (k1, to
+    4 planes channels) with the gate on the wide map; child names and their order are the state_dict contract (conv1, bn1,
+    conv2, bn2, conv3, bn3, relu, se_module, downsample -- senet.py:132-144)."""
+    expansion = 4
+    precise_convs = True      # functional.training_step: conv2 is packed for F(2,3) at every width (H._wino)
+
+    def __init__(self, inplanes, planes, groups, reduction, stride=1, downsample=None):
+        super(SEResNetBottleneck, self).__init__()
+        if groups != 1:
+            raise NotImplementedError('grouped convolutions (senet18 / senet154, the ResNeXt nets) are not on the accelerated path')
+        c = planes * 4
+        cr = c // reduction if reduction >= 1 else 0
+        if planes % 32 or inplanes % 32 or not F_.H.se_wide_ok(c, cr) or cr * reduction != c:
+            raise NotImplementedError('the SE bottleneck takes planes and inplanes that are multiples of 32 and a gate on 4 planes <= '
+                                      '2048 channels whose hidden width is a multiple of 16 up to 128 (reduction 16 on the four stages)')
+        self.conv1 = nn.Conv1d(inplanes, planes, kernel_size=1, bias=False, stride=stride)
+        self.bn1 = nn.BatchNorm1d(planes)
+        self.conv2 = nn.Conv1d(planes, planes, kernel_size=3, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm1d(planes)
+        self.conv3 = nn.Conv1d(planes, planes * 4, kernel_size=1, bias=False)
+        self.bn3 = nn.BatchNorm1d(planes * 4)
+        self.relu = nn.ReLU(inplace=True)
+        self.se_module = SEModule(planes * 4, reduction=reduction)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward_rlc(self, x, R):
+        """x: (rows, L, C) channels-last; R rows per BatchNorm window."""
+        ds, se = self.downsample, self.se_module
+        dsw = (None, None, None, None) if ds is None else (ds[0].weight, ds[1].weight, ds[1].bias, F_.BNState(ds[1]))
+        return F_.SEBottleneckFunction.apply(
+            x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias,
+            self.conv3.weight, self.bn3.weight, self.bn3.bias, se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias,
+            dsw[0], dsw[1], dsw[2], self.stride, R, F_.BNState(self.bn1), F_.BNState(self.bn2), F_.BNState(self.bn3), dsw[3])
+
+
 class SENet(nn.Module):
-    """Four stages of SEBasicBlocks behind layer0 = conv k7 s2 -> BN -> ReLU -> MaxPool1d(3, 2, ceil_mode=True).  The module
+    """Four stages of SEBasicBlocks or SEResNetBottlenecks behind layer0 = conv k7 s2 -> BN -> ReLU -> MaxPool1d(3, 2, ceil_mode=True).  The module
     tree (names, order, shapes) is the reference's (senet.py:219-289)."""
 
     fused_tail = True     # forward_windows(pooled='fused'): the 7-position map, which the head pools
@@ -71,8 +109,9 @@ class SENet(nn.Module):
     def __init__(self, block, layers, groups, reduction, dropout_p=0.2, inplanes=128, input_3x3=True, downsample_kernel_size=3,
                  downsample_padding=1):
         super(SENet, self).__init__()
-        if block is not SEBasicBlock:
-            raise NotImplementedError('only SEBasicBlock (se_resnet18 style) is on the accelerated path')
+        if block not in (SEBasicBlock, SEResNetBottleneck):
+            raise NotImplementedError('only SEBasicBlock (se_resnet18 style) and SEResNetBottleneck (se_resnet50 style) are on '
+                                      'the accelerated path')
         if groups != 1:
             raise NotImplementedError('grouped convolutions (senet18 / senet154, the ResNeXt nets) are not on the accelerated path')
         if input_3x3:
@@ -108,7 +147,7 @@ class SENet(nn.Module):
         return nn.Sequential(*stage)
 
     def _map(self, x, rows_per_window):
-        """The last block's map (rows, L / 32, 512) channels-last."""
+        """The last block's map (rows, L / 32, 512 * block.expansion) channels-last."""
         if F_.conv_dtype() != 'f32' or F_.storage_dtype() != 'f32':
             raise NotImplementedError("the SE-ResNets run with conv arithmetic 'f32' and float storage only (got %s / %s): the SE "
                                       'tail has no bf16 / f32x3p forms' % (F_.conv_dtype(), F_.storage_dtype()))
@@ -158,3 +197,22 @@ def se_resnet18():
                   downsample_kernel_size=1, downsample_padding=0)
     model.network_name = 'se_resnet18'
     return model
+
+
+def _se_resnet_bottleneck(name, layers):
+    model = SENet(SEResNetBottleneck, layers, groups=1, reduction=16, dropout_p=None, inplanes=64, input_3x3=False,
+                  downsample_kernel_size=1, downsample_padding=0)
+    model.network_name = name
+    return model
+
+
+def se_resnet50():
+    return _se_resnet_bottleneck('se_resnet50', [3, 4, 6, 3])
+
+
+def se_resnet101():
+    return _se_resnet_bottleneck('se_resnet101', [3, 4, 23, 3])
+
+
+def se_resnet152():
+    return _se_resnet_bottleneck('se_resnet152', [3, 8, 36, 3])

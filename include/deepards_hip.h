@@ -570,6 +570,39 @@ int da_se_gate_bwd(const float* dsum, const float* s, const float* hid, const fl
                    int Cr, da_stream_t stream);
 int da_se_bwd_scale(const float* g, const float* s, const float* dpool, float* dz, int rows, int L, int C, da_stream_t stream);
 
+/* ---- the same tail at an SE-ResNet Bottleneck's width (senet.py:15-34 SEModule, :71-95 Bottleneck.forward, :122-144
+ * SEResNetBottleneck; se_resnet50 / 101 / 152 :351-372): the gate acts on 4 planes channels with reduction 16 --------------
+ *     out = relu(z * s + res),  z = bn3(y3),  s = sigmoid(fc2(relu(fc1(mean_L z))))  per (row, channel)
+ * Shapes: C % 64 == 0, 64 <= C <= 2048, Cr % 16 == 0, 16 <= Cr <= 128 (da_se_wide_shape_ok), any L >= 1, rows L and rows C below 2^31, R dividing
+ * rows; anything else -> DA_EINVAL before any launch.  float storage only; z is never stored; no atomics, every sum in an
+ * order fixed by the shape.
+ *   da_se_wide_stats      one kernel over y3 (each row slice read twice by its block, the second time from the cache): rowsum (rows, C) = sum_l y3 and mean / invstd (rows / R, C) (row moments merged in
+ *                         row order); workspace rows C floats.  replaces bn3's statistics and SEModule.avg_pool, senet.py:28,88
+ *   da_se_wide_gate_fwd   three launches: pool = fmaf(rowsum / L, sc, sh) elementwise, then per tile of 32 rows hid = relu(pool
+ *                         W1^T + b1) and s = sigmoid(hid W2^T + b2) as GEMMs on the fp32 matrix cores (senet.py:29-32), each
+ *                         weight read once per row tile; the map itself is not read
+ *   da_se_wide_scale_fwd, da_se_wide_bwd_scale   da_se_scale_fwd / da_se_bwd_scale's kernels at these widths (senet.py:33,93-94)
+ *   da_se_wide_bwd_reduce g = dout . mask and dsum[row][c] = sum_l g z
+ *   da_se_wide_gate_bwd   dpool and dw1 / db1 / dw2 / db2 (+= when accumulate): GEMMs with K = rows over chunks of
+ *                         da_se_wide_chunk_rows() rows, folded in chunk order; workspace da_se_wide_gate_bwd_workspace() bytes */
+int da_se_wide_shape_ok(int C, int Cr);
+int da_se_wide_stats(const float* y3, int rows, int R, int L, int C, float eps, float* mean, float* invstd, float* rowsum,
+                     float* workspace, da_stream_t stream);
+int da_se_wide_gate_fwd(const float* rowsum, int rows, int R, int L, int C, int Cr, const float* mean, const float* invstd,
+                        const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2, const float* b2,
+                        float* pool, float* hid, float* s, da_stream_t stream);
+int da_se_wide_scale_fwd(const float* y3, const float* res, float* out, void* mask, int rows, int R, int L, int C,
+                         const float* mean, const float* invstd, const float* gamma, const float* beta, const float* s,
+                         da_stream_t stream);
+int da_se_wide_bwd_reduce(const float* dout, const void* mask, const float* y3, float* g, float* dsum, int rows, int R, int L,
+                          int C, const float* mean, const float* invstd, const float* gamma, const float* beta, da_stream_t stream);
+int da_se_wide_chunk_rows(void);
+size_t da_se_wide_gate_bwd_workspace(int rows, int C, int Cr);
+int da_se_wide_gate_bwd(const float* dsum, const float* s, const float* hid, const float* pool, const float* w1, const float* w2,
+                        float* dpool, float* dw1, float* db1, float* dw2, float* db2, int accumulate, float* workspace, int rows,
+                        int C, int Cr, da_stream_t stream);
+int da_se_wide_bwd_scale(const float* g, const float* s, const float* dpool, float* dz, int rows, int L, int C, da_stream_t stream);
+
 /* ---- the pooled stages and the feature layout of the VGG backbones (vgg.py:37-50 make_layers, :15,20-24) --------------------
  *     out[row][j][c] = max(relu(z[2j]), relu(z[2j + 1])),  z = bn(y) = fmaf(y, gamma invstd, beta - mean gamma invstd),  j < Lin / 2
  * float activations, y [rows][Lin][ldy] the stored conv output (WITHOUT the conv bias: BN(conv + b) == BN(conv)), BatchNorm
