@@ -314,9 +314,8 @@ def load_base_network(path, base_networks, build_args=None):
     name = name or build_args.get('base_network')
     if name not in base_networks:
         raise ValueError('base network %r of %s is not built by this package' % (name, path))
-    kwargs = build_args.get('resnet_kwargs', {}) if name.startswith('resnet') else {} if name.startswith(('se_', 'vgg')) else \
-        build_args.get('densenet_kwargs', {})
-    net = base_networks[name](**kwargs)
+    from . import models as M
+    net = M.build_base_network(name, build_args)
     net.load_state_dict(bb, strict=True)
     return net
 

@@ -189,16 +189,17 @@ def _entry_fwd(entry, x, x3, w1, wd, stride):
     return H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 1), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
 
 
-def _entry_dgrad(entry, dy1, w1, dyd, wd, stride, lin):
+def _entry_dgrad(entry, dy1, w1, dyd, wd, stride, lin, precise=False):
     """dx = conv1's data gradient + the downsample conv's, in the one launch of the entry form the forward chose -- or as
-    two launches, the second accumulating: ``entry`` None (separate convs), or BF16 with _BF16_DGRAD_PAIR off."""
+    two launches, the second accumulating: ``entry`` None (separate convs, conv1's ``precise`` as in its forward), or BF16 with
+    _BF16_DGRAD_PAIR off."""
     if entry == H.X3:
         return H.conv_x3p_s2_dgrad(dy1, _pack(w1, H.X3)[3], dyd, _pack(wd, H.X3)[3])
     if entry == H.DIRECT:
         return H.conv_dgrad_s2_pair(dy1, _pack(w1, H.DIRECT)[1], dyd, _pack(wd, H.DIRECT)[1], lin)
     if entry == H.BF16 and _BF16_DGRAD_PAIR:
         return H.conv_dgrad_bf16_s2_pair(dy1, _pack(w1, H.BF16)[3], dyd, _pack(wd, H.BF16)[3], lin)
-    dx = _conv_dgrad(dy1, w1, stride, 1, lin)
+    dx = _conv_dgrad(dy1, w1, stride, 1, lin, precise=precise)
     return _conv_dgrad(dyd, wd, stride, 0, lin, out=dx, accumulate=True)
 
 
@@ -253,7 +254,7 @@ def _bn_apply_x(x, R, s, st, gamma, beta, relu, res=None, want_mask=False, out_x
     r = H.bn_fwd_x(x, R, gamma, beta, relu=relu, res=res, eps=st.eps, want_mask=want_mask, out_x3=out_x3)
     s.mean, s.invstd = r[1], r[2]
     s.mask = r[3] if want_mask else None
-    _running(x, R, s, st)
+    _running(s.mean, s.invstd, R * x.shape[1], st)
     return r[0]
 
 
@@ -287,15 +288,15 @@ def _bn_apply(x, R, s, st, gamma, beta, relu, res=None, want_mask=False):
         out, s.mean, s.invstd, s.mask = H.bn_fwd(x, R, gamma, beta, relu=relu, res=res, eps=st.eps, want_mask=True)
     else:
         out, s.mean, s.invstd = H.bn_fwd(x, R, gamma, beta, relu=relu, res=res, eps=st.eps)
-    _running(x, R, s, st)
+    _running(s.mean, s.invstd, R * x.shape[1], st)
     return out
 
 
-def _running(x, R, s, st):
+def _running(mean, invstd, wn, st):
+    """Book the running-statistics update of BatchNorm ``st`` from the batch statistics of its windows of ``wn`` positions."""
     if st.running_mean is None:
         return
-    item = (s.mean, s.invstd, R * x.shape[1], st.running_mean, st.running_var, st.num_batches_tracked, st.momentum,
-            st.eps)
+    item = (mean, invstd, wn, st.running_mean, st.running_var, st.num_batches_tracked, st.momentum, st.eps)
     if _STEP['on']:
         _STEP['running'].append(item)
     else:
@@ -314,7 +315,6 @@ class StemFunction(Function):
         # statistics, the apply + pool pass and the whole backward recompute it from the raw rows (bit for bit the same
         # forward values; H.stem_fused_fwd / stem_fused_bwd).  The stems with FFT channels keep the stored map.
         ctx.fused = _STEM_FUSED and H.stem_fused_ok(x2d, w, R)
-        s_ = _Stats()
         c0 = w.shape[0]
         buf = view = None
         if out_cb > c0:
@@ -333,13 +333,7 @@ class StemFunction(Function):
             wn = R * y0.shape[1]
         if buf is not None:
             out = buf
-        s_.mean, s_.invstd = mean, invstd
-        if st.running_mean is not None:
-            item = (mean, invstd, wn, st.running_mean, st.running_var, st.num_batches_tracked, st.momentum, st.eps)
-            if _STEP['on']:
-                _STEP['running'].append(item)
-            else:
-                H.bn_running_multi([item])
+        _running(mean, invstd, wn, st)
         ctx.save_for_backward(x2d, y0, mean, invstd, gamma, beta)
         ctx.R, ctx.pool_mode = R, pool_mode
         ctx.gt = _tgt(w, gamma, beta)
@@ -395,9 +389,7 @@ class DoubleStemFunction(Function):
         y2 = H.conv_fwd(h, wf, 2, 3)                                  # (rows, L / 2, C0)
         m2, i2 = H.bn_stats(y2, R, st2.eps)
         out = H.bn_relu_pool_fwd(y2, R, m2, i2, g2, b2, pool_mode, out_x3=want_out3)
-        s2 = _Stats()
-        s2.mean, s2.invstd = m2, i2
-        _running(y2, R, s2, st2)
+        _running(m2, i2, R * y2.shape[1], st2)
         ctx.save_for_backward(x2d, ya, s1.mean, s1.invstd, g1, b1, h, wd, y2, m2, i2, g2, b2)
         ctx.R, ctx.pool_mode = R, pool_mode
         ctx.gt = _tgt(wa, g1, b1, w2, g2, b2)
@@ -525,8 +517,8 @@ class BasicBlockFunction(Function):
         if bn_pair:
             (res, sd.mean, sd.invstd, _), (h1, s1.mean, s1.invstd, _) = H.bn_fwd_pair(
                 [(yd, gd, bd, False, None, False), (y1, g1, b1, True, None, False)], R, st1.eps)
-            _running(yd, R, sd, std)
-            _running(y1, R, s1, st1)
+            _running(sd.mean, sd.invstd, R * yd.shape[1], std)
+            _running(s1.mean, s1.invstd, R * y1.shape[1], st1)
         elif pair:        # the downsample BatchNorm first: yd is still in L2 / MALL right after the shared launch
             res = _bn_apply(yd, R, sd, std, gd, bd, False)   # (forking it beside bn1 / conv2 on another stream was measured slower)
         if fuse1:         # bn1 + ReLU applied while conv2 stages its operand: statistics from the records conv1's epilogue wrote
@@ -534,7 +526,7 @@ class BasicBlockFunction(Function):
             s1.mean = torch.empty((wn_, y1.shape[2]), device=y1.device, dtype=torch.float32)
             s1.invstd = torch.empty_like(s1.mean)
             y2 = H.conv3_bf16_bn(y1, _pack(w2, H.BF16)[2], R, rec=rec1, mean=s1.mean, invstd=s1.invstd, gamma=g1, beta=b1, eps=st1.eps)
-            _running(y1, R, s1, st1)
+            _running(s1.mean, s1.invstd, R * y1.shape[1], st1)
             h1 = y1                                     # (placeholder in the saved list: the backward rebuilds h1 for the weight gradient)
             if DECISION_TAP is not None:
                 _tap(H.bn_fwd(y1, R, g1, b1, relu=True, eps=st1.eps)[0])
@@ -558,7 +550,7 @@ class BasicBlockFunction(Function):
             if mid3 or want_out3 or wd is not None or not H.bn_pool_ok(y2, R):
                 raise ValueError('pool_out: an identity block on a map with the pooled BatchNorm form (pool_out_ok)')
             out, s2.mean, s2.invstd, s2.mask = H.bn_fwd_pool(y2, R, g2, b2, res=res, eps=st2.eps)
-            _running(y2, R, s2, st2)
+            _running(s2.mean, s2.invstd, R * y2.shape[1], st2)
             if DECISION_TAP is not None:
                 _tap(H.bn_fwd(y2, R, g2, b2, relu=True, res=res, eps=st2.eps)[0])
         elif mid3:        # x3 residual and / or x3 output: the store forms (always with the ReLU bit mask)
@@ -649,101 +641,21 @@ class BasicBlockFunction(Function):
         return dx, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd, None, None, None, None, None, None, None, None, None
 
 
-class SEBasicBlockFunction(Function):
-    """conv3(s) -> BN -> ReLU -> conv3 -> BN -> * gate (+ identity | BN(conv1x1(s))) -> ReLU with
-    gate = sigmoid(fc2(relu(fc1(mean_L(bn2(..)))))) per row and channel.
-    reference models/senet.py:52-68 (SEBasicBlock.forward), :27-34 (SEModule.forward), :295-300 (downsample).
-
-    The tail [stats -> gate -> scale + residual + ReLU] is H.se_stats / se_gate_fwd / se_scale_fwd: bn2's output z is never
-    stored (the kernels recompute it from y2); the backward is H.se_bwd_reduce -> se_gate_bwd -> se_bwd_scale in front of bn2's
-    plain BatchNorm backward.  fp32 conv arithmetic and float storage only (no x3 / bf16 / pooled-output forms).  Its k3 s1
-    convs keep off F(4,3) (``precise``, H._wino): at 512 channels they run on F(2,3), forward, data and weight gradients."""
-
-    @staticmethod
-    def forward(ctx, x, w1, g1, b1, w2, g2, b2, f1w, f1b, f2w, f2b, wd, gd, bd, stride, R, st1, st2, std):
-        if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
-            raise NotImplementedError('the SE block runs with fp32 conv arithmetic and float activation storage only')
-        # conv1 and the downsample conv of a stride-2 entry in one launch (H.DIRECT), or None: separate convs
-        entry = H.s2_entry_kernel(w1.shape, None if wd is None else wd.shape, stride, x.shape[1], False)
-        ctx.entry = entry
-        if entry is not None:
-            y1, yd = _entry_fwd(entry, x, None, w1, wd, stride)
-        else:
-            y1 = _conv_fwd(x, w1, stride, 1, precise=True)
-        if wd is not None:
-            if entry is None:
-                yd = _conv_fwd(x, wd, stride, 0)
-            sd = _Stats()
-            res = _bn_apply(yd, R, sd, std, gd, bd, False)
-            md, idd = sd.mean, sd.invstd
-        else:
-            res = x
-        s1 = _Stats()
-        h1 = _bn_apply(y1, R, s1, st1, g1, b1, True)
-        _tap(h1)
-        y2 = _conv_fwd(h1, w2, 1, 1, precise=True)
-        s2 = _Stats()
-        s2.mean, s2.invstd = H.se_stats(y2, R, st2.eps)
-        _running(y2, R, s2, st2)
-        pool, hid, gate = H.se_gate_fwd(y2, R, s2.mean, s2.invstd, g2, b2, f1w, f1b, f2w, f2b)
-        out, mask = H.se_scale_fwd(y2, R, s2.mean, s2.invstd, g2, b2, gate, res)
-        _tap(out)
-        ctx.has_ds = wd is not None
-        ctx.stride, ctx.R, ctx.lin = stride, R, x.shape[1]
-        ctx.gt = _tgt(w1, g1, b1, w2, g2, b2, f1w, f1b, f2w, f2b, wd, gd, bd)
-        saved = [x, w1, g1, b1, w2, g2, b2, f1w, f2w, y1, s1.mean, s1.invstd, h1, y2, s2.mean, s2.invstd, pool, hid, gate, mask]
-        if ctx.has_ds:
-            saved += [wd, gd, bd, yd, md, idd]
-        ctx.save_for_backward(*saved)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        s = ctx.saved_tensors
-        x, w1, g1, b1, w2, g2, b2, f1w, f2w, y1, m1, i1, h1, y2, m2, i2, pool, hid, gate, mask = s[:20]
-        tw1, tg1, tb1, tw2, tg2, tb2, tf1w, tf1b, tf2w, tf2b, twd, tgd, tbd = ctx.gt
-        R, stride, lin = ctx.R, ctx.stride, ctx.lin
-        # relu + residual add (g: the residual's gradient), the gate, then bn2 on dz
-        g, dsum = H.se_bwd_reduce(dout.contiguous(), mask, y2, R, m2, i2, g2, b2)
-        se_t = (tf1w, tf1b, tf2w, tf2b)
-        direct = all(t is not None for t in se_t)          # a trainer's destinations: written (or accumulated) in place
-        dpool, se_g = H.se_gate_bwd(dsum, gate, hid, pool, f1w, f2w, grads=se_t if direct else None, accumulate=direct and _acc())
-        df1w, df1b, df2w, df2b = (None,) * 4 if direct else se_g
-        dz = H.se_bwd_scale(g, gate, dpool)
-        dy2, dg2, db2 = _bn_bwd(dz, y2, R, m2, i2, g2, b2, 0, tg2, tb2, dx=dz)
-        if ctx.has_ds:        # the downsample BatchNorm's backward right away: g is still cache-resident
-            wd, gd, bd, yd, md, idd = s[20:]
-            dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, tgd, tbd, dx=g)
-        dw2 = _wgrad(dy2, h1, 3, 1, 1, tw2, precise=True)
-        dh1 = _conv_dgrad(dy2, w2, 1, 1, y1.shape[1], precise=True)
-        dy1, dg1, db1 = _bn_bwd(dh1, y1, R, m1, i1, g1, b1, 1, tg1, tb1, dx=dh1)
-        dw1 = _wgrad(dy1, x, 3, stride, 1, tw1, precise=True)
-        if ctx.has_ds:
-            dwd = _wgrad(dyd, x, 1, stride, 0, twd)
-            dx = _entry_dgrad(ctx.entry, dy1, w1, dyd, wd, stride, lin)
-        else:
-            dwd = dgd = dbd = None
-            dx = _conv_dgrad(dy1, w1, stride, 1, lin, out=g, accumulate=True, precise=True)       # identity grad + conv path
-        return dx, dw1, dg1, db1, dw2, dg2, db2, df1w, df1b, df2w, df2b, dwd, dgd, dbd, None, None, None, None, None
-
-
-def _se_tail_fwd(y, R, st, gamma, beta, f1w, f1b, f2w, f2b, res):
-    """[statistics -> gate -> scale + residual + ReLU] behind a block's last conv on the kernel family H.se_gate_family names
-    for the gate's (C, Cr).  Wide: one kernel over the map gives the statistics and the row sums, the gate never reads the map.
-    -> out, mask, (mean, invstd, pool, hid, gate), family."""
-    fam = H.se_gate_family(y.shape[2], f1w.shape[0])
-    s = _Stats()
+def _se_tail_fwd(fam, y, R, st, gamma, beta, f1w, f1b, f2w, f2b, res):
+    """[statistics -> gate -> scale + residual + ReLU] behind a block's last conv on the kernel family ``fam`` (H.SE_NARROW /
+    H.SE_WIDE: the block names it, models/senet.py).  Wide: one kernel over the map gives the statistics and the row sums, the
+    gate never reads the map.  -> out, mask, (mean, invstd, pool, hid, gate)."""
     if fam == H.SE_WIDE:
-        s.mean, s.invstd, rowsum = H.se_wide_stats(y, R, st.eps)
-        _running(y, R, s, st)
-        pool, hid, gate = H.se_wide_gate_fwd(rowsum, R, y.shape[1], s.mean, s.invstd, gamma, beta, f1w, f1b, f2w, f2b)
-        out, mask = H.se_wide_scale_fwd(y, R, s.mean, s.invstd, gamma, beta, gate, res)
+        mean, invstd, rowsum = H.se_wide_stats(y, R, st.eps)
+        _running(mean, invstd, R * y.shape[1], st)
+        pool, hid, gate = H.se_wide_gate_fwd(rowsum, R, y.shape[1], mean, invstd, gamma, beta, f1w, f1b, f2w, f2b)
+        out, mask = H.se_wide_scale_fwd(y, R, mean, invstd, gamma, beta, gate, res)
     else:
-        s.mean, s.invstd = H.se_stats(y, R, st.eps)
-        _running(y, R, s, st)
-        pool, hid, gate = H.se_gate_fwd(y, R, s.mean, s.invstd, gamma, beta, f1w, f1b, f2w, f2b)
-        out, mask = H.se_scale_fwd(y, R, s.mean, s.invstd, gamma, beta, gate, res)
-    return out, mask, (s.mean, s.invstd, pool, hid, gate), fam
+        mean, invstd = H.se_stats(y, R, st.eps)
+        _running(mean, invstd, R * y.shape[1], st)
+        pool, hid, gate = H.se_gate_fwd(y, R, mean, invstd, gamma, beta, f1w, f1b, f2w, f2b)
+        out, mask = H.se_scale_fwd(y, R, mean, invstd, gamma, beta, gate, res)
+    return out, mask, (mean, invstd, pool, hid, gate)
 
 
 def _se_tail_bwd(fam, dout, mask, y, R, mean, invstd, gamma, beta, pool, hid, gate, f1w, f2w, se_t):
@@ -758,77 +670,100 @@ def _se_tail_bwd(fam, dout, mask, y, R, mean, invstd, gamma, beta, pool, hid, ga
     return g, dz, (None,) * 4 if direct else se_g
 
 
-class SEBottleneckFunction(Function):
-    """conv1(k1, s) -> BN -> ReLU -> conv3 -> BN -> ReLU -> conv1 -> BN -> * gate (+ identity | BN(conv1x1(s))) -> ReLU with
-    gate = sigmoid(fc2(relu(fc1(mean_L(bn3(..)))))) per row and channel.
-    reference models/senet.py:75-95 (Bottleneck.forward), :122-144 (SEResNetBottleneck: the stride sits on conv1), :27-34
-    (SEModule.forward), :295-300 (downsample; layer1.0 has one with stride 1).
+class SEBlockFunction(Function):
+    """An SE residual block over its conv units: conv(s) -> [BN -> ReLU -> conv]* -> BN -> * gate (+ identity | BN(conv1x1(s)))
+    -> ReLU with gate = sigmoid(fc2(relu(fc1(mean_L(bn(..)))))) per row and channel.  Two units k3, k3: SEBasicBlock (reference
+    models/senet.py:52-68); three units k1, k3, k1 with the stride on the first: SEResNetBottleneck (:75-95, :122-144);
+    :27-34 (SEModule.forward), :295-300 (downsample; a bottleneck net's layer1.0 has one with stride 1).
 
-    The k1 convs run on the direct kernels, the two that read a block entry's input in one launch where H.conv_fwd_multi takes
-    them; conv2 (always k3 s1 p1) keeps off F(4,3) as in SEBasicBlockFunction (``precise``).  The tail is _se_tail_fwd /
-    _se_tail_bwd: bn3's output z is never stored, and on the wide family the map y3 is read twice forward (statistics with
-    row sums, scale) and the narrow activations h1, h2 are the only stored post-ReLU maps.  fp32 conv arithmetic and float
-    storage only."""
+    ``units``: (kernel size, precise, BNState) of every conv unit; ``params``: (conv weight, BN weight, BN bias) of every
+    unit, fc1 / fc2 weight and bias, then the downsample's (conv weight, BN weight, BN bias) where there is one (``std``:
+    its BNState).  ``family``: the gate kernels' (H.SE_NARROW / H.SE_WIDE), named by the block.
+
+    The entry is the first unit's: a k3 conv1 and the downsample conv of a stride-2 entry in one launch (H.s2_entry_kernel), a
+    k1 conv1 and the downsample conv in one H.conv_fwd_multi launch -- both read the block's input.  The k3 convs keep off
+    F(4,3) (``precise``, H._wino): at 512 channels they run on F(2,3), forward, data and weight gradients; the k1 convs run on
+    the direct kernels.  The tail [stats -> gate -> scale + residual + ReLU] is _se_tail_fwd / _se_tail_bwd in front of the last
+    BatchNorm's plain backward: that BatchNorm's output z is never stored (the kernels recompute it from the last conv's map),
+    and on the wide family the map is read twice forward (statistics with row sums, scale).  fp32 conv arithmetic and float
+    storage only (no x3 / bf16 / pooled-output forms)."""
 
     @staticmethod
-    def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f1b, f2w, f2b, wd, gd, bd, stride, R, st1, st2, st3, std):
+    def forward(ctx, x, stride, R, family, units, std, *params):
         if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
-            raise NotImplementedError('the SE bottleneck runs with fp32 conv arithmetic and float activation storage only')
-        if wd is not None:          # conv1 and the downsample conv read the same input: one launch
-            y1, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 0), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
-            sd = _Stats()
-            res = _bn_apply(yd, R, sd, std, gd, bd, False)
+            raise NotImplementedError('the SE blocks run with fp32 conv arithmetic and float activation storage only')
+        n = len(units)
+        convs = [params[3 * i:3 * i + 3] for i in range(n)]
+        f1w, f1b, f2w, f2b = params[3 * n:3 * n + 4]
+        wd, gd, bd = params[3 * n + 4:] or (None, None, None)
+        w1, (k1, precise1, _) = convs[0][0], units[0]
+        # conv1 and the downsample conv in one launch where the entry has that form; else separate convs
+        ctx.entry = H.s2_entry_kernel(w1.shape, None if wd is None else wd.shape, stride, x.shape[1], False) if k1 == 3 else None
+        if ctx.entry is not None:
+            y, yd = _entry_fwd(ctx.entry, x, None, w1, wd, stride)
+        elif k1 == 1 and wd is not None:
+            y, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 0), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
         else:
-            y1 = _conv_fwd(x, w1, stride, 0)
-            res = x
-        s1 = _Stats()
-        h1 = _bn_apply(y1, R, s1, st1, g1, b1, True)
-        _tap(h1)
-        y2 = _conv_fwd(h1, w2, 1, 1, precise=True)
-        s2 = _Stats()
-        h2 = _bn_apply(y2, R, s2, st2, g2, b2, True)
-        _tap(h2)
-        y3 = _conv_fwd(h2, w3, 1, 0)
-        out, mask, tail, ctx.family = _se_tail_fwd(y3, R, st3, g3, b3, f1w, f1b, f2w, f2b, res)
+            y = _conv_fwd(x, w1, stride, k1 // 2, precise=precise1)
+            yd = None if wd is None else _conv_fwd(x, wd, stride, 0)
+        sd = _Stats()
+        res = x if wd is None else _bn_apply(yd, R, sd, std, gd, bd, False)
+        ys, hs, ms = [y], [], []                    # every unit's conv output; the stored post-ReLU maps; (mean, invstd) pairs
+        for i in range(1, n):
+            s = _Stats()
+            h = _bn_apply(ys[-1], R, s, units[i - 1][2], convs[i - 1][1], convs[i - 1][2], True)
+            _tap(h)
+            k, precise, _ = units[i]
+            ys.append(_conv_fwd(h, convs[i][0], 1, k // 2, precise=precise))
+            hs.append(h)
+            ms += [s.mean, s.invstd]
+        out, mask, tail = _se_tail_fwd(family, ys[-1], R, units[-1][2], convs[-1][1], convs[-1][2], f1w, f1b, f2w, f2b, res)
         _tap(out)
-        ctx.has_ds = wd is not None
-        ctx.stride, ctx.R, ctx.lin = stride, R, x.shape[1]
-        ctx.gt = _tgt(w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f1b, f2w, f2b, wd, gd, bd)
-        saved = [x, w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f2w, y1, s1.mean, s1.invstd, h1, y2, s2.mean, s2.invstd, h2, y3,
-                 *tail, mask]
-        if ctx.has_ds:
+        ctx.meta = [(k, precise) for k, precise, _ in units]
+        ctx.family, ctx.stride, ctx.R = family, stride, R
+        ctx.gt = _tgt(*params)
+        saved = [x, f1w, f2w, mask, *tail] + [t for c in convs for t in c] + ys + hs + ms
+        if wd is not None:
             saved += [wd, gd, bd, yd, sd.mean, sd.invstd]
         ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        s = ctx.saved_tensors
-        x, w1, g1, b1, w2, g2, b2, w3, g3, b3, f1w, f2w, y1, m1, i1, h1, y2, m2, i2, h2, y3, m3, i3, pool, hid, gate, mask = s[:27]
-        tw1, tg1, tb1, tw2, tg2, tb2, tw3, tg3, tb3, tf1w, tf1b, tf2w, tf2b, twd, tgd, tbd = ctx.gt
-        R, stride, lin = ctx.R, ctx.stride, ctx.lin
-        # relu + residual add (g: the residual's gradient), the gate, then bn3 on dz
-        g, dz, (df1w, df1b, df2w, df2b) = _se_tail_bwd(ctx.family, dout.contiguous(), mask, y3, R, m3, i3, g3, b3, pool, hid, gate,
-                                                       f1w, f2w, (tf1w, tf1b, tf2w, tf2b))
-        dy3, dg3, db3 = _bn_bwd(dz, y3, R, m3, i3, g3, b3, 0, tg3, tb3, dx=dz)
-        if ctx.has_ds:        # the downsample BatchNorm's backward right away: g is still cache-resident
-            wd, gd, bd, yd, md, idd = s[27:]
-            dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, tgd, tbd, dx=g)
-        dw3 = _wgrad(dy3, h2, 1, 1, 0, tw3)
-        dh2 = _conv_dgrad(dy3, w3, 1, 0, y2.shape[1])
-        dy2, dg2, db2 = _bn_bwd(dh2, y2, R, m2, i2, g2, b2, 1, tg2, tb2, dx=dh2)
-        dw2 = _wgrad(dy2, h1, 3, 1, 1, tw2, precise=True)
-        dh1 = _conv_dgrad(dy2, w2, 1, 1, y1.shape[1], precise=True)
-        dy1, dg1, db1 = _bn_bwd(dh1, y1, R, m1, i1, g1, b1, 1, tg1, tb1, dx=dh1)
-        dw1 = _wgrad(dy1, x, 1, stride, 0, tw1)
-        if ctx.has_ds:        # both k1 data gradients land on the same (every stride-th) positions: the second launch accumulates
-            dwd = _wgrad(dyd, x, 1, stride, 0, twd)
+        s, t, n = ctx.saved_tensors, ctx.gt, len(ctx.meta)
+        x, f1w, f2w, mask, mean, invstd, pool, hid, gate = s[:9]
+        convs = [s[9 + 3 * i:12 + 3 * i] for i in range(n)]
+        o = 9 + 3 * n
+        ys, hs = s[o:o + n], (x,) + s[o + n:o + 2 * n - 1]                    # hs[i]: what unit i's conv read
+        ms, ds = s[o + 2 * n - 1:o + 4 * n - 3] + (mean, invstd), s[o + 4 * n - 3:]
+        R, stride, lin = ctx.R, ctx.stride, x.shape[1]
+        grads = [None] * (3 * n)
+        # relu + residual add (g: the residual's gradient), the gate, then the last BatchNorm on dz
+        g, dz, dgate = _se_tail_bwd(ctx.family, dout.contiguous(), mask, ys[-1], R, mean, invstd, convs[-1][1], convs[-1][2],
+                                    pool, hid, gate, f1w, f2w, t[3 * n:3 * n + 4])
+        dy, grads[-2], grads[-1] = _bn_bwd(dz, ys[-1], R, mean, invstd, convs[-1][1], convs[-1][2], 0, t[3 * n - 2], t[3 * n - 1],
+                                           dx=dz)
+        if ds:                # the downsample BatchNorm's backward right away: g is still cache-resident
+            wd, gd, bd, yd, md, idd = ds
+            dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, t[3 * n + 5], t[3 * n + 6], dx=g)
+        for i in range(n - 1, 0, -1):
+            k, precise = ctx.meta[i]
+            grads[3 * i] = _wgrad(dy, hs[i], k, 1, k // 2, t[3 * i], precise=precise)
+            dh = _conv_dgrad(dy, convs[i][0], 1, k // 2, ys[i - 1].shape[1], precise=precise)
+            dy, grads[3 * i - 2], grads[3 * i - 1] = _bn_bwd(dh, ys[i - 1], R, ms[2 * i - 2], ms[2 * i - 1], convs[i - 1][1],
+                                                             convs[i - 1][2], 1, t[3 * i - 2], t[3 * i - 1], dx=dh)
+        (k1, precise1), w1 = ctx.meta[0], convs[0][0]
+        grads[0] = _wgrad(dy, x, k1, stride, k1 // 2, t[0], precise=precise1)
+        if not ds:
+            dx = _conv_dgrad(dy, w1, stride, k1 // 2, lin, out=g, accumulate=True, precise=precise1)   # identity grad + conv path
+            return (dx, None, None, None, None, None, *grads, *dgate)
+        dwd = _wgrad(dyd, x, 1, stride, 0, t[3 * n + 4])
+        if k1 == 3:
+            dx = _entry_dgrad(ctx.entry, dy, w1, dyd, wd, stride, lin, precise=precise1)
+        else:                 # both k1 data gradients land on the same (every stride-th) positions: the second launch accumulates
             dx = _conv_dgrad(dyd, wd, stride, 0, lin)
-            dx = _conv_dgrad(dy1, w1, stride, 0, lin, out=dx, accumulate=True)
-        else:
-            dwd = dgd = dbd = None
-            dx = _conv_dgrad(dy1, w1, 1, 0, lin, out=g, accumulate=True)                         # identity grad + conv path
-        return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3, df1w, df1b, df2w, df2b, dwd, dgd, dbd) + (None,) * 6
+            dx = _conv_dgrad(dy, w1, stride, 0, lin, out=dx, accumulate=True)
+        return (dx, None, None, None, None, None, *grads, *dgate, dwd, dgd, dbd)
 
 
 class VGGStageFunction(Function):
@@ -860,10 +795,7 @@ class VGGStageFunction(Function):
         zero_bias = tb is not None and _OV['on']        # no zero-fill in this step: the bias gradient's 0 is written here
         if st.running_mean is not None or zero_bias:
             mean_b = H.bn_mean_bias(mean, bias, dbias=tb if zero_bias else None)
-            if st.running_mean is not None:
-                s_ = _Stats()
-                s_.mean, s_.invstd = mean_b, invstd
-                _running(y, R, s_, st)
+            _running(mean_b, invstd, R * y.shape[1], st)
         ctx.R, ctx.pool, ctx.first, ctx.precise = R, bool(pool), bool(first), bool(precise)
         ctx.has_mask, ctx.has_out = mask is not None, out_keep is not None
         ctx.gt = (tw, tb, tg, tbe)

@@ -1,5 +1,6 @@
 """MI355X-native mirror of the reference's ``deepards.models`` operator surface for the cnn_linear
 hot path: same constructors, attributes and ``state_dict`` keys."""
+from .backbone import Backbone, HEAD_MAP, HEAD_FLAT     # noqa: F401
 from .resnet import ResNet, BasicBlock, resnet18, resnet34  # noqa: F401
 from .densenet import DenseNet, densenet18, densenet121, densenet169, densenet201       # noqa: F401
 from .torch_cnn_linear_network import (CNNLinearNetwork, CNNLinearToMean, CNNLinearComprToRF,      # noqa: F401
@@ -16,7 +17,24 @@ from .transformer import MultiHeadAttention, Block, Transformer, CNNTransformerN
 # for 8192 features and raise a shape error on the first forward); vgg11 / vgg13 are its vgg11_bn / vgg13_bn (:67-68);
 # densenet161 (growth 48), the plain Bottleneck ResNets, the grouped / 3x3-stem SE nets (senet18, senet154, se_resnext*), the
 # VGG nets without BatchNorm and vgg16 / vgg19 are not built
-base_networks = {'resnet18': resnet18, 'resnet34': resnet34, 'densenet18': densenet18, 'densenet121': densenet121,
-                 'densenet169': densenet169, 'densenet201': densenet201, 'se_resnet18': se_resnet18,
-                 'se_resnet50': se_resnet50, 'se_resnet101': se_resnet101, 'se_resnet152': se_resnet152,
-                 'vgg11': vgg11_bn, 'vgg13': vgg13_bn}
+# name -> (factory, class, the group of the driver's build arguments the factory takes -- None: it takes none).  What the
+# trainer and the driver decide about a backbone they read from the class's data (models/backbone.py), not from the name.
+BACKBONES = {'resnet18': (resnet18, ResNet, 'resnet_kwargs'), 'resnet34': (resnet34, ResNet, 'resnet_kwargs'),
+             'densenet18': (densenet18, DenseNet, 'densenet_kwargs'), 'densenet121': (densenet121, DenseNet, 'densenet_kwargs'),
+             'densenet169': (densenet169, DenseNet, 'densenet_kwargs'), 'densenet201': (densenet201, DenseNet, 'densenet_kwargs'),
+             'se_resnet18': (se_resnet18, SENet, None), 'se_resnet50': (se_resnet50, SENet, None),
+             'se_resnet101': (se_resnet101, SENet, None), 'se_resnet152': (se_resnet152, SENet, None),
+             'vgg11': (vgg11_bn, VGG, None), 'vgg13': (vgg13_bn, VGG, None)}
+base_networks = {name: row[0] for name, row in BACKBONES.items()}
+
+
+def backbone_class(name):
+    """The class of base network ``name`` (its class data: ``running_stats``, ``bf16_storage``); None for a name not built here."""
+    return BACKBONES[name][1] if name in BACKBONES else None
+
+
+def build_base_network(name, build_args=None):
+    """A fresh base network ``name`` from the driver's build arguments ({'resnet_kwargs': .., 'densenet_kwargs': ..}): the
+    factory gets its own group, or nothing."""
+    factory, _, group = BACKBONES[name]
+    return factory(**((build_args or {}).get(group, {}) if group else {}))

@@ -13,7 +13,8 @@ import torch
 import torch.nn as nn
 
 from .. import functional as F_
-from .resnet import _require_cuda, conv1d, init_like_reference
+from .backbone import Backbone, check_windows
+from .resnet import conv1d, init_like_reference
 
 
 def _bn(c):
@@ -101,13 +102,8 @@ class _Features(nn.Sequential):
     drop_rate = 0.0
 
     def forward_rlc(self, x, R, relu):
-        _require_cuda(x, 'DenseNet')
-        cin = self.conv0.in_channels                       # 1, or 2 / 3 with the FFT channels (densenet.py:109-115)
-        if x.dim() != 3 or x.shape[1] != cin:
-            raise ValueError('expected (rows, %d, L) input, got %s' % (cin, tuple(x.shape)))
+        """x: checked (rows, C_in, L) input (DenseNet.check_input) -> the norm5 output (rows, L', C) channels-last."""
         rows, _, l = x.shape
-        if rows % R:
-            raise ValueError('rows not a multiple of rows_per_window')
         x2d = x.contiguous().float()                       # (rows, C_in, L): the stem kernel reads the NCL rows directly
         use_drop = self.training and self.drop_rate > 0
         plan = self._block_plan(rows, R, l, use_drop)
@@ -179,13 +175,17 @@ class _Features(nn.Sequential):
         return h
 
     def forward(self, x):
+        check_windows('DenseNet', x, x.shape[0], self.conv0.in_channels)
         return self.forward_rlc(x, x.shape[0], False).permute(0, 2, 1)
 
 
-class DenseNet(nn.Module):
+class DenseNet(Backbone):
     """DenseNet-BC on 1-D windows: stem (conv0 k7 s2, norm0, relu0, pool0), `block_config` dense blocks of growth-rate
     layers with halving transitions between them, norm5.  Module names / order / shapes are the reference's
     (densenet.py:83-166): 64 state_dict keys for cnn_linear + densenet18."""
+
+    running_stats = False
+    in_channels = property(lambda self: self.features.conv0.in_channels)     # 1, or 2 / 3 with the FFT channels (densenet.py:109-115)
 
     def __init__(self, growth_rate=32, block_config=(6, 12, 24, 16), num_init_features=64, bn_size=4,
                  drop_rate=0.2, num_classes=1000, with_fft=False, only_fft=False, fft_real_only=False):
@@ -232,26 +232,17 @@ class DenseNet(nn.Module):
     def conv_info(self):
         return self.kernel_sizes, self.strides, self.paddings
 
-    def _features_rlc(self, x, R):
-        return self.features.forward_rlc(x, R, True)
+    def final_length(self, l):
+        cur = ((l + 2 * 3 - 7) // 2 + 1 - 1) // 2 + 1            # conv0 k7 s2 p3, pool0 (3, 2, 1)
+        return cur >> sum(isinstance(mod, _Transition) for mod in self.features.children())
 
-    def forward_windows(self, x, rows_per_window, pooled=True):
-        """pooled=False: the last map (rows, L, C) itself, for a head that pools it in its own kernel (CNNLinearNetwork.forward_loss)."""
-        h = self._features_rlc(x, rows_per_window)
-        if h.shape[1] < 7:
-            raise ValueError('AvgPool1d(7, stride=1) needs a final length >= 7 (seq_len >= 224); got %d' % h.shape[1])
-        if not pooled:
-            if h.shape[1] != 7:
-                raise TypeError('the un-pooled map is only handed out at the 7-position length the fused head pools')
-            return h
-        return F_.GlobalAvgPoolFunction.apply(h)
-
-    def forward(self, x):
-        return self.forward_windows(x, x.shape[0])
+    def _map(self, x, rows_per_window):
+        return self.features.forward_rlc(x, rows_per_window, True)
 
     def forward_no_pool(self, x):
         """relu(features(x)) in the reference's (N, C, L) layout (densenet.py:191-193)."""
-        return self._features_rlc(x, x.shape[0]).permute(0, 2, 1)
+        self.check_input(x, x.shape[0])
+        return self._map(x, x.shape[0]).permute(0, 2, 1)
 
 
 def densenet18(pretrained=False, progress=True, **kwargs):

@@ -12,12 +12,7 @@ import math
 import torch.nn as nn
 
 from .. import functional as F_
-
-
-def _require_cuda(x, what):
-    if not x.is_cuda:
-        raise RuntimeError('%s: the deepards_amd models run on MI355X only (input is on %s); there is no '
-                           'CPU fallback' % (what, x.device))
+from .backbone import Backbone
 
 
 def conv1d(cin, cout, k, stride=1):
@@ -74,12 +69,12 @@ _SPLIT_DX = True          # an identity block's input gradient as two terms, sum
 _FUSED_TAIL = True        # the last block's BatchNorm pools for the head (False, tests: its map is stored and the head pools it)
 
 
-class ResNet(nn.Module):
+class ResNet(Backbone):
     """Four stages of BasicBlocks behind a k7 s2 stem.  The module tree (names, order, shapes -- including the stem's
     unused conv1_alt / conv2 / bn2, SURVEY finding 6) is the reference's (resnet.py:81-135): 129 state_dict keys for
     cnn_linear + resnet18."""
 
-    fused_tail = True     # forward_windows(pooled='fused')
+    bf16_storage = True
 
     def __init__(self, block, layers, initial_planes=64, first_pool_type='max', double_conv_first=False):
         super(ResNet, self).__init__()
@@ -111,26 +106,32 @@ class ResNet(nn.Module):
         init_like_reference(self)
         self.n_out_filters = width
 
-    def forward_windows(self, x, rows_per_window, pooled=True):
-        """x: (rows, 1, L) with rows = windows * rows_per_window; BatchNorm statistics are taken per
-        window, exactly as when the reference feeds one (NB, 1, L) window at a time.  pooled=False: the last map
-        (rows, 7, C) itself, for a head that pools it in its own kernel; pooled='fused' (CNNLinearNetwork.forward_loss):
-        that map, or -- where the last block can pool it itself -- the pooled features (rows, C) without the map."""
-        _require_cuda(x, 'ResNet')
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError('expected (rows, 1, L) input, got %s' % (tuple(x.shape),))
+    def _blocks(self):
+        return [blk for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for blk in layer]
+
+    def _lengths(self, l):
+        """Every block's input length, then the last map's, for rows of l samples."""
+        lens = [((l // 2) - 1) // 2 + 1]                     # stem conv s2, then pool(3, 2, 1)
+        for blk in self._blocks():
+            lens.append((lens[-1] - 1) // blk.stride + 1 if blk.stride > 1 else lens[-1])
+        return lens
+
+    def final_length(self, l):
+        return self._lengths(l)[-1]
+
+    def head_operand(self, x, rows_per_window):
+        """The 7-position map, or -- where the last block can pool it itself -- the pooled features (rows, C) without the map:
+        the fused head takes either."""
+        self._check(x, rows_per_window, want_map=True)
+        return self._map(x, rows_per_window, fused=True)
+
+    def _map(self, x, rows_per_window, fused=False):
         rows, _, l = x.shape
-        if rows % rows_per_window:
-            raise ValueError('rows not a multiple of rows_per_window')
         x2d = x.contiguous().float().view(rows, l)
         pool = F_.POOL_MAX if self.first_pool_type == 'max' else F_.POOL_AVG
         # which blocks read their input in the x3 format (conv arithmetic 'f32x3p'): decided from the shapes up front, so
         # that every producer knows what its consumer wants
-        blocks = [blk for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for blk in layer]
-        lens, cur = [], ((l // 2) - 1) // 2 + 1              # stem conv s2, then pool(3, 2, 1)
-        for blk in blocks:
-            lens.append(cur)
-            cur = (cur - 1) // blk.stride + 1 if blk.stride > 1 else cur
+        blocks, lens = self._blocks(), self._lengths(l)
         takes3 = [blk.takes_x3(rows, li, rows_per_window) for blk, li in zip(blocks, lens)] + [False]
         if self.double_conv_first:          # resnet.py:144-149: conv1_alt -> bn1 -> conv2 -> bn2 (conv1 is the dead one then)
             h = F_.DoubleStemFunction.apply(x2d, self.conv1_alt.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight,
@@ -140,9 +141,9 @@ class ResNet(nn.Module):
             h = F_.StemFunction.apply(x2d, self.conv1.weight, self.bn1.weight, self.bn1.bias, rows_per_window, pool,
                                       F_.BNState(self.bn1), takes3[0])
         for i, blk in enumerate(blocks):
-            # pooled='fused' (CNNLinearNetwork.forward_loss): the last block hands over its POOLED output (rows, C) -- its map
-            # is never stored (BasicBlockFunction pool_out) -- when it is an identity block on the 7-position map
-            pool_out = pooled == 'fused' and _FUSED_TAIL and i == len(blocks) - 1 and not takes3[i] and \
+            # fused (head_operand): the last block hands over its POOLED output (rows, C) -- its map is never stored
+            # (BasicBlockFunction pool_out) -- when it is an identity block on the 7-position map
+            pool_out = fused and _FUSED_TAIL and i == len(blocks) - 1 and not takes3[i] and \
                 blk.downsample is None and blk.stride == 1 and lens[i] == 7 and F_.H.bn_pool_ok(h, rows_per_window)
             # an identity block behind another block hands its input gradient back as two terms (BasicBlockFunction split_dx)
             split_dx = _SPLIT_DX and i > 0 and blk.downsample is None and not takes3[i] and not takes3[i - 1]
@@ -151,21 +152,7 @@ class ResNet(nn.Module):
                 h = blk.forward_rlc(h, rows_per_window, h3, takes3[i + 1])
             else:
                 h = blk.forward_rlc(h, rows_per_window, None, takes3[i + 1], pool_out, split_dx)
-        if pooled == 'fused':
-            if h.dim() == 3 and h.shape[1] != 7:
-                raise TypeError('the un-pooled map is only handed out at the 7-position length the fused head pools')
-            return h
-        if h.shape[1] < 7:
-            raise ValueError('AvgPool1d(7, stride=1) needs a final length >= 7 (seq_len >= 224); got %d' % h.shape[1])
-        if not pooled:
-            if h.shape[1] != 7:
-                raise TypeError('the un-pooled map is only handed out at the 7-position length the fused head pools')
-            return h
-        return F_.GlobalAvgPoolFunction.apply(h)
-
-    def forward(self, x):
-        # one call == one BatchNorm batch, like the reference's breath_block(x[i])
-        return self.forward_windows(x, x.shape[0])
+        return h
 
 
 def resnet18(pretrained=False, **kwargs):

@@ -15,7 +15,7 @@ from collections import OrderedDict
 import torch.nn as nn
 
 from .. import functional as F_
-from .resnet import _require_cuda
+from .backbone import Backbone
 
 
 class SEModule(nn.Module):
@@ -28,6 +28,18 @@ class SEModule(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.fc2 = nn.Conv1d(channels // reduction, channels, kernel_size=1, padding=0)
         self.sigmoid = nn.Sigmoid()
+
+
+def _se_block(blk, x, R, units, family):
+    """F_.SEBlockFunction on block ``blk``: ``units`` = its (conv, BatchNorm, precise) in order, ``family`` its gate kernels'."""
+    ds, se = blk.downsample, blk.se_module
+    params = [t for conv, bn, _ in units for t in (conv.weight, bn.weight, bn.bias)]
+    params += [se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias]
+    if ds is not None:
+        params += [ds[0].weight, ds[1].weight, ds[1].bias]
+    return F_.SEBlockFunction.apply(x, blk.stride, R, family,
+                                    [(conv.kernel_size[0], precise, F_.BNState(bn)) for conv, bn, precise in units],
+                                    None if ds is None else F_.BNState(ds[1]), *params)
 
 
 class SEBasicBlock(nn.Module):
@@ -54,13 +66,8 @@ class SEBasicBlock(nn.Module):
         self.stride = stride
 
     def forward_rlc(self, x, R):
-        """x: (rows, L, C) channels-last; R rows per BatchNorm window."""
-        ds, se = self.downsample, self.se_module
-        dsw = (None, None, None, None) if ds is None else (ds[0].weight, ds[1].weight, ds[1].bias, F_.BNState(ds[1]))
-        return F_.SEBasicBlockFunction.apply(
-            x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias,
-            se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias, dsw[0], dsw[1], dsw[2], self.stride, R,
-            F_.BNState(self.bn1), F_.BNState(self.bn2), dsw[3])
+        """x: (rows, L, C) channels-last; R rows per BatchNorm window.  The gate stays on the narrow kernels at every width."""
+        return _se_block(self, x, R, ((self.conv1, self.bn1, True), (self.conv2, self.bn2, True)), F_.H.SE_NARROW)
 
 
 class SEResNetBottleneck(nn.Module):
@@ -92,19 +99,16 @@ class SEResNetBottleneck(nn.Module):
 
     def forward_rlc(self, x, R):
         """x: (rows, L, C) channels-last; R rows per BatchNorm window."""
-        ds, se = self.downsample, self.se_module
-        dsw = (None, None, None, None) if ds is None else (ds[0].weight, ds[1].weight, ds[1].bias, F_.BNState(ds[1]))
-        return F_.SEBottleneckFunction.apply(
-            x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias,
-            self.conv3.weight, self.bn3.weight, self.bn3.bias, se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias,
-            dsw[0], dsw[1], dsw[2], self.stride, R, F_.BNState(self.bn1), F_.BNState(self.bn2), F_.BNState(self.bn3), dsw[3])
+        fc1 = self.se_module.fc1
+        return _se_block(self, x, R, ((self.conv1, self.bn1, False), (self.conv2, self.bn2, True), (self.conv3, self.bn3, False)),
+                         F_.H.se_gate_family(fc1.in_channels, fc1.out_channels))
 
 
-class SENet(nn.Module):
+class SENet(Backbone):
     """Four stages of SEBasicBlocks or SEResNetBottlenecks behind layer0 = conv k7 s2 -> BN -> ReLU -> MaxPool1d(3, 2, ceil_mode=True).  The module
     tree (names, order, shapes) is the reference's (senet.py:219-289)."""
 
-    fused_tail = True     # forward_windows(pooled='fused'): the 7-position map, which the head pools
+    f32_only = ('SE-ResNets', 'the SE tail has no bf16 / f32x3p forms')
 
     def __init__(self, block, layers, groups, reduction, dropout_p=0.2, inplanes=128, input_3x3=True, downsample_kernel_size=3,
                  downsample_padding=1):
@@ -146,17 +150,15 @@ class SENet(nn.Module):
         stage += [block(self.inplanes, planes, groups, reduction) for _ in range(1, blocks)]
         return nn.Sequential(*stage)
 
+    def final_length(self, l):
+        cur = F_.H.pool_out_len(l // 2, F_.POOL_MAX_CEIL)          # layer0: conv s2, then the ceil-mode pool
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            cur = (cur - 1) // layer[0].stride + 1
+        return cur
+
     def _map(self, x, rows_per_window):
         """The last block's map (rows, L / 32, 512 * block.expansion) channels-last."""
-        if F_.conv_dtype() != 'f32' or F_.storage_dtype() != 'f32':
-            raise NotImplementedError("the SE-ResNets run with conv arithmetic 'f32' and float storage only (got %s / %s): the SE "
-                                      'tail has no bf16 / f32x3p forms' % (F_.conv_dtype(), F_.storage_dtype()))
-        _require_cuda(x, 'SENet')
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError('expected (rows, 1, L) input, got %s' % (tuple(x.shape),))
         rows, _, l = x.shape
-        if rows % rows_per_window:
-            raise ValueError('rows not a multiple of rows_per_window')
         l0 = self.layer0
         h = F_.StemFunction.apply(x.contiguous().float().view(rows, l), l0.conv1.weight, l0.bn1.weight, l0.bn1.bias,
                                   rows_per_window, F_.POOL_MAX_CEIL, F_.BNState(l0.bn1), False)
@@ -165,31 +167,15 @@ class SENet(nn.Module):
                 h = blk.forward_rlc(h, rows_per_window)
         return h
 
-    def forward_windows(self, x, rows_per_window, pooled=True):
-        """x: (rows, 1, L) with rows = windows * rows_per_window; BatchNorm statistics are taken per window, exactly as when
-        the reference feeds one (NB, 1, L) window at a time.  pooled=False or 'fused': the last map (rows, 7, C) itself, for a
-        head that pools it in its own kernel; pooled=True: the pooled features."""
-        h = self._map(x, rows_per_window)
-        if h.shape[1] < 7:
-            raise ValueError('AvgPool1d(7, stride=1) needs a final length >= 7 (seq_len >= 224); got %d' % h.shape[1])
-        if pooled == 'fused' or not pooled:
-            if h.shape[1] != 7:
-                raise TypeError('the un-pooled map is only handed out at the 7-position length the fused head pools')
-            return h
-        return F_.GlobalAvgPoolFunction.apply(h)
-
     def features(self, x):
         """layer0 .. layer4 of one BatchNorm batch: the last map in the reference's (N, C, L) layout (senet.py:311-317)."""
+        self.check_input(x, x.shape[0])
         return self._map(x, x.shape[0]).permute(0, 2, 1)
 
     def logits(self, x):
         """AvgPool1d(7, stride=1) of an (N, C, L) map (senet.py:319-323; there is no dropout on this path)."""
         n, c, _ = x.shape
         return F_.GlobalAvgPoolFunction.apply(x.permute(0, 2, 1).contiguous()).view(n, c, -1)
-
-    def forward(self, x):
-        # one call == one BatchNorm batch, like the reference's breath_block(x[i]) (senet.py:325-328: logits(features(x)).squeeze())
-        return self.forward_windows(x, x.shape[0])
 
 
 def se_resnet18():

@@ -66,20 +66,18 @@ class CNNLinearNetwork(_WindowHead):
         pool, view(-1), linear_final, the loss and its first gradient -- as ONE autograd node in two launches
         (functional.HeadLossFunction); ``loss.backward()`` then runs the whole backward.  With gradients required the
         two returned tensors are FILLED BY THAT BACKWARD (its first kernel derives them from the forward's partial dot
-        products): read them after it; under no_grad they are complete on return.  None when the breath block's last
-        map is not the 7-position one the fused head pools (seq_len != 224 cannot happen here; a backbone without
-        ``forward_windows(..., pooled=False)``): the caller then takes forward() + the loss kernels."""
+        products): read them after it; under no_grad they are complete on return.  None -- before the breath block
+        runs -- when it has no operand for the fused head at this length (Backbone.head_operand_kind): the caller then takes
+        forward() + the loss kernels."""
         if x.shape[-1] != SEQ_LEN:
             raise Exception('input breaths must have sequence length of 224')
         if x.shape[0] == 0:
             raise IndexError('index 0 is out of bounds for dimension 0 with size 0')
         self._no_metadata(self.metadata_features)
         b, nb, c, l = x.shape
-        try:       # ('fused': a backbone whose last block can pool for the head hands over (rows, F) features instead of the map)
-            hmap = self.breath_block.forward_windows(x.reshape(b * nb, c, l), nb,
-                                                     pooled='fused' if getattr(self.breath_block, 'fused_tail', False) else False)
-        except TypeError:
+        if self.breath_block.head_operand_kind(l) is None:
             return None
+        hmap = self.breath_block.head_operand(x.reshape(b * nb, c, l), nb)       # the 7-position map, or (rows, F) features
         return F_.head_loss(hmap, self.linear_final.weight, self.linear_final.bias, target, nb)
 
 

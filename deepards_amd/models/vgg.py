@@ -15,7 +15,7 @@ import math
 import torch.nn as nn
 
 from .. import functional as F_
-from .resnet import _require_cuda
+from .backbone import Backbone, HEAD_FLAT
 
 # (channels, pooled) of every stage, by the reference's configuration letter (vgg.py:53-55): A = vgg11, B = vgg13
 STAGES = {
@@ -66,11 +66,11 @@ def init_like_reference(net):
             m.bias.data.zero_()
 
 
-class VGG(nn.Module):
+class VGG(Backbone):
     """``features`` -> ``avgpool`` (AdaptiveAvgPool1d(7)) -> view(N, -1) (vgg.py:20-24): (N, 1, L) -> (N, 3584), feature
     c * 7 + i.  ``features``: what make_layers builds."""
 
-    fused_tail = True     # forward_windows(pooled='fused'): the (rows, 3584) features, which the head takes as they are
+    f32_only = ('VGG nets', 'the pooled stages have no bf16 / f32x3p forms')
     POOLED_LEN = 7
 
     def __init__(self, features, init_weights=True):
@@ -99,15 +99,7 @@ class VGG(nn.Module):
 
     def _map(self, x, rows_per_window):
         """The last stage's map (rows, L / 32, 512) channels-last."""
-        if F_.conv_dtype() != 'f32' or F_.storage_dtype() != 'f32':
-            raise NotImplementedError("the VGG nets run with conv arithmetic 'f32' and float storage only (got %s / %s): the pooled "
-                                      'stages have no bf16 / f32x3p forms' % (F_.conv_dtype(), F_.storage_dtype()))
-        _require_cuda(x, 'VGG')
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError('expected (rows, 1, L) input, got %s' % (tuple(x.shape),))
         rows, _, l = x.shape
-        if rows % rows_per_window:
-            raise ValueError('rows not a multiple of rows_per_window')
         h = x.contiguous().float().view(rows, l)
         for k, (conv, bn, pooled) in enumerate(self.stages()):
             if pooled and h.shape[1] < 2:
@@ -116,17 +108,20 @@ class VGG(nn.Module):
                                           k == 0, bool(getattr(conv, 'precise_conv', False)))
         return h
 
+    def head_operand_kind(self, seq_len):
+        return HEAD_FLAT
+
+    def head_operand(self, x, rows_per_window):
+        return self.forward_windows(x, rows_per_window)
+
     def forward_windows(self, x, rows_per_window, pooled=True):
         """x: (rows, 1, L) with rows = windows * rows_per_window; BatchNorm statistics are taken per window, exactly as when
-        the reference feeds one (NB, 1, L) window at a time.  -> (rows, 3584) features, for pooled=True and for 'fused' (the
-        head's flat form takes them); there is no un-pooled map to hand out (pooled=False: TypeError)."""
-        if pooled is False:
+        the reference feeds one (NB, 1, L) window at a time.  -> (rows, 3584) features (a fused head's flat form takes them as
+        they are); there is no un-pooled map to hand out (pooled=False: TypeError)."""
+        if not pooled:
             raise TypeError('VGG has no un-pooled map: its features are the flattened AdaptiveAvgPool1d(7) output')
+        self.check_input(x, rows_per_window)
         return F_.AdaptiveAvgPoolFlatFunction.apply(self._map(x, rows_per_window), self.avgpool.output_size)
-
-    def forward(self, x):
-        # one call == one BatchNorm batch, like the reference's breath_block(x[i]) (vgg.py:20-24)
-        return self.forward_windows(x, x.shape[0])
 
 
 def _vgg(name, cfg):

@@ -276,8 +276,7 @@ class HotPathTrainer(object):
             else float(loss_param)
         self._plain_bce = loss == 'bce' and loss_calc == 'all_breaths' and not carry_state
         self._carry = self._flag = None    # (2, 2H): row 0 zeros, row 1 the carried [hx | cx]; the step's row index
-        bb_name = str(getattr(getattr(model, 'breath_block', None), 'network_name', ''))
-        if self.eval_test and bb_name.startswith(('resnet', 'se_resnet', 'vgg')):     # (BatchNorm with running statistics)
+        if self.eval_test and getattr(getattr(model, 'breath_block', None), 'running_stats', False):   # (Backbone class data)
             raise NotImplementedError('eval_test on a ResNet / VGG breath block means inference on running statistics, which this '
                                       'package does not have')
         self.model = model

@@ -142,7 +142,7 @@ class BaseTraining(object):
             self._prev_dtypes = (F_.conv_dtype(), F_.storage_dtype())
             F_.set_conv_dtype(args.conv_dtype)
             # BASELINE's bf16 configs: bf16 storage too where the network has bf16 kernels throughout (the ResNets)
-            if args.conv_dtype == 'bf16' and str(args.base_network).startswith('resnet') and \
+            if args.conv_dtype == 'bf16' and getattr(M.backbone_class(args.base_network), 'bf16_storage', False) and \
                     getattr(args, 'act_dtype', None) != 'f32':
                 F_.set_storage_dtype('bf16')
         self.results = Results()
@@ -171,12 +171,8 @@ class BaseTraining(object):
         if a.load_base_network:
             from .checkpoint import load_base_network
             base_network = load_base_network(a.load_base_network, base_networks, kw)
-        elif a.base_network.startswith('resnet'):
-            base_network = base_networks[a.base_network](**kw['resnet_kwargs'])
-        elif a.base_network.startswith(('se_', 'vgg')):
-            base_network = base_networks[a.base_network]()
         else:
-            base_network = base_networks[a.base_network](**kw['densenet_kwargs'])
+            base_network = M.build_base_network(a.base_network, kw)
         if _flag(a, 'freeze_base_network'):
             for p in base_network.parameters():
                 p.requires_grad = False
@@ -636,7 +632,7 @@ class CNNLSTMModel(PerBreathClassifierMixin, BaseTraining, PatientClassifierMixi
     carries_lstm_state = True
 
     def __init__(self, args):
-        if str(args.base_network).startswith(('resnet', 'se_resnet', 'vgg')):
+        if getattr(M.backbone_class(args.base_network), 'running_stats', False):
             raise NotImplementedError('cnn_lstm with a ResNet / VGG base network: its test epoch runs under model.eval() '
                                       '(train_ards_detector.py:861), i.e. BatchNorm inference on running statistics, which '
                                       'is not implemented here; use a DenseNet base network')

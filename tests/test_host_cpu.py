@@ -961,3 +961,86 @@ def test_wgrad_padded_width_follows_the_instantiated_tile_pairs():
     assert 0 < padded < 17 * 17
     assert (q(96, 64), q(224, 64), q(32, 32), q(160, 128), q(64, 96), q(512, 512)) == (128, 256, 128, 160, 128, 512)
     assert q(48, 64) == -1 and q(64, 48) == -1 and q(0, 64) == -1
+
+
+class _StubBackbone(torch.nn.Module):
+    """A breath block that only answers the fused head's questions: ``kind`` is what it reports for every sequence length, and
+    handing anything over -- by the head-operand method or by forward_windows -- counts a run and raises TypeError('boom')."""
+    n_out_filters = 4
+
+    def __init__(self, kind):
+        torch.nn.Module.__init__(self)
+        self.kind, self.runs = kind, 0
+
+    def head_operand_kind(self, seq_len):
+        return self.kind
+
+    def head_operand(self, x, rows_per_window):
+        return self.forward_windows(x, rows_per_window, pooled=False)
+
+    def forward_windows(self, x, rows_per_window, pooled=True):
+        self.runs += 1
+        raise TypeError('boom')
+
+
+def test_fused_head_lets_a_type_error_from_the_backbone_through():
+    import deepards_amd.models as M
+    bb = _StubBackbone(M.HEAD_MAP)
+    with pytest.raises(TypeError, match='boom'):
+        M.CNNLinearNetwork(bb, 2, 0).forward_loss(torch.zeros(3, 2, 1, 224), torch.zeros(3, 2))
+    assert bb.runs == 1
+
+
+def test_fused_head_asks_before_the_backbone_runs():
+    import deepards_amd.models as M
+    bb = _StubBackbone(None)
+    assert M.CNNLinearNetwork(bb, 2, 0).forward_loss(torch.zeros(3, 2, 1, 224), torch.zeros(3, 2)) is None
+    assert bb.runs == 0
+
+
+# name -> (BatchNorm keeps running statistics, keyword group of the driver's build arguments, bf16 storage under conv dtype
+# bf16): what the name-prefix rules of the trainer, the driver and the checkpoint loader gave before the table took over
+_BACKBONE_DATA = {
+    'resnet18': (True, 'resnet_kwargs', True), 'resnet34': (True, 'resnet_kwargs', True),
+    'densenet18': (False, 'densenet_kwargs', False), 'densenet121': (False, 'densenet_kwargs', False),
+    'densenet169': (False, 'densenet_kwargs', False), 'densenet201': (False, 'densenet_kwargs', False),
+    'se_resnet18': (True, None, False), 'se_resnet50': (True, None, False), 'se_resnet101': (True, None, False),
+    'se_resnet152': (True, None, False), 'vgg11': (True, None, False), 'vgg13': (True, None, False),
+}
+
+
+def test_backbone_table_holds_what_the_name_prefixes_said():
+    import deepards_amd.models as M
+    assert set(M.base_networks) == set(_BACKBONE_DATA) == set(M.BACKBONES)
+    for name in M.base_networks:
+        factory, cls, group = M.BACKBONES[name]
+        assert factory is M.base_networks[name] and cls is M.backbone_class(name) and issubclass(cls, M.Backbone), name
+        assert (cls.running_stats, group, cls.bf16_storage) == _BACKBONE_DATA[name], name
+    assert M.backbone_class('resnet50') is None
+    for name in ('resnet18', 'densenet18', 'se_resnet18', 'vgg11'):              # the instance reads the same data
+        bb = M.base_networks[name]()
+        assert type(bb) is M.backbone_class(name)
+        assert (bb.running_stats, bb.bf16_storage) == (_BACKBONE_DATA[name][0], _BACKBONE_DATA[name][2]), name
+        assert not list(M.Backbone().state_dict()) and bb.head_operand_kind(224) == (M.HEAD_FLAT if name == 'vgg11' else M.HEAD_MAP)
+        assert bb.head_operand_kind(256) == (M.HEAD_FLAT if name == 'vgg11' else None)
+
+
+def test_driver_and_checkpoint_loader_build_through_one_function(monkeypatch, tmp_path):
+    import deepards_amd.models as M
+    from deepards_amd import checkpoint as C
+    from deepards_amd import train_ards_detector as T
+    calls = []
+
+    def build(name, build_args=None):
+        calls.append((name, build_args))
+        return torch.nn.Linear(1, 1, bias=False)
+    monkeypatch.setattr(M, 'build_base_network', build)
+    drv = object.__new__(T.network_map['cnn_linear'])           # (the constructor needs a device; get_base_network does not)
+    drv.args = T.make_args(base_network='se_resnet50')
+    assert isinstance(drv.get_base_network(), torch.nn.Linear)
+    assert calls == [('se_resnet50', drv._base_network_kwargs())]
+    path = str(tmp_path / 'sd.pth')
+    torch.save({'breath_block.weight': torch.full((1, 1), 3.0), 'linear_final.bias': torch.zeros(2)}, path)
+    kw = {'base_network': 'vgg13', 'resnet_kwargs': {'initial_planes': 128}}
+    net = C.load_base_network(path, M.base_networks, kw)
+    assert calls[1:] == [('vgg13', kw)] and float(net.weight.detach()) == 3.0

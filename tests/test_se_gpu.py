@@ -1,4 +1,4 @@
-"""The se_resnet18 backbone on the GPU: the five SE-tail kernels (csrc/se.hip), the chained SEBasicBlockFunction, the
+"""The se_resnet18 backbone on the GPU: the five SE-tail kernels (csrc/se.hip), the chained SEBlockFunction on an SEBasicBlock, the
 ceil-mode stem pool (csrc/stem_pool.hip, pool_mode 2), the whole model, the trainer and the driver.
 
 Bound per tensor (the one of tests/test_transformer_gpu.py): rel-l2 against the float64 oracle <= min(max(4 err32, 16 2^-23),
@@ -254,7 +254,7 @@ BLOCK_TAGS = ['id_6x3x7x64', 'id_4x2x56x64', 'id_5x5x7x512', 'id_4x2x5x512', 's2
 @pytest.mark.parametrize('winograd', [True, False], ids=['default', 'DA_WINOGRAD=0'])
 @pytest.mark.parametrize('tag', BLOCK_TAGS)
 def test_chained_block_function(H, M, tag, winograd):
-    """SEBasicBlockFunction (identity and stride-2 entries) through the module, forward and backward, against the oracle at
+    """SEBlockFunction on an SEBasicBlock (identity and stride-2 entries) through the module, forward and backward, against the oracle at
     the golden's err32; the ReLU decisions of the output must be the oracle's.  Then the same block inside a training step
     with gradient destinations on every parameter (the batched weight-gradient launch, the queued folds, the SE parameters
     written in place): the destinations hold the same gradients at the same bound.
@@ -317,6 +317,36 @@ def test_chained_block_function(H, M, tag, winograd):
     w = x.shape[0] // R_
     assert int(blk.bn2.num_batches_tracked) == 2 * w == int(blk.bn1.num_batches_tracked)       # (two forwards)
     assert torch.isfinite(blk.bn2.running_var).all() and float((blk.bn2.running_mean != 0).float().mean()) > 0.9
+
+
+def test_basic_block_gate_stays_narrow_at_512_32(H, M, monkeypatch):
+    """An SEBasicBlock of 512 planes with reduction 16 has the gate (C, Cr) = (512, 32): the one shape both kernel families take
+    at which H.se_gate_family names the wide one (se_ops.WIDE_SHARED, timed for the bottleneck).  The basic block names its
+    family itself: forward and backward run the narrow gate kernels and never the wide ones."""
+    from deepards_amd import functional as F_
+    assert H.se_gate_family(512, 32) == H.SE_WIDE and H.se_narrow_ok(512, 32)
+    calls = {}
+
+    def counted(name):
+        fn = getattr(H, name)
+
+        def wrapper(*a, **kw):
+            calls[name] = calls.get(name, 0) + 1
+            return fn(*a, **kw)
+        return wrapper
+    names = ('se_gate_fwd', 'se_wide_gate_fwd', 'se_gate_bwd', 'se_wide_gate_bwd')
+    for n in names:
+        monkeypatch.setattr(H, n, counted(n))
+    assert F_.H is H
+    torch.manual_seed(11)
+    blk = M.SEBasicBlock(512, 512, 1, 16).cuda().train()
+    x = torch.randn(2, 3, 512, device='cuda').requires_grad_(True)             # (rows 2, L 3, C 512), one window of R = 2 rows
+    out = blk.forward_rlc(x, 2)
+    out.backward(torch.randn_like(out))
+    torch.cuda.synchronize()
+    assert calls == {'se_gate_fwd': 1, 'se_gate_bwd': 1}, calls
+    assert tuple(out.shape) == (2, 3, 512) and torch.isfinite(out).all() and torch.isfinite(x.grad).all()
+    assert all(q.grad is not None and torch.isfinite(q.grad).all() for q in blk.parameters())
 
 
 # ---- memory discipline ----------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The se_resnet50 / 101 / 152 backbones on the GPU: the wide SE-tail kernels (csrc/se_wide.hip), the chained
-SEBottleneckFunction, the whole model, the trainer and the driver.
+SEBlockFunction on the bottleneck, the whole model, the trainer and the driver.
 
 Bound per tensor (the one of tests/test_se_gpu.py): rel-l2 against the float64 oracle <= min(max(4 err32, 16 2^-23), 1e-4),
 err32 = the reference's own fp32-against-fp64 rel-l2 from the golden where the shape has one, else tests/tools/sebn_ref.py
@@ -393,7 +393,7 @@ def block_ref(tag):
 @pytest.mark.parametrize('winograd', [True, False], ids=['default', 'DA_WINOGRAD=0'])
 @pytest.mark.parametrize('tag', BLOCK_TAGS)
 def test_chained_block_function(H, M, tag, winograd):
-    """SEBottleneckFunction (identity blocks, the stride-1 entry of layer1 and the stride-2 entries) through the module, forward
+    """SEBlockFunction on an SEResNetBottleneck (identity blocks, the stride-1 entry of layer1 and the stride-2 entries) through the module, forward
     and backward, against the oracle at the golden's err32; the output's ReLU decisions must be the oracle's.  Then the same
     block inside a training step with gradient destinations on every parameter (the batched weight-gradient launch, the queued
     folds, the SE parameters written in place): the destinations hold the same gradients at the same bound."""
