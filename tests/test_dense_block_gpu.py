@@ -1,7 +1,8 @@
 """The dense block as one design (deepards_amd/functional.py DenseBlockFunction; csrc: conv1x1_bn_kernel, the wgrad operand
 forms, bn_bwd_fused_kernel<EXT>, the Winograd kernel's dropout epilogue) against oracle/np_ref.py (fp64) -- reference
 models/densenet.py:18-44 (_DenseLayer), :46-66 (_DenseBlock), :68-81 (_Transition).  Kernel tolerances are those of the
-kernels these replace (tests/test_hip_ops_gpu.py: 2e-6 ... 2e-5 of the scale)."""
+kernels these replace (tests/test_hip_ops_gpu.py: 2e-6 ... 2e-5 of the scale).
+The shapes here are those of nb = 20; the window, tile and record edges are in tests/test_dense_edges_gpu.py."""
 import os
 import sys
 
