@@ -1783,3 +1783,4 @@ from .se_ops import (pool_out_len, se_stats, se_gate_fwd, se_scale_fwd, se_bwd_r
 from .se_ops import NARROW as SE_NARROW, WIDE as SE_WIDE        # noqa: E402,F401
 from .vgg_ops import (vgg_stats, bn_relu_maxpool2_fwd, bn_relu_maxpool2_bwd, bn_mean_bias,   # noqa: E402,F401
                       adaptive_avgpool_flat_fwd, adaptive_avgpool_flat_bwd)
+from .gradcam_ops import GradCamOutputs, gradcam, gradcam_shape_ok, gradcam_workspace   # noqa: E402,F401

@@ -629,6 +629,32 @@ int da_adaptive_avgpool_flat_bwd(const float* dfeat, float* dx, int rows, int Li
 
 int da_gather_rows(const float* src, const int64_t* idx, float* out, int B, int width, da_stream_t stream);
 
+/* ---- batched Grad-CAM of a cnn_linear + DenseNet model from the norm5 map alone (gradcam.py:28-205) ----------------------
+ * Behind `features` the head is relu -> AvgPool1d(Lm) -> view(-1) -> linear_final, so the guided gradient is closed form,
+ * d out[k] / d F[n][l][c] = (F[n][l][c] > 0) W[k][n C + c] / Lm, and every CAM is a reduction over the map:
+ *     P[n][c] = (1 / Lm) sum_l max(F, 0)        logits[k] = bias[k] + sum_{n,c} W[k][n C + c] P[n][c]
+ *     m[n][c] = #{l : F[n][l][c] > 0}           wr_k[n][c] = W[k][n C + c] m[n][c] / Lm^2        ww_k[c] = (1 / NB) sum_n wr_k[n][c]
+ *     R_k[n][l] = sum_c wr_k[n][c] F[n][l][c]   (generate_read_cam)        A_k[l] = sum_c ww_k[c] (1 / NB) sum_n F[n][l][c]   (generate_cam)
+ * F (B NB, Lm, C) float, channels-last, WITHOUT the final ReLU; W (2, NB C), bias (2); target_in (B) int: 0 / 1 (any other
+ * value >= 0 counts as 1) selects the class, < 0 the arg-max of logits (the first maximum, as np.argmax).  Outputs, t = target[b]:
+ *     logits (B, 2), target (B) int, A (B, 2, Lm), R (B, 2, NB, Lm)                                    float
+ *     cam (B, Lm) = max(A_t, 0)                                                                       UnNormalizedCam
+ *     cam_maxmin (B, Lm), read_maxmin (B, NB, Lm): u = trunc(255 (r - min r) / (max r - min r)), r = max(v, 0) over l of A_t /
+ *         of each row of R_t (MaxMinNormCam.normalize); where max r == min r -- the reference divides 0 by 0 and casts the NaN,
+ *         which is platform-defined -- the bytes are 0 and cam_degenerate (B) / read_degenerate (B, NB) is 1 (else 0)
+ *     read_frac (B, NB, Lm): u = trunc(255 rt / (ro + rt)) of the ReLU'd target / other class read CAMs, 0 where ro + rt == 0
+ *         (FracTotalNormCam.normalize)
+ * Shapes (da_gradcam_shape_ok): C % 32 == 0, 32 <= C <= 1920, 1 <= NB <= 1024, 1 <= Lm <= 8, B >= 1, B NB Lm C < 2^31; anything
+ * else -> DA_EINVAL before any launch.  Two launches on `stream`, no atomics, no synchronisation, no allocation: every sum runs in
+ * an order fixed by (NB, Lm, C), so a window's outputs are the same bits in any batch at any position.  workspace:
+ * da_gradcam_workspace() bytes, written before it is read. */
+int da_gradcam_shape_ok(int NB, int Lm, int C);
+size_t da_gradcam_workspace(int B, int NB, int C);
+int da_gradcam(const float* F, const float* W, const float* bias, const int* target_in, int B, int NB, int Lm, int C,
+               float* workspace, float* logits, int* target, float* A, float* R, float* cam, unsigned char* cam_maxmin,
+               unsigned char* cam_degenerate, unsigned char* read_maxmin, unsigned char* read_degenerate,
+               unsigned char* read_frac, da_stream_t stream);
+
 /* ---- test epoch on the device: window predictions + per-patient vote table --------------------------------
  * CNNLinearModel._process_test_batch_results train_ards_detector.py:932-936 (outputs.argmax) and
  * DeepARDSResults.perform_patient_predictions metrics.py:572-604 (votes per pathology, pred_frac, majority). */
