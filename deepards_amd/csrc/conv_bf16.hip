@@ -318,7 +318,7 @@ struct ConvBf16GenArgs {
   int tap_split;
 };
 
-template <int SS, typename AT>
+template <int SS, typename AT, bool TWO>
 __device__ __forceinline__ void conv_bf16_gen_body(const ConvBf16GenArgs& a, const int tile, unsigned char* lds) {
   const AT* ax = reinterpret_cast<const AT*>(a.x);
   AT* ay = reinterpret_cast<AT*>(a.y);
@@ -401,15 +401,31 @@ __device__ __forceinline__ void conv_bf16_gen_body(const ConvBf16GenArgs& a, con
   const unsigned char* xfrag = Xs + (wm * 64 + frow) * CB_PITCH + kg * 16;
   const unsigned char* wfrag = Ws + (wn * 32 + frow) * CB_PITCH + kg * 16;
 
-  f32x16 acc[2];
+  // two sources (TWO: a launch that has such a job; only those pay for the registers): the first source's sums are set aside
+  // when the second source's K steps begin and added at the end -- the sum the two single-source launches give (the second
+  // accumulating onto the first's stored result), bit for bit with float storage
+  f32x16 acc[2], acc1[TWO ? 2 : 1];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+    for (int r = 0; r < 16; ++r) {
+      acc[mt][r] = 0.f;
+      if constexpr (TWO) acc1[mt][r] = 0.f;
+    }
 
   gload(0);
   for (int ks = 0; ks < ksteps; ++ks) {
     const int t0 = ks >= kc ? tsplit : 0, t1 = ks >= kc ? a.ntaps : tsplit;      // this step's taps
+    if constexpr (TWO) {
+      if (a.x2 && ks == kc) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          acc1[mt] = acc[mt];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+        }
+      }
+    }
     __syncthreads();
 #pragma unroll
     for (int p = 0; p < NXP; ++p) {
@@ -452,6 +468,9 @@ __device__ __forceinline__ void conv_bf16_gen_body(const ConvBf16GenArgs& a, con
         const int j = (int)((uint32_t)m - rq * (uint32_t)a.Lm);
         AT* o = ay + ((size_t)rq * a.Ldst + (size_t)j * a.dst_stride + a.dst_off) * a.ldy + n_blk + wn * 32 + frow;
         float v = acc[mt][r];
+        if constexpr (TWO) {
+          if (a.x2) v += acc1[mt][r];
+        }
         if (a.accumulate) v += Act<AT>::ld1(o);
         Act<AT>::st1(o, v);
       }
@@ -467,13 +486,24 @@ struct ConvBf16GenTable {
   int n;
 };
 
-template <int SS, typename AT>
+template <int SS, typename AT, bool TWO = false>
 __global__ __launch_bounds__(256) void conv_bf16_gen_kernel(ConvBf16GenTable t) {
   constexpr int XBYTES = (SS == 2 ? 2 * (CB_TM + 1) : SS * (CB_TM - 1) + 3) * CB_PITCH;
   __shared__ __attribute__((aligned(16))) unsigned char lds[XBYTES + 3 * CB_TN * CB_PITCH];
   int i = 0;
   while (i + 1 < t.n && (int)blockIdx.x >= t.first_block[i + 1]) ++i;      // wave-uniform
-  conv_bf16_gen_body<SS, AT>(t.d[i], xcd_chunked(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
+  conv_bf16_gen_body<SS, AT, TWO>(t.d[i], xcd_chunked(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
+}
+
+// The launch with a two-source job at source stride 1 (a stride-2 block entry's data gradients in one launch): the second set
+// of accumulators fits 3 waves a SIMD when the compiler is held to it (168 registers; left alone it takes 200 and 2 waves)
+template <typename AT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_bf16_gen_two_kernel(ConvBf16GenTable t) {
+  constexpr int XBYTES = (CB_TM - 1 + 3) * CB_PITCH;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[XBYTES + 3 * CB_TN * CB_PITCH];
+  int i = 0;
+  while (i + 1 < t.n && (int)blockIdx.x >= t.first_block[i + 1]) ++i;      // wave-uniform
+  conv_bf16_gen_body<1, AT, true>(t.d[i], xcd_chunked(blockIdx.x - t.first_block[i], t.first_block[i + 1] - t.first_block[i]), lds);
 }
 
 // wf[t][co][ci] = bf16(w[co][ci][t]) (forward taps), wd[t][ci][co] = bf16(w[co][ci][2 - t]) (data-gradient taps)
@@ -1042,7 +1072,11 @@ int da_conv_bf16_multi(const da_conv_job* jobs, int n, hipStream_t stream) {
     if (!cnt) continue;
     t.n = cnt;
     t.first_block[cnt] = blocks;
-    if (ss == 1) DA_ACT_DISPATCH(hipLaunchKernelGGL((conv_bf16_gen_kernel<1, AT>), dim3((unsigned)blocks), dim3(256), 0, stream, t));
+    bool two = false;                             // a job of the launch contracts over two sources
+    for (int i = 0; i < cnt; ++i) two = two || t.d[i].x2 != nullptr;
+    if (two && ss == 1) DA_ACT_DISPATCH(hipLaunchKernelGGL((conv_bf16_gen_two_kernel<AT>), dim3((unsigned)blocks), dim3(256), 0, stream, t));
+    else if (two) DA_ACT_DISPATCH(hipLaunchKernelGGL((conv_bf16_gen_kernel<2, AT, true>), dim3((unsigned)blocks), dim3(256), 0, stream, t));
+    else if (ss == 1) DA_ACT_DISPATCH(hipLaunchKernelGGL((conv_bf16_gen_kernel<1, AT>), dim3((unsigned)blocks), dim3(256), 0, stream, t));
     else DA_ACT_DISPATCH(hipLaunchKernelGGL((conv_bf16_gen_kernel<2, AT>), dim3((unsigned)blocks), dim3(256), 0, stream, t));
     DA_CHECK_LAUNCH();
   }

@@ -462,7 +462,8 @@ def test_fresh_inputs_vs_numpy_oracle(M):
 @pytest.mark.parametrize('nb', [40, 8])
 def test_other_sub_batch_counts_vs_numpy_oracle(M, nb):
     """n_sub_batches other than 20 (BASELINE config C5 runs nb40; BatchNorm windows of 40 rows go through the 16-channel
-    single-pass kernels or the two-stage path, the head is F*NB wide): logits and loss against the oracle."""
+    single-pass kernels or the two-stage path, the head is F*NB wide): logits, loss and every parameter gradient of the eager
+    pass against the oracle (the gradients under the decisions the run took, as everywhere), then three trainer steps."""
     from deepards_amd.functional import bce_with_logits
     from deepards_amd.train import HotPathTrainer
     for backbone in ('resnet18', 'densenet18'):
@@ -473,14 +474,17 @@ def test_other_sub_batch_counts_vs_numpy_oracle(M, nb):
         model = model.cuda().train()
         x, t = seeded_batch(3, nb, 5, 'flow')
         ref = np_ref.cnn_linear_forward_backward({k: v.astype(np.float64) for k, v in p32.items()}, x.astype(np.float64),
-                                                 t.astype(np.float64), backbone=backbone, n_sub_batches=nb, need_grads=False)
+                                                 t.astype(np.float64), backbone=backbone, n_sub_batches=nb, need_grads=True)
         xt, tt = torch.from_numpy(x).cuda(), torch.from_numpy(t).cuda()
-        out = model(xt, None)
+        with tapped() as taps:
+            out = model(xt, None)
         loss = bce_with_logits(out, tt)
         loss.backward()
         err = np.abs(out.detach().cpu().numpy() - ref['logits']).max()
         log(backbone, 'nb=%d: logits err %.3e loss %.7f vs %.7f' % (nb, err, float(loss), ref['loss']))
         assert err < 1e-4 and abs(float(loss) - ref['loss']) < 1e-5
+        # (nb 40: twice the rows of the (3, 20) batches the default of 12 flips was set at)
+        assert_gradients_match(ref, grads64(model, ref), '%s nb=%d' % (backbone, nb), max_flips=12 * max(1, nb // 20), taps=taps)
         tr = HotPathTrainer(model, use_graph=True)
         assert all(np.isfinite(float(tr.train_step(xt, tt))) for _ in range(3))
 
