@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip.so')   # (override: A/B builds, scripts/)
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
-           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip']
+           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -205,6 +205,16 @@ SIGNATURES = {
     'da_gradcam_shape_ok': (_I, [_I] * 3),
     'da_gradcam_workspace': (_Z, [_I] * 3),
     'da_gradcam': (_I, [_P] * 4 + [_I] * 4 + [_P] * 12),
+    'da_bias_act_fwd': (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    'da_bias_act_bwd_workspace': (_Z, [_I, _I]),
+    'da_bias_act_bwd': (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    'da_proto_shape_ok': (_I, [_I] * 4),
+    'da_proto_row_tile': (_I, [_I, _I]),
+    'da_proto_fwd': (_I, [_P] * 6 + [_I] * 4 + [_P]),
+    'da_proto_bwd_workspace': (_Z, [_I] * 3),
+    'da_proto_bwd': (_I, [_P] * 8 + [_I, _P] + [_I] * 4 + [_P]),
+    'da_ppnet_loss': (_I, [_P] * 3 + [_I] * 3 + [_F] * 4 + [_P] * 4),
+    'da_grad_add_decay': (_I, [_P, _P, _Z, _F, _P]),
     'da_vote_counts': (_I, [_P, _P, _I, _I, _P, _P, _P]),
     'da_concat2': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _Z, _P]),
     'da_slice_copy': (_I, [_P, _I, _I, _P, _I, _I, _Z, _I, _P]),

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void linear2_fwd_kernel(const float* __restric
   }
   __syncthreads();
   if (threadIdx.x < 2) {
-    float s = bias[threadIdx.x];
+    float s = bias ? bias[threadIdx.x] : 0.f;             // (null: a layer without a bias, PPNet.last_layer)
     for (int k = 0; k < 4; ++k) s += red[threadIdx.x][k];
     logits[(size_t)b * 2 + threadIdx.x] = s;
   }
@@ -224,7 +224,7 @@ __device__ __forceinline__ void linear2_bwd_weight_block(const float* dl, const 
     }
     s0 = wave_sum(s0);
     s1 = wave_sum(s1);
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && dbias) {                    // (null: a layer without a bias)
       dbias[0] = accumulate ? dbias[0] + s0 : s0;
       dbias[1] = accumulate ? dbias[1] + s1 : s1;
     }
@@ -952,7 +952,7 @@ const void* da_hip_runtime_symbol(void) { return (const void*)&hipGetLastError; 
 int da_linear2_fwd(const float* flat, const float* W, const float* bias, float* logits, int B, int K,
                    hipStream_t stream) {
   DA_ENTER();
-  if (!flat || !W || !bias || !logits || K % 4) return DA_EINVAL;
+  if (!flat || !W || !logits || K % 4) return DA_EINVAL;          // bias may be null: Linear(K, 2, bias=False)
   if (B == 0) return DA_OK;
   hipLaunchKernelGGL(linear2_fwd_kernel, dim3(B), dim3(256), 0, stream, flat, W, bias, logits, K);
   DA_CHECK_LAUNCH();
@@ -1002,7 +1002,7 @@ int da_linear2_bwd(const float* dlogits, const float* flat, const float* W, floa
                        W, dflat, B, K);
     DA_CHECK_LAUNCH();
   }
-  if (dW && dbias) {
+  if (dW) {                                               // dbias may be null: a layer without a bias
     hipLaunchKernelGGL(linear2_bwd_weight_kernel, dim3((K / 4 + 15) / 16), dim3(256), 0, stream, dlogits, flat, dW,
                        dbias, B, K, accumulate);
     DA_CHECK_LAUNCH();

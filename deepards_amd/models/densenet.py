@@ -100,6 +100,10 @@ class _Features(nn.Sequential):
     HIP pipeline and returns the norm5 output in the reference's (N, C, L) layout WITHOUT the final ReLU, as
     ``nn.Sequential.__call__`` does there -- what gradcam.py:45 hooks."""
     drop_rate = 0.0
+    # True: a dense block runs as one DenseBlockFunction where its shape allows (_block_plan).  False (PPNet sets it on its
+    # breath block): always the per-layer Functions, whose BatchNorm statistics are taken window by window and not merged
+    # from tile records -- slower, but a window's map then has the same bits at any position of a batch.
+    block_kernels = True
 
     def forward_rlc(self, x, R, relu):
         """x: checked (rows, C_in, L) input (DenseNet.check_input) -> the norm5 output (rows, L', C) channels-last."""
@@ -127,6 +131,8 @@ class _Features(nn.Sequential):
         """[(block, its transition or None, length, C0, Cb)] when EVERY dense block of the network can run as one
         F_.DenseBlockFunction (one pitched buffer + one statistics table per block, see there), else None: the per-layer
         Functions below then take the whole network (other shapes, bf16 convs, DA_DENSE_BLOCK=0)."""
+        if not self.block_kernels:
+            return None
         mods = list(self.children())
         lb = ((l + 2 * 3 - 7) // 2 + 1 - 1) // 2 + 1            # conv0 k7 s2 p3, pool0 (3, 2, 1)
         c0 = self.conv0.out_channels

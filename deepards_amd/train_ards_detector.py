@@ -52,6 +52,7 @@ BUILD_DEFAULTS = dict(
     kfolds=None, only_fold=None, load_checkpoint=None, load_base_network=None, save_model=None, saved_models_dir=None,
     train_from_pickle=None, train_to_pickle=None, test_from_pickle=None, test_to_pickle=None,
     experiment_name='deepards_amd', config_override=None, folds_in_flight=None, fold_groups=None, transformer_blocks=2,
+    use_l1=None, average_linear_layer=None,
 )
 
 # make_args(): the merged view with every reference default, for callers that build ``args`` in Python
@@ -71,6 +72,8 @@ DEFAULTS = dict(
     test_to_pickle=None, stop_on_loss=False, stop_thresh=1.5, stop_after_epoch=1,
     train_store=None, test_store=None, test_patient_slot=None, use_graph=True, seed=None, conv_dtype=None, act_dtype=None,
     butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None, post_hoc_downsampling=None,
+    n_warm_epochs=3, push_start_epoch=6, push_every_n=6, n_push_iters=5, clust_lambda=0.8, sep_lambda=0.2, n_prototypes=10,
+    incorrect_strength=-0.5, use_l1=False, average_linear_layer=False, folds_in_flight=None,
 )
 
 
@@ -673,6 +676,118 @@ class CNNTransformerModel(PerBreathClassifierMixin, BaseTraining, PatientClassif
                                        self.args.time_series_hidden_units, 2 if blocks is None else blocks)
 
 
+class ProtoPNetModel(object):
+    """:1156-1371 for the trainer of ``deepards_amd.protopnet``: ``get_optimizer`` returns ONE ProtoPNetTrainer that holds the
+    reference's three optimisers as phases (warm / joint / last layer), ``calc_loss`` is the loss kernel, ``run_train_epoch``
+    carries the epoch schedule (:1255-1329) and the push.  Never clips (the reference's loops do not call the base class's
+    clipping, although the experiment files set clip_grad).  One GPU, the folds one after the other."""
+
+    def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
+        from .protopnet import ProtoPNetTrainer
+        a = self.args
+        if a.optimizer not in ('adam', 'sgd'):
+            raise ValueError('optimizer must be adam or sgd')
+        return ProtoPNetTrainer(model, optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
+                                clust_lambda=a.clust_lambda, sep_lambda=a.sep_lambda, use_l1=bool(_flag(a, 'use_l1')),
+                                world_size=world_size, rank=rank, process_group=process_group,
+                                use_graph=_flag(a, 'use_graph', True))
+
+    def calc_loss(self, model, cls_output, target, min_distances):
+        """-> loss, cls_loss, cluster_cost, separation_cost, l1 (:1194-1247), one launch (+ the l1 term with --use-l1)."""
+        from . import protopnet_ops as PO
+        w = mask = None
+        if _flag(self.args, 'use_l1'):
+            w = model.last_layer.weight
+            mask = (1 - torch.t(model.prototype_class_identity_linear_layer)).to(w.device)
+        nb = min_distances.shape[1] // model.num_prototypes
+        parts = PO.ppnet_loss(cls_output.detach().contiguous(), target.contiguous(), min_distances.detach().contiguous(), nb,
+                              model.num_prototypes, self.max_dist, self.args.clust_lambda, self.args.sep_lambda,
+                              want_grad=False, l1_weight=w, l1_mask=mask)[0]
+        return tuple(parts[i] for i in range(5))
+
+    def _process_test_batch_results(self, outputs, target, inputs, fold_num):
+        return outputs.argmax(dim=-1).cpu().tolist()
+
+    def _epoch_generator(self, fold_num, epoch_num, salt=0):
+        if self.args.seed is None:
+            return None
+        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + 100003 * salt)
+
+    def run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num):
+        """:1255-1329: the warm optimiser while epoch_num <= n_warm_epochs, the joint one after; from push_start_epoch on,
+        every push_every_n epochs, the push and n_push_iters last-layer passes over the training set."""
+        a = self.args
+        store, batch_size, shuffle = train_loader
+        if optimizer.model is not model:
+            raise ValueError('optimizer was built for another model')
+        optimizer.set_phase('warm' if epoch_num <= a.n_warm_epochs else 'joint')
+        for loss in run_train_epoch_from_store(optimizer, store, batch_size=batch_size, shuffle=shuffle,
+                                               generator=self._epoch_generator(fold_num, epoch_num)):
+            parts = optimizer.last_parts.clone()              # (the captured step's own buffer: the next replay refills it)
+            for i, name in ((1, 'cls_loss'), (2, 'clst_loss'), (3, 'sep_loss'), (4, 'l1_loss')):
+                self.results.update_meter(name, fold_num, parts[i])
+            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
+            self.results.update_meter('loss', fold_num, loss)
+            if _flag(a, 'debug'):
+                break
+        if epoch_num >= a.push_start_epoch and (epoch_num - a.push_start_epoch) % a.push_every_n == 0:
+            self.push_func(train_loader, model, epoch_num)
+            optimizer.set_phase('last_layer')
+            for it in range(a.n_push_iters):
+                for loss in run_train_epoch_from_store(optimizer, store, batch_size=batch_size, shuffle=shuffle,
+                                                       generator=self._epoch_generator(fold_num, epoch_num, it + 1)):
+                    self.results.update_meter('loss', fold_num, loss)
+                if _flag(a, 'debug'):
+                    break
+
+    def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
+        """:1331-1349: under model.eval(), the loss kernel, softmaxed outputs; the votes as in BaseTraining.run_test_epoch."""
+        made = optimizer is None
+        if made:
+            optimizer = self.get_optimizer(model)
+        res = BaseTraining.run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=optimizer,
+                                          _steps_only=_steps_only)
+        if made and not _steps_only:
+            optimizer.release_graphs()
+        return res
+
+
+class ProtoPNet1DModel(ProtoPNetModel, BaseTraining, PatientClassifierMixin):
+    """:1374-1391.  NOT in ``network_map`` (its key set is pinned, as for cnn_transformer; README.md, "Networks"): build it
+    directly, ``ProtoPNet1DModel(args).train_and_test()``.  The base network must be one of this package's DenseNets."""
+
+    def __init__(self, args):
+        if M.backbone_class(args.base_network) is not M.DenseNet:
+            raise NotImplementedError('protopnet needs a DenseNet base network (forward_no_pool exists only there), got %r'
+                                      % (args.base_network,))
+        if self._world_size() > 1:
+            raise NotImplementedError('protopnet runs on one GPU: its phases and the push are not sharded over ranks')
+        n_flight = getattr(args, 'folds_in_flight', None)
+        if n_flight is not None and int(n_flight) > 1:
+            raise NotImplementedError('--folds-in-flight > 1 with protopnet: the phase schedule and the push walk one fold at '
+                                      'a time; run the folds one after the other')
+        args.folds_in_flight = 1
+        super(ProtoPNet1DModel, self).__init__(args)
+
+    @staticmethod
+    def _world_size():
+        return int(os.environ.get('WORLD_SIZE', '1'))
+
+    def get_network(self, base_network):
+        a = self.args
+        model = M.construct_PPNet(base_network, sub_batch_size=a.n_sub_batches, prototype_shape=(a.n_prototypes * 2, 128, 1),
+                                  batch_size=a.batch_size, incorrect_strength=a.incorrect_strength,
+                                  average_linear=bool(_flag(a, 'average_linear_layer')))
+        self.max_dist = model.prototype_shape[1] * model.prototype_shape[2]
+        return model
+
+    def push_func(self, train_loader, model, epoch_num):
+        from .protopnet import push_prototypes
+        store, batch_size, _ = train_loader
+        self.last_push = push_prototypes(model, store, batch_size=batch_size)
+        return self.last_push
+
+
 network_map = {
     'cnn_lstm': CNNLSTMModel,
     'cnn_linear': CNNLinearModel,
@@ -687,10 +802,8 @@ OUT_OF_SCOPE_FLAGS = (
     '--transforms', '-tp', '--transform-probability', '--use-i', '-r2', '--drop-if-under-r2', '--drop-i-lim', '--drop-e-lim',
     '--truncate-e-lim', '--butter-low', '--post-hoc-downsampling', '--load-siamese', '--fl-gamma', '--fl-alpha',
     '--plot-untiled-disease-evol', '--plot-tiled-disease-evol', '--plot-dtw-with-disease', '--plot-pt-dtw-by-minute',
-    '--perform-dtw-preprocessing', '--n-warm-epochs', '-pse', '--push-start-epoch', '--push-every-n', '--n-push-iters',
-    '--clust-lambda', '--sep-lambda', '-vse', '--viz-start-epoch', '--viz-every-n', '--prototype-results-dir',
-    '--prototype-fname-prefix', '-np', '--n-prototypes', '-ic', '--incorrect-strength', '--average-linear-layer', '--use-l1',
-    '-2dt', '--two-dim-transforms', '-bks', '--block-kernel-size', '--multitask-epochs', '--row-mix', '-usf',
+    '--perform-dtw-preprocessing', '-vse', '--viz-start-epoch', '--viz-every-n', '--prototype-results-dir',
+    '--prototype-fname-prefix', '-2dt', '--two-dim-transforms', '-bks', '--block-kernel-size', '--multitask-epochs', '--row-mix', '-usf',
     '--undersample-factor', '-usdf', '--undersample-std-factor', '--train-pt-frac', '--final-validation',
     '--holdout-set-type', '--downsample-factor', '--bm-to-linear',
 )
@@ -727,7 +840,8 @@ def build_parser():
     true_false_flag('--debug', 'debug code and dont train')
     parser.add_argument('--optimizer', choices=['adam', 'sgd'])
     parser.add_argument('-dt', '--dataset-type', choices=['unpadded_centered_sequences', 'padded_breath_by_breath',
-                                                          'padded_breath_by_breath_with_flow_time_features'])
+                                                          'padded_breath_by_breath_with_flow_time_features',
+                                                          'unpadded_centered_with_bm'])
     parser.add_argument('-lr', '--learning-rate', type=float)
     parser.add_argument('--loader-threads', type=int, help='accepted and ignored: batches are gathered on the device')
     parser.add_argument('--save-model', help='save the model to a specific file')
@@ -770,6 +884,17 @@ def build_parser():
     parser.add_argument('--fft-filtering-low', type=float, help='FFT band filter: keep |f| above this (Hz); needs both bounds')
     parser.add_argument('--fft-filtering-high', type=float, help='FFT band filter: keep |f| below this (Hz); needs both bounds')
     true_false_flag('--bootstrap', '')
+    # protopnet (ProtoPNet1DModel; :1546-1560)
+    parser.add_argument('--n-warm-epochs', type=int, help='number of warm epochs to run with protopnet')
+    parser.add_argument('-pse', '--push-start-epoch', type=int, help='epoch to start the projection pushes')
+    parser.add_argument('--push-every-n', type=int, help='starting at push start, push every n epochs')
+    parser.add_argument('--n-push-iters', type=int, help='number of iterations to optimize last layer following push')
+    parser.add_argument('--clust-lambda', type=float, help='multiplier of cluster loss for protopnet')
+    parser.add_argument('--sep-lambda', type=float, help='multiplier of separation loss for protopnet')
+    parser.add_argument('-np', '--n-prototypes', type=int, help='number of prototypes to use per class in our model')
+    parser.add_argument('-ic', '--incorrect-strength', type=float, help='the incorrect strength value for the linear layer of protopnet')
+    true_false_flag('--average-linear-layer', 'protopnet: average like features over the breaths in front of the last layer')
+    true_false_flag('--use-l1', 'add an l1 regularization for ppnet')
     # this build's own switches
     parser.add_argument('--seed', type=int, help='seed of the initialisation, the shuffles and the oversampler')
     parser.add_argument('--no-graph', dest='use_graph', action='store_false', default=None, help='run the step eagerly')

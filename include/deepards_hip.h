@@ -422,7 +422,8 @@ int da_global_avgpool_bwd(const float* dfeat, da_act_t* dx, int lddx, int rows, 
 
 /* ---- head + loss ---------------------------------------------------------------------------
  * linear_final on view(-1) of the (NB,F) block: torch_cnn_linear_network.py:102,110-112 ;
- * BCEWithLogitsLoss (mean): train_ards_detector.py:530,929-930 */
+ * BCEWithLogitsLoss (mean): train_ards_detector.py:530,929-930
+ * bias / dbias may be null: a Linear(K, 2, bias=False) (PPNet.last_layer); with one, nothing changes. */
 int da_linear2_fwd(const float* flat, const float* W, const float* bias, float* logits, int B, int K,
                    da_stream_t stream);
 int da_bce_logits(const float* logits, const float* target, int n, float gscale, float* loss, float* dlogits,
@@ -654,6 +655,46 @@ int da_gradcam(const float* F, const float* W, const float* bias, const int* tar
                float* workspace, float* logits, int* target, float* A, float* R, float* cam, unsigned char* cam_maxmin,
                unsigned char* cam_degenerate, unsigned char* read_maxmin, unsigned char* read_degenerate,
                unsigned char* read_frac, da_stream_t stream);
+
+/* ---- the head of the 1-D ProtoPNet (models/protopnet1d/model.py:113-354; train_ards_detector.py:1194-1247) ----------------
+ * All float32; z is the map [rows][L][D] behind the add-on layers, channels innermost, rows = B NB.  No atomics: every sum
+ * runs in an order fixed by the shape, so a row's outputs are the same bits in any batch at any position.  Every entry returns
+ * DA_EINVAL on a shape it does not take, before any launch.
+ *
+ * da_bias_act_fwd   y[m][n] = act(x[m][n] + bias[n]); act 0: ReLU, 1: sigmoid; N % 4 == 0, N <= 4096 (the add-on layers'
+ *                   1x1 convolutions themselves are da_conv_gemm / da_conv_wgrad).  y may be x.
+ * da_bias_act_bwd   dx = dy act'(y) from the stored y (dx null: skipped; dx may be dy), dbias[n] (+)= sum_m dx[m][n] (null:
+ *                   skipped) through `workspace` (da_bias_act_bwd_workspace bytes, written before it is read).
+ * da_proto_fwd      dist[row][p][l] = sum_c (z[row][l][c] - protos[p][c])^2 in the DIRECT form (never negative; exactly 0 for a
+ *                   prototype that is bitwise a patch) -- null: not stored; min_d[row][p] = min_l, arg[row][p] the lowest l
+ *                   attaining it, sim = log((min_d + 1) / (min_d + 1e-4)).  D % 32 == 0 up to 512, 2 <= P <= 64, 1 <= L <= 64,
+ *                   rows >= 1, prototype kernel size 1.  da_proto_row_tile: the rows one block takes at (L, P).
+ * da_proto_bwd      g = dmin + dsim * d sim / d min_d (either of dsim, dmin [rows][P] may be null, not both: the similarity's
+ *                   derivative is folded in HERE, the loss's own min_d term comes in as dmin);
+ *                   dz[row][l][c] = sum_p 2 g (z - protos[p]) at l == arg[row][p], 0 elsewhere -- every element written (null:
+ *                   skipped); dprotos[p][c] (+)= sum_row 2 g (protos[p] - z[row][arg]) (null: skipped) through `workspace`
+ *                   (da_proto_bwd_workspace bytes).
+ * da_ppnet_loss     calc_loss without its l1 term: logits, target [B][2], min_d [B][NB P]; out[5] = total, cls, cluster,
+ *                   separation, 0; dlogits [B][2], dmin_d [B][NB P] (null: skipped; every element written); P even; gscale on
+ *                   the gradients only.  One launch. */
+int da_bias_act_fwd(const float* x, const float* bias, float* y, int M, int N, int act, da_stream_t stream);
+size_t da_bias_act_bwd_workspace(int M, int N);
+int da_bias_act_bwd(const float* dy, const float* y, float* dx, float* dbias, int accumulate, float* workspace, int M, int N,
+                    int act, da_stream_t stream);
+int da_proto_shape_ok(int rows, int L, int D, int P);
+int da_proto_row_tile(int L, int P);
+int da_proto_fwd(const float* z, const float* protos, float* dist, float* min_d, int* arg, float* sim, int rows, int L, int D,
+                 int P, da_stream_t stream);
+size_t da_proto_bwd_workspace(int rows, int D, int P);
+int da_proto_bwd(const float* dsim, const float* dmin, const float* min_d, const int* arg, const float* z, const float* protos,
+                 float* dz, float* dprotos, int accumulate, float* workspace, int rows, int L, int D, int P,
+                 da_stream_t stream);
+int da_ppnet_loss(const float* logits, const float* target, const float* min_d, int B, int NB, int P, float max_dist,
+                  float clust_lambda, float sep_lambda, float gscale, float* out, float* dlogits, float* dmin_d,
+                  da_stream_t stream);
+/* g[i] += weight_decay * p[i]: the L2 term torch.optim.Adam(weight_decay=...) adds to the gradient in front of its moments
+ * (da_clamp_adam* take no weight decay; the ProtoPNet optimisers, train_ards_detector.py:1163-1191, give Adam one). */
+int da_grad_add_decay(float* g, const float* p, size_t n, float weight_decay, da_stream_t stream);
 
 /* ---- test epoch on the device: window predictions + per-patient vote table --------------------------------
  * CNNLinearModel._process_test_batch_results train_ards_detector.py:932-936 (outputs.argmax) and
