@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip.so')   # (override: A/B builds, scripts/)
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
-           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip']
+           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -175,6 +175,13 @@ SIGNATURES = {
     'da_window_median_bwd': (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     'da_lstm_fwd': (_I, [_P] * 11 + [_I, _I, _I, _P]),
     'da_lstm_bwd': (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    'da_lstm_seq_block_seqs': (_I, [_I]),
+    'da_lstm_seq_fwd': (_I, [_P] * 5 + [_I] + [_P] * 3 + [_I, _I, _I, _P]),
+    'da_lstm_seq_bwd_workspace': (_Z, [_I, _I]),
+    'da_lstm_seq_bwd': (_I, [_P] * 14 + [_I] * 4 + [_P]),
+    'da_lstm_seq_proj_fwd': (_I, [_P] * 4 + [_I] * 3 + [_P]),
+    'da_lstm_seq_proj_bwd_workspace': (_Z, [_I] * 3),
+    'da_lstm_seq_proj_bwd': (_I, [_P] * 7 + [_I] * 4 + [_P]),
     'da_tfm_block_form': (_I, [_I, _I, _I, _IP, _IP, ctypes.POINTER(_Z), ctypes.POINTER(_Z)]),
     'da_tfm_block_fwd': (_I, [_P] * 9 + [_I] * 4 + [_P, _U, _U, _F, _P]),
     'da_tfm_block_bwd': (_I, [_P] * 17 + [_I] * 4 + [_P, _U, _U, _F, _P]),

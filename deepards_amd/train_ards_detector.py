@@ -788,6 +788,56 @@ class ProtoPNet1DModel(ProtoPNetModel, BaseTraining, PatientClassifierMixin):
         return self.last_push
 
 
+class LSTMOnlyModel(BaseTraining, PatientClassifierMixin):
+    """:1024-1040.  The network reads the raw waveform with an LSTM and has no CNN: no base network is built
+    (``get_base_network`` is not called, ``--base-network`` is ignored), so ``--load-base-network`` and
+    ``--freeze-base-network`` have nothing to act on and are refused.  Window-level (B, 2) outputs; the test epoch is
+    ``BaseTraining.run_test_epoch`` (no ``model.eval()``).  NOT in ``network_map`` (its key set is pinned, as for
+    cnn_transformer; README.md, "Networks"): build it directly, ``LSTMOnlyModel(args).train_and_test()``."""
+    clip_odd_batches = True
+
+    def __init__(self, args):
+        for flag in ('load_base_network', 'freeze_base_network'):
+            if _flag(args, flag, None):
+                raise ValueError('--%s with %s: the network has no base network (the LSTM reads the raw waveform), so there '
+                                 'is nothing to load into or freeze' % (flag.replace('_', '-'), type(self).__name__))
+        super(LSTMOnlyModel, self).__init__(args)
+
+    def calc_loss(self, outputs, target, inputs):
+        return self.criterion(outputs, target)
+
+    def _process_test_batch_results(self, outputs, target, inputs, fold_num):
+        return outputs.argmax(dim=-1).cpu().tolist()
+
+    def get_base_network(self):
+        raise RuntimeError('%s has no base network' % type(self).__name__)
+
+    def get_model(self):
+        """BaseTraining.get_model without a base network: ``get_network(None)``."""
+        if self.args.load_checkpoint:
+            from .checkpoint import load_model_weights
+            model = load_model_weights(self.args.load_checkpoint, lambda: self.get_network(None))
+        else:
+            if self.args.seed is not None:
+                torch.manual_seed(self.args.seed)
+            model = self.get_network(None)
+        return self.model_cuda_wrapper(model)
+
+    def _hidden_units(self):
+        h = getattr(self.args, 'time_series_hidden_units', None)
+        return 16 if h is None else h
+
+    def get_network(self, _):
+        return M.LSTMOnlyNetwork(self._hidden_units(), self.args.n_sub_batches)
+
+
+class LSTMOnlyWithPackingModel(LSTMOnlyModel):
+    """:1043-1059: LSTMOnlyModel on padded breath-by-breath datasets, whose padding is exactly 0.0."""
+
+    def get_network(self, _):
+        return M.LSTMOnlyWithPacking(self._hidden_units(), self.args.n_sub_batches)
+
+
 network_map = {
     'cnn_lstm': CNNLSTMModel,
     'cnn_linear': CNNLinearModel,

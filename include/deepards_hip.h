@@ -515,6 +515,31 @@ int da_lstm_fwd(const float* gx, const float* whh, const float* bih, const float
 int da_lstm_bwd(const float* dh_all, const float* whh, const float* hs, const float* cs, const float* gates,
                 const float* h0, const float* c0, float* dgates, float* dwhh_part, int B, int T, int H,
                 da_stream_t stream);
+/* ---- waveform LSTM of the lstm_only networks (reference models/lstm_only.py:8-69 LSTMOnlyNetwork, :72-124
+ * LSTMOnlyWithPacking): nn.LSTM(1, H, batch_first) over the T raw samples of each of N breath rows, zero initial state, gates
+ * i,f,g,o.  x [N][T], w_ih [4H] (the (4H, 1) weight), w_hh [4H][H], b_ih / b_hh [4H].  H a multiple of 8 in [8, 64], T >= 1,
+ * N >= 0; anything else: -1, outputs untouched.  There is no gx tensor and no stored gates: the forward keeps cs [N][T][H] and
+ * lens [N] (int) beside its output hs [N][T][H]; the backward recomputes the gates with the forward's own arithmetic.
+ * packed = 1 (LSTMOnlyWithPacking.pack_sequence, :100-113): step t of a row runs iff x[0] == 0 or no sample among
+ * x[0 .. t-1] equals zero (-0.0 counts); lens = the steps run; hs at t >= lens is +0.0 and dhs there is never read.
+ * packed = 0: lens = T.  Every sum runs in an order fixed by the shape; a sequence's hs does not depend on N or its index. */
+int da_lstm_seq_block_seqs(int H);      /* sequences one block works on (tests put N around it); -1 for a refused H */
+int da_lstm_seq_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int packed,
+                    float* hs, float* cs, int* lens, int N, int T, int H, da_stream_t stream);
+size_t da_lstm_seq_bwd_workspace(int N, int H);      /* bytes; 0 for a refused shape */
+/* dhs [N][T][H] -> dw_ih [4H], dw_hh [4H][H], db [4H] (serves both biases; db2, if not NULL, receives it too), (+)= when
+   accumulate; no input gradient */
+int da_lstm_seq_bwd(const float* dhs, const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                    const float* hs, const float* cs, const int* lens, float* dw_ih, float* dw_hh, float* db, float* db2,
+                    float* workspace, int accumulate, int N, int T, int H, da_stream_t stream);
+/* the per-breath projection linear_breath_inst = Linear(K = T H -> F) over the N rows (lstm_only.py:26,65): y [N][F] =
+ * hs [N][K] W [F][K]^T + bias.  K a multiple of 4, F a multiple of 16 up to 64; else -1.  The backward writes dhs [N][K] and
+ * dW [F][K], dbias [F] (+)= when accumulate, partial sums over chunks of 32 rows folded in chunk order. */
+int da_lstm_seq_proj_fwd(const float* hs, const float* W, const float* bias, float* y, int N, int K, int F, da_stream_t stream);
+size_t da_lstm_seq_proj_bwd_workspace(int N, int K, int F);
+int da_lstm_seq_proj_bwd(const float* dy, const float* hs, const float* W, float* dhs, float* dW, float* dbias, float* workspace,
+                         int accumulate, int N, int K, int F, da_stream_t stream);
+
 /* ---- cnn_transformer head: one Block of Transformer (reference models/transformer.py:13-88; CNNTransformerNetwork
  * models/cnn_transformer.py:8-44) in three fp32 launches.  x, y [B][T][D]; `params` = the block's sixteen parameter
  * pointers in named_parameters() order (q / k / v / joint_linear weight, bias; attention_norm; ff.0; ff.2; ff_norm), each
