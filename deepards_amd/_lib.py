@@ -13,7 +13,8 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip.so')   # (override: A/B builds, scripts/)
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
-           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip']
+           'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip',
+           'siamese.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -228,6 +229,11 @@ SIGNATURES = {
     'da_dropout': (_I, [_P, _P, _Z, _P, _U, _F, _P]),
     'da_concat2_dropout': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _Z, _P, _U, _F, _P]),
     'da_slice_dropout': (_I, [_P, _I, _I, _P, _I, _I, _Z, _P, _U, _F, _P]),
+    'da_siamese_draw': (_I, [_P] * 4 + [_I, _I, _U, _U, _I, _P]),
+    'da_siamese_head_rows_per_block': (_I, []),
+    'da_siamese_head_fwd': (_I, [_P] * 4 + [_I] + [_P] * 7 + [_I] * 3 + [_P]),
+    'da_siamese_head_bwd_workspace': (_Z, [_I] * 3),
+    'da_siamese_head_bwd': (_I, [_P] * 4 + [_I] + [_P] * 8 + [_I] + [_P] * 5 + [_F] + [_I] * 4 + [_P]),
 }
 
 

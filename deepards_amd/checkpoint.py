@@ -251,9 +251,9 @@ def _own_module_classes():
     deepards_amd.models.* and torch.nn's own module classes (containers, Conv1d / BatchNorm1d / Linear / LSTM ... that
     the models hold as parameter containers)."""
     import inspect
-    from .models import densenet, resnet, senet, torch_cnn_linear_network, transformer, vgg
+    from .models import densenet, resnet, senet, siamese, torch_cnn_linear_network, transformer, vgg
     allow = []
-    for mod in (resnet, densenet, senet, vgg, torch_cnn_linear_network, transformer):
+    for mod in (resnet, densenet, senet, vgg, torch_cnn_linear_network, transformer, siamese):
         allow += [c for c in vars(mod).values()
                   if inspect.isclass(c) and issubclass(c, torch.nn.Module) and c.__module__ == mod.__name__]
     allow += [c for c in vars(torch.nn).values() if inspect.isclass(c) and issubclass(c, torch.nn.Module)]

@@ -36,12 +36,13 @@ class BNState(object):
 #   * the ~60 tiny per-layer launches -- BN running statistics, BN dgamma/dbeta folds, split-K slab
 #     reductions of the weight gradients -- are queued and served by three batched launches.
 # Outside it (plain autograd use, tests) everything runs immediately.
-_STEP = {'on': False, 'pack': {}, 'running': [], 'pgrad': [], 'wgrad': [], 'wslab': [], 'stemred': None}
+_STEP = {'on': False, 'pack': {}, 'running': [], 'running_early': [], 'groups': 1, 'pgrad': [], 'wgrad': [], 'wslab': [],
+         'stemred': None}
 
 
 @contextlib.contextmanager
 def training_step(model=None):
-    _STEP.update(on=True, pack={}, running=[], pgrad=[], wgrad=[], wslab=[], stemred=None, dout2={})
+    _STEP.update(on=True, pack={}, running=[], running_early=[], pgrad=[], wgrad=[], wslab=[], stemred=None, dout2={})
     try:
         if model is not None:
             # (the convs of a block that keeps off F(4,3): a class attribute ``precise_convs`` on the block, H._wino)
@@ -58,7 +59,7 @@ def training_step(model=None):
                 _STEP['pack'][(w.data_ptr(), int(c))] = e
         yield
     finally:
-        _STEP.update(on=False, pack={}, running=[], pgrad=[], wgrad=[], wslab=[], stemred=None, dout2={})
+        _STEP.update(on=False, pack={}, running=[], running_early=[], pgrad=[], wgrad=[], wslab=[], stemred=None, dout2={})
 
 
 def flush_forward(defer=False):
@@ -66,8 +67,32 @@ def flush_forward(defer=False):
     them queued for flush_backward, whose one launch carries them (nothing reads the running statistics in between)."""
     if defer:
         return
+    _flush_early_running()
     H.bn_running_multi(_STEP['running'])
     _STEP['running'] = []
+
+
+@contextlib.contextmanager
+def running_update_groups(groups):
+    """The windows of every BatchNorm pass inside stand for ``groups`` consecutive passes of equal size (the siamese triplet
+    batch: ``model(seq, pos)`` then ``model(seq, neg)``): the running statistics take ``groups`` updates, one per group of
+    windows in order, instead of one over all windows.  The update of W windows is a closed form (csrc/bn.hip,
+    bn_running_multi_kernel), so one update over 2 W windows and two over W agree only to rounding; with this the one pass
+    leaves the bits of the separate passes.  Costs ``groups - 1`` small launches."""
+    old = _STEP['groups']
+    _STEP['groups'] = int(groups)
+    try:
+        yield
+    finally:
+        _STEP['groups'] = old
+
+
+def _flush_early_running():
+    """The running updates of all window groups but the last, group by group: two updates of one BatchNorm must not share a
+    launch (its blocks run side by side)."""
+    for items in _STEP['running_early']:
+        H.bn_running_multi(items)
+    _STEP['running_early'] = []
 
 
 def flush_backward():
@@ -75,6 +100,7 @@ def flush_backward():
     if _STEP.get('dout2'):      # a block left the second term of its input gradient for a consumer that never came
         raise RuntimeError('a two-term input gradient (BasicBlockFunction split_dx) was not picked up by the block in front')
     _launch_wgrads()
+    _flush_early_running()
     # one launch: slab reductions + dgamma / dbeta folds + the running statistics a deferred flush_forward left queued
     dst = [dw.data_ptr() for _, dw in _STEP['wslab']] + [t.data_ptr() for _, tg, tb in _STEP['pgrad'] for t in (tg, tb)]
     if len(set(dst)) != len(dst):                   # a destination written twice in one step (shared parameters)
@@ -296,11 +322,23 @@ def _running(mean, invstd, wn, st):
     """Book the running-statistics update of BatchNorm ``st`` from the batch statistics of its windows of ``wn`` positions."""
     if st.running_mean is None:
         return
-    item = (mean, invstd, wn, st.running_mean, st.running_var, st.num_batches_tracked, st.momentum, st.eps)
-    if _STEP['on']:
-        _STEP['running'].append(item)
+    tail = (wn, st.running_mean, st.running_var, st.num_batches_tracked, st.momentum, st.eps)
+    g, w = _STEP['groups'], mean.shape[0]
+    if g > 1 and w % g == 0:                           # running_update_groups: one update per group of windows, in order
+        k = w // g
+        items = [(mean[i * k:(i + 1) * k], invstd[i * k:(i + 1) * k]) + tail for i in range(g)]
     else:
-        H.bn_running_multi([item])
+        items = [(mean, invstd) + tail]
+    if _STEP['on']:
+        early = _STEP['running_early']
+        while len(early) < len(items) - 1:
+            early.append([])
+        for lst, item in zip(early, items[:-1]):
+            lst.append(item)
+        _STEP['running'].append(items[-1])
+    else:
+        for item in items:
+            H.bn_running_multi([item])
 
 
 class StemFunction(Function):

@@ -243,6 +243,13 @@ def check_loss_choice(loss, per_breath_outputs):
                          'the class axis, every mean is 0.5 and the term is a constant or an exception')
 
 
+def refuse_eval_on_running_stats(model):
+    """A test epoch under ``model.eval()`` on a breath block whose BatchNorm keeps running statistics is refused."""
+    if getattr(getattr(model, 'breath_block', None), 'running_stats', False):                         # (Backbone class data)
+        raise NotImplementedError('eval_test on a ResNet / VGG breath block means inference on running statistics, which this '
+                                  'package does not have')
+
+
 class HotPathTrainer(object):
     """One model replica on one GPU.  ``train_step(inputs, target)`` == one iteration of the
     reference's batch loop; ``test_step`` == one iteration of run_test_epoch (train-mode modules,
@@ -276,9 +283,8 @@ class HotPathTrainer(object):
             else float(loss_param)
         self._plain_bce = loss == 'bce' and loss_calc == 'all_breaths' and not carry_state
         self._carry = self._flag = None    # (2, 2H): row 0 zeros, row 1 the carried [hx | cx]; the step's row index
-        if self.eval_test and getattr(getattr(model, 'breath_block', None), 'running_stats', False):   # (Backbone class data)
-            raise NotImplementedError('eval_test on a ResNet / VGG breath block means inference on running statistics, which this '
-                                      'package does not have')
+        if self.eval_test:
+            refuse_eval_on_running_stats(model)
         self.model = model
         self.optimizer = optimizer
         self.lr, self.wd, self.momentum = learning_rate, weight_decay, momentum

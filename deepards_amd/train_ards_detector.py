@@ -52,7 +52,7 @@ BUILD_DEFAULTS = dict(
     kfolds=None, only_fold=None, load_checkpoint=None, load_base_network=None, save_model=None, saved_models_dir=None,
     train_from_pickle=None, train_to_pickle=None, test_from_pickle=None, test_to_pickle=None,
     experiment_name='deepards_amd', config_override=None, folds_in_flight=None, fold_groups=None, transformer_blocks=2,
-    use_l1=None, average_linear_layer=None,
+    use_l1=None, average_linear_layer=None, share_anchor=None,
 )
 
 # make_args(): the merged view with every reference default, for callers that build ``args`` in Python
@@ -73,7 +73,7 @@ DEFAULTS = dict(
     train_store=None, test_store=None, test_patient_slot=None, use_graph=True, seed=None, conv_dtype=None, act_dtype=None,
     butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None, post_hoc_downsampling=None,
     n_warm_epochs=3, push_start_epoch=6, push_every_n=6, n_push_iters=5, clust_lambda=0.8, sep_lambda=0.2, n_prototypes=10,
-    incorrect_strength=-0.5, use_l1=False, average_linear_layer=False, folds_in_flight=None,
+    incorrect_strength=-0.5, use_l1=False, average_linear_layer=False, folds_in_flight=None, share_anchor=False,
 )
 
 
@@ -837,6 +837,164 @@ class LSTMOnlyWithPackingModel(LSTMOnlyModel):
     def get_network(self, _):
         return M.LSTMOnlyWithPacking(self._hidden_units(), self.args.n_sub_batches)
 
+
+class SiameseMixin(object):
+    """:558-658 for the trainer of ``deepards_amd.siamese``: the datasets are ``SiameseTileStore`` s (``--train-from-pickle`` /
+    ``--test-from-pickle``: a SiameseNetworkDataset pickle, read without unpickling, or any prepared ARDSRawDataset pickle /
+    .npz; or stores handed in as ``args.train_store`` / ``args.test_store``), ``get_optimizer`` returns a ``SiameseTrainer``,
+    the train epoch draws and gathers every triplet batch on the device, the test epoch (under ``model.eval()``, :635) fills the
+    ``accuracy`` and ``test_loss`` meters per fold and per epoch (``accuracy_epoch_<n>`` / ``test_loss_epoch_<n>``).
+
+    With a base network whose BatchNorm keeps running statistics (ResNet, SE-ResNet, VGG) ``model.eval()`` would mean
+    inference on them, which this package does not have: such a run TRAINS, prints one notice and skips its test epochs.
+    No k-folds (the reference's dataset is not meant for them), one GPU, no folds in flight.  ``--share-anchor`` runs the
+    anchor once per triplet -- a departure, see ``deepards_amd.siamese``."""
+
+    def __init__(self, args):
+        if getattr(args, 'kfolds', None):
+            raise ValueError('siamese pretraining is not meant to be run with k-folds (dataset.py:1597): triplets are drawn over '
+                             'the whole training set')
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise NotImplementedError('siamese pretraining runs on one GPU: the triplet draw and its batch are not sharded over '
+                                      'ranks')
+        n_flight = getattr(args, 'folds_in_flight', None)
+        if n_flight is not None and int(n_flight) > 1:
+            raise NotImplementedError('--folds-in-flight > 1 with siamese pretraining: its dataset has no folds')
+        args.folds_in_flight = 1
+        self._test_skipped = False
+        super(SiameseMixin, self).__init__(args)
+
+    def set_loss_criterion(self):
+        from . import functional as F_
+        self.criterion = F_.bce_with_logits
+
+    def calc_loss(self, outputs_pos, outputs_neg):
+        """:564-571 on logits somebody already has (the trainer's step computes the same sum inside the head kernel)."""
+        t_pos = torch.tensor([[0.0, 1.0]], device=outputs_pos.device).repeat((outputs_pos.shape[0], 1))
+        t_neg = torch.tensor([[1.0, 0.0]], device=outputs_neg.device).repeat((outputs_neg.shape[0], 1))
+        return self.criterion(outputs_pos, t_pos) + self.criterion(outputs_neg, t_neg)
+
+    def _process_test_batch_results(self, outputs_pos, outputs_neg):
+        preds = torch.cat([outputs_pos, outputs_neg], dim=0).argmax(dim=1).cpu().numpy()
+        return preds, [1] * outputs_pos.shape[0] + [0] * outputs_pos.shape[0]
+
+    def record_testing_results(self, accuracy, epoch_num, fold_num):
+        self.results.update_meter('accuracy', fold_num, accuracy)
+        self.results.update_meter('accuracy_epoch_{}'.format(epoch_num), fold_num, accuracy)
+
+    def perform_post_modeling_actions(self):
+        """:576-577 saves the results object; here: the meters' means, returned and kept as ``self.summary``."""
+        self.summary = {}
+        for (name, fold), vals in self.results.meters.items():
+            host = [float(v.detach()) if isinstance(v, torch.Tensor) else float(v) for v in vals]
+            self.summary['%s/%s' % (name, fold)] = sum(host) / len(host) if host else None
+        return self.summary
+
+    def get_base_datasets(self):
+        from .siamese import SiameseTileStore
+        a = self.args
+        seed = 0 if a.seed is None else int(a.seed)
+        if a.train_store is not None:
+            train, test = a.train_store, a.test_store
+        else:
+            if not a.train_from_pickle:
+                raise ValueError('no dataset: pass --train-from-pickle <dataset.pkl|.npz> (or args.train_store / args.test_store); '
+                                 'building one from raw ventilator files (--data-path) is outside the accelerated path')
+            train = SiameseTileStore.from_pickle(a.train_from_pickle, device=self.device, seed=seed)
+            # test_dataset.scaling_factors = train_dataset.scaling_factors (:605)
+            test = SiameseTileStore.from_pickle(a.test_from_pickle, device=self.device, scaling_from=train, seed=seed + 1) \
+                if a.test_from_pickle else None
+        if not isinstance(train, SiameseTileStore) or not (test is None or isinstance(test, SiameseTileStore)):
+            raise TypeError('siamese pretraining takes SiameseTileStore datasets')
+        if any(v is not None for v in self._filter_kwargs().values()) or a.train_store is None:
+            for ds in (train, test):
+                if ds is not None:
+                    ds.set_filters(**self._filter_kwargs())
+        self.n_sub_batches = train.n_sub_batches
+        return train, test
+
+    def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
+        from .siamese import SiameseTrainer
+        a = self.args
+        if a.optimizer not in ('adam', 'sgd'):
+            raise ValueError('optimizer must be adam or sgd')
+        return SiameseTrainer(model, share_anchor=bool(_flag(a, 'share_anchor')), optimizer=a.optimizer,
+                              learning_rate=a.learning_rate, weight_decay=a.weight_decay, clip_grad=bool(_flag(a, 'clip_grad')),
+                              clip_val=a.clip_val, world_size=world_size, rank=rank, process_group=process_group,
+                              use_graph=_flag(a, 'use_graph', True))
+
+    def _generator(self, fold_num, epoch_num, salt=0):
+        if self.args.seed is None:
+            return None
+        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + salt)
+
+    def run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num):
+        from .siamese import run_siamese_train_epoch
+        store, batch_size, shuffle = train_loader
+        if optimizer.model is not model:
+            raise ValueError('optimizer was built for another model')
+        for loss in run_siamese_train_epoch(optimizer, store, batch_size=batch_size, shuffle=shuffle,
+                                            generator=self._generator(fold_num, epoch_num)):
+            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
+            self.results.update_meter('loss', fold_num, loss)
+            if _flag(self.args, 'debug'):
+                break
+
+    def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
+        from .siamese import run_siamese_test_epoch
+        why = None
+        if test_dataset is None:
+            why = 'no test dataset was given (--test-from-pickle)'
+        elif getattr(model.breath_block, 'running_stats', False):
+            why = ('the siamese test epoch runs under model.eval() (train_ards_detector.py:635); with a %s base network that is '
+                   'BatchNorm inference on running statistics, which this package does not have'
+                   % type(model.breath_block).__name__)
+        if why is not None:
+            if not self._test_skipped:
+                print('siamese: the test epochs are skipped -- %s; training is not affected' % why)
+                self._test_skipped = True
+            return None
+        store, batch_size, shuffle = test_loader
+        made = optimizer is None
+        trainer = self.get_optimizer(model) if made else optimizer
+        for loss, acc in run_siamese_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
+                                                generator=self._generator(fold_num, epoch_num, 500009)):
+            self.results.update_meter('test_loss', fold_num, loss)
+            self.results.update_meter('test_loss_epoch_{}'.format(epoch_num), fold_num, loss)
+            self.record_testing_results(acc, epoch_num, fold_num)
+        if made:
+            trainer.release_graphs()
+        return {'accuracy': self.results.get_meter('accuracy_epoch_{}'.format(epoch_num), fold_num),
+                'test_loss': self.results.get_meter('test_loss_epoch_{}'.format(epoch_num), fold_num)}
+
+
+class SiameseCNNLinearModel(SiameseMixin, BaseTraining):
+    """:1137-1142.  NOT in ``network_map`` (its key set is pinned, as for cnn_transformer): reached through
+    ``python -m deepards_amd.siamese -n siamese_cnn_linear`` (``siamese_network_map``) or built directly."""
+
+    def get_network(self, base_network):
+        return M.SiameseCNNLinearNetwork(base_network, self.n_sub_batches)
+
+
+class SiameseCNNLSTMModel(SiameseMixin, BaseTraining):
+    """:1119-1126.  NOT in ``network_map`` (pinned key set): ``python -m deepards_amd.siamese -n siamese_cnn_lstm``."""
+
+    def get_network(self, base_network):
+        return M.SiameseCNNLSTMNetwork(base_network, self.args.time_series_hidden_units, self.n_sub_batches)
+
+
+class SiameseCNNTransformerModel(SiameseMixin, BaseTraining):
+    """:1129-1134.  NOT in ``network_map`` (pinned key set): ``python -m deepards_amd.siamese -n siamese_cnn_transformer``."""
+
+    def get_network(self, base_network):
+        return M.SiameseCNNTransformerNetwork(base_network, self.args.time_series_hidden_units, self.n_sub_batches)
+
+
+siamese_network_map = {
+    'siamese_cnn_linear': SiameseCNNLinearModel,
+    'siamese_cnn_lstm': SiameseCNNLSTMModel,
+    'siamese_cnn_transformer': SiameseCNNTransformerModel,
+}
 
 network_map = {
     'cnn_lstm': CNNLSTMModel,

@@ -741,6 +741,38 @@ int da_slice_copy(const float* src, int lds, int off, float* dst, int ldd, int C
 int da_dropout(const float* x, float* y, size_t n, const int64_t* seed, unsigned salt, float p,
                da_stream_t stream);
 
+/* ---- siamese pretraining (csrc/siamese.hip): the triplet draw and the |a - c| head ------------------------------------
+ * models/siamese.py:56-83 (and its LSTM / Transformer siblings), dataset.py:1586-1591 (SiameseNetworkDataset.__getitem__).
+ * da_siamese_draw   anchor [B] int64 absolute window indices into a store whose windows are sorted so that a patient's
+ *                   windows are contiguous; pat_start / pat_count [N] int32 per WINDOW: first index and number of windows of
+ *                   that window's patient (2 <= count < N).  out int64: [anchor | pos | anchor | neg] (4 B, literal != 0) or
+ *                   [anchor | pos | neg] (3 B).  pos = anchor + 1, or anchor - 1 for the patient's last window;
+ *                   r = mix32(mix32(seed, step), slot), off = (r M) >> 32 with M = N - count,
+ *                   neg = off < start ? off : off + count -- uniform over the other patients' windows up to a relative bias of
+ *                   M / 2^32.  Every index written lies in [0, N).  DA_EINVAL for N < 2, B < 1, a null pointer.
+ * da_siamese_head_fwd   fa_pos, fc_pos, fa_neg, fc_neg [B NB][D] float rows of pitch ld (fa_pos == fa_neg: one shared
+ *                   anchor); W1 [2][D], b1 [2], W2 [2][2 NB], b2 [2].  u [2][B NB][2] = W1 |fc - fa| + b1 per pair (pos, neg);
+ *                   z [2][B][2] = W2 vec(u) + b2; loss[0] = mean BCE(z_pos, [0, 1]) + mean BCE(z_neg, [1, 0]) in the stable
+ *                   max(z, 0) - z t + log1p(exp(-|z|)) form, each mean over 2 B elements.  Any D, NB, B >= 1; 16-byte loads when
+ *                   D, ld are multiples of 4 and the pointers 16-byte aligned.  Two launches.
+ * da_siamese_head_bwd   from the forward's u and z: dfc_* = sign(fc - fa) W1^T du (sign(0) = 0), dfa_* = -dfc_* -- with a shared
+ *                   anchor dfa_pos = (-dfc_pos) + (-dfc_neg) and dfa_neg is not written (may be null); rows of pitch ldg, every
+ *                   element of the D columns written.  dW1, db1, dW2, db2 (+)= with `accumulate`.  gscale multiplies the
+ *                   gradients only.  `workspace`: da_siamese_head_bwd_workspace bytes, written before it is read.  No float
+ *                   atomics: every sum's order depends on (B, NB, D) alone.  Two launches.
+ * da_siamese_head_rows_per_block   rows of [B NB] one block of the two row kernels takes (tests place B NB around it). */
+int da_siamese_draw(const int64_t* anchor, const int* pat_start, const int* pat_count, int64_t* out, int B, int N, unsigned seed,
+                    unsigned step, int literal, da_stream_t stream);
+int da_siamese_head_rows_per_block(void);
+int da_siamese_head_fwd(const float* fa_pos, const float* fc_pos, const float* fa_neg, const float* fc_neg, int ld, const float* W1,
+                        const float* b1, const float* W2, const float* b2, float* u, float* z, float* loss, int B, int NB, int D,
+                        da_stream_t stream);
+size_t da_siamese_head_bwd_workspace(int B, int NB, int D);
+int da_siamese_head_bwd(const float* fa_pos, const float* fc_pos, const float* fa_neg, const float* fc_neg, int ld, const float* W1,
+                        const float* W2, const float* u, const float* z, float* dfa_pos, float* dfc_pos, float* dfa_neg,
+                        float* dfc_neg, int ldg, float* dW1, float* db1, float* dW2, float* db2, float* workspace, float gscale,
+                        int accumulate, int B, int NB, int D, da_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
