@@ -289,6 +289,22 @@ def load_model_weights(path, build_model):
     return model
 
 
+# The reference's other pretraining route saves an AutoencoderNetwork (models/autoencoder_network.py: ``base_network`` an
+# AutoencoderCNN, ``breath_block`` its nn.Sequential encoder).  Neither that network nor the second stage is built here.
+AUTOENCODER_CHECKPOINT = ('%s is an autoencoder checkpoint: autoencoder pretraining is not built in this package, and neither is its '
+                          'second stage, loading the breath_block (the encoder) into a classifier -- which the reference cannot run '
+                          'either: its get_base_network reads network_name off the nn.Sequential that breath_block is')
+
+
+def _refuse_autoencoder(path, class_name=None, keys=()):
+    """Raise for a file of the reference's AutoencoderNetwork: by its class (a pickled module), or by the parameter names of
+    both halves of AutoencoderCNN under ``base_network.`` (a state_dict)."""
+    keys = set(keys)
+    if (class_name or '').split('.')[-1] == 'AutoencoderNetwork' or \
+            {'base_network.conv_down1.weight', 'base_network.conv_up4.weight', 'breath_block.0.weight'} <= keys:
+        raise ValueError(AUTOENCODER_CHECKPOINT % path)
+
+
 def load_base_network(path, base_networks, build_args=None):
     """``--load-base-network`` (train_ards_detector.py:383-388): the ``breath_block`` of a saved model.  Foreign
     files: a fresh base network of the architecture the file names (``breath_block.network_name``) receives the
@@ -306,6 +322,8 @@ def load_base_network(path, base_networks, build_args=None):
     else:
         info = read_module_checkpoint(path)
         sd, name = info['state_dict'], info['network_name']
+        _refuse_autoencoder(path, info['class_name'])
+    _refuse_autoencoder(path, keys=[k[7:] if k.startswith('module.') else k for k in sd])
     sd = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in sd.items())
     bb = OrderedDict((k[len('breath_block.'):], v) for k, v in sd.items() if k.startswith('breath_block.'))
     if not bb:

@@ -996,6 +996,29 @@ siamese_network_map = {
     'siamese_cnn_transformer': SiameseCNNTransformerModel,
 }
 
+def regression_scores(target, preds):
+    """(mean_absolute_error, r2_score, mean_squared_error) of sklearn.metrics with ``multioutput='uniform_average'`` for
+    (n_samples, n_outputs) arrays, in float64 numpy: the errors are averaged over the samples per output column, then over
+    the columns; r2 per column is 1 - SS_res / SS_tot, and a constant column scores 1 when it is matched exactly, else 0
+    (sklearn's ``force_finite``).  What the reference's RegressorMixin (:661-677) books as ``test_mae``, ``r2`` and ``test_mse``
+    per test batch, without importing sklearn; no model class of this package calls it yet."""
+    import numpy as np
+    t, p = np.asarray(target, dtype=np.float64), np.asarray(preds, dtype=np.float64)
+    if t.ndim == 1:
+        t, p = t[:, None], p[:, None]
+    if t.shape != p.shape or t.ndim != 2 or t.shape[0] < 1:
+        raise ValueError('regression_scores: (n_samples, n_outputs) arrays of one shape expected, got %s and %s' % (t.shape, p.shape))
+    mae = float(np.mean(np.mean(np.abs(t - p), axis=0)))
+    mse = float(np.mean(np.mean((t - p) ** 2, axis=0)))
+    num = np.sum((t - p) ** 2, axis=0)
+    den = np.sum((t - np.mean(t, axis=0)) ** 2, axis=0)
+    ok = den != 0
+    r2 = np.ones(t.shape[1])
+    r2[ok] = 1.0 - num[ok] / den[ok]
+    r2[~ok & (num != 0)] = 0.0
+    return mae, float(np.mean(r2)), mse
+
+
 network_map = {
     'cnn_lstm': CNNLSTMModel,
     'cnn_linear': CNNLinearModel,
