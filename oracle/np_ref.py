@@ -435,9 +435,11 @@ def resnet18_features(t, x, prefix='breath_block.', first_pool_type='max', layer
 
     def bwd(dout):
         d = t.rs(avgpool_bwd(dout.reshape(feat.shape), 7, 1, lh))
-        for b in reversed(backs):
+        for b in reversed(backs[1:]):
             d = b(d)
-        return d
+        t.stem_in = d                # what reaches the stem: a stem decision taken the other way changes nothing before it
+        return b_stem(d)
+    t.stem_bwd = b_stem
     return out, bwd
 
 
@@ -488,9 +490,11 @@ def densenet18_features(t, x, prefix='breath_block.', drop_masks=None, block_con
 
     def bwd(dout):
         d = b1(b2(avgpool_bwd(dout.reshape(feat.shape), 7, 1, lh)))
-        for b in reversed(backs):
+        for b in reversed(backs[1:]):
             d = b(d)
-        return d
+        t.stem_in = d                # (as resnet18_features)
+        return b_stem(d)
+    t.stem_bwd = b_stem
     return out, bwd
 
 
@@ -546,8 +550,8 @@ def lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None):
     """nn.LSTM(F, H, num_layers=1, batch_first=True): x (B,T,F) -> h (B,T,H), (hT, cT), tape.  Gate order i, f, g, o."""
     b, t, _ = x.shape
     hd = w_hh.shape[1]
-    h = np.zeros((b, hd)) if h0 is None else h0
-    c = np.zeros((b, hd)) if c0 is None else c0
+    h = np.zeros((b, hd), dtype=x.dtype) if h0 is None else h0
+    c = np.zeros((b, hd), dtype=x.dtype) if c0 is None else c0
     hs, tape = [], []
     for s in range(t):
         z = x[:, s] @ w_ih.T + b_ih + h @ w_hh.T + b_hh
@@ -567,8 +571,8 @@ def lstm_bwd(x, w_ih, w_hh, tape, dh_all):
     b, t, _ = x.shape
     hd = w_hh.shape[1]
     dx = np.zeros_like(x)
-    dw_ih, dw_hh, db = np.zeros_like(w_ih), np.zeros_like(w_hh), np.zeros(4 * hd)
-    dh_next, dc_next = np.zeros((b, hd)), np.zeros((b, hd))
+    dw_ih, dw_hh, db = np.zeros_like(w_ih), np.zeros_like(w_hh), np.zeros(4 * hd, dtype=w_ih.dtype)
+    dh_next, dc_next = np.zeros((b, hd), dtype=x.dtype), np.zeros((b, hd), dtype=x.dtype)
     for s in range(t - 1, -1, -1):
         h_prev, c_prev, i, f, g, o, tc = tape[s]
         dh = dh_all[:, s] + dh_next

@@ -741,11 +741,11 @@ REGIMES = {9: 'per-layer', 10: 'blocks, last block without records', 15: 'blocks
 @pytest.mark.parametrize('nb', [9, 10, 15, 16])
 def test_host_regimes_against_the_oracle(H, nb):
     """CNNLinearNetwork(densenet18(drop_rate=0), nb, 0) at B = 2 against np_ref.cnn_linear_forward_backward, judged as
-    tests/test_model_gpu.py::test_logits_and_grads_match_reference_golden judges (logits 1e-4, every gradient 1e-4 under
-    matched decisions, at most 12 adopted flips) -- and the case must have run the form it is there for: the regime is
+    tests/test_model_gpu.py::test_logits_and_grads_match_reference_golden judges (logits 1e-4, every gradient within 8 x
+    the oracle's own float32 error, 1e-4 at the most, under matched decisions, at most 12 adopted flips) -- and the case must have run the form it is there for: the regime is
     derived from the predicates and the calls are counted."""
     from deepards_amd.functional import bce_with_logits
-    from decision_match import assert_gradients_match
+    from decision_match import assert_gradients_match, oracle_pair
     B = 2
     model = build(nb)
     x, t = seeded_batch(B, nb, 40 + nb)
@@ -761,15 +761,13 @@ def test_host_regimes_against_the_oracle(H, nb):
         assert want['pend_wu'][-1] == 64 and want['stats'] == 1 and 7 in want['wino_bn_l']
     loss = bce_with_logits(out, tt)
     loss.backward()
-    params = {k: v.astype(np.float64) for k, v in seeded_params('densenet18', 3, n_sub_batches=nb).items()}
-    ref = np_ref.cnn_linear_forward_backward(params, x.astype(np.float64), t.astype(np.float64), backbone='densenet18',
-                                             n_sub_batches=nb)
+    ref, noise = oracle_pair(seeded_params('densenet18', 3, n_sub_batches=nb), x, t, backbone='densenet18', n_sub_batches=nb)
     err = np.abs(host(out) - ref['logits']).max()
     print('  nb %d: logits max err %.3e, loss %.8f vs %.8f' % (nb, err, float(loss), ref['loss']))
     assert err < 1e-4 and abs(float(loss) - ref['loss']) < 1e-5
     ours = {n: host(p.grad) for n, p in model.named_parameters() if p.grad is not None and n in ref['grads']}
     assert len(ours) == len(ref['grads'])
-    worst, flips = assert_gradients_match(ref, ours, 'densenet18 nb %d' % nb, max_flips=12, taps=taps)
+    worst, flips = assert_gradients_match(ref, ours, noise, 'densenet18 nb %d' % nb, max_flips=12, taps=taps)
     print('  nb %d: worst gradient rel-l2 %.3e with %d flips' % (nb, worst, len(flips)))
 
 

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 from oracle import np_ref  # noqa: E402
 from oracle.weights import seeded_params  # noqa: E402
 import loss_ref  # noqa: E402
-from decision_match import assert_gradients_match  # noqa: E402
+from decision_match import assert_gradients_match, fp32_noise, plain_twin  # noqa: E402
 
 GOLD = os.path.join(ROOT, 'tests', 'golden')
 
@@ -59,21 +59,22 @@ class tapped(object):
         F_.DECISION_TAP = None
 
 
-def oracle_step(monkeypatch, g, loss, param):
+def oracle_step(monkeypatch, g, loss, param, dtype=np.float64):
     """The oracle's model restatement (oracle/np_ref.py, pinned to these goldens by the existing parity tests) with the loss
     oracle (tests/tools/loss_ref.py, pinned to the reference's loss.py by tests/test_losses_cpu.py) in the place of its
-    BCE: np_ref hands its loss function the (B * NB, 2) logits and the repeated target."""
+    BCE: np_ref hands its loss function the (B * NB, 2) logits and the repeated target.  ``dtype``: the arithmetic of the whole
+    run, loss included (float32: the noise figure of decision_match.fp32_noise)."""
     nb = g['x'].shape[1]
 
     def chained(logits2, target_rep):
         lg, tg = logits2.reshape(-1, nb, 2), target_rep[::nb]
-        l, d = (loss_ref.vacillating if loss == 'vacillating' else loss_ref.confidence)(lg, tg, param)
+        l, d = (loss_ref.vacillating if loss == 'vacillating' else loss_ref.confidence)(lg, tg, param, dtype=dtype)
         return l, d.reshape(logits2.shape)
     monkeypatch.setattr(np_ref, 'bce_with_logits', chained)
     head, backbone = str(g['head']), str(g['backbone'])
-    p64 = {k: v.astype(np.float64) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=float(g['bn_bias_shift']),
-                                                             head=head).items()}
-    return np_ref.cnn_linear_forward_backward(p64, g['x'].astype(np.float64), g['target'].astype(np.float64), backbone=backbone,
+    p64 = {k: v.astype(dtype) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=float(g['bn_bias_shift']),
+                                                        head=head).items()}
+    return np_ref.cnn_linear_forward_backward(p64, g['x'].astype(dtype), g['target'].astype(dtype), backbone=backbone,
                                               first_pool_type=str(g['first_pool_type']), head=head)
 
 
@@ -82,7 +83,8 @@ def oracle_step(monkeypatch, g, loss, param):
                                   'head_single_breath_resnet18_b2.npz', 'head_single_breath_resnet18_b2_active.npz'])
 def test_one_train_step_matches_the_chained_oracles(M, monkeypatch, gold, loss, param):
     """One train_step from the golden's weights: the loss within 1e-5 and every parameter gradient by the suite's one
-    yardstick (decision_match.assert_gradients_match, 1e-4 under the decisions the run took; no ReLU flips on '_active')
+    yardstick (decision_match.assert_gradients_match: per tensor 8 x the chained oracles' own float32 error, 1e-4 at the most,
+    under the decisions the run took; no ReLU flips on '_active')
     of oracle loss gradient -> oracle model backward.  Then eager == graph-replayed steps, bit for bit."""
     from deepards_amd.train import HotPathTrainer
     g = _gold(gold)
@@ -98,7 +100,9 @@ def test_one_train_step_matches_the_chained_oracles(M, monkeypatch, gold, loss, 
     ours = {n: p.grad.cpu().numpy().astype(np.float64) for n, p in model.named_parameters()
             if p.grad is not None and n in ref['grads']}
     assert set(ours) == {n for n, p in model.named_parameters() if p.grad is not None} and len(ours) > 10
-    assert_gradients_match(ref, ours, '%s %s' % (gold[:-4], loss), strict=float(g['bn_bias_shift']) > 0, taps=taps, log=log)
+    noise = fp32_noise(ref, oracle_step(monkeypatch, g, loss, param, dtype=np.float32))
+    assert_gradients_match(ref, ours, noise, '%s %s' % (gold[:-4], loss), strict=float(g['bn_bias_shift']) > 0, taps=taps, log=log,
+                           twin=plain_twin(os.path.join(GOLD, gold)))
     # eager and graph-replayed steps, bit for bit (step 1 is eager in both; 2 captures and replays; 3, 4 replay)
     ma, mb = build_head(M, g), build_head(M, g)
     ta = HotPathTrainer(ma, use_graph=False, loss=loss, loss_param=param)

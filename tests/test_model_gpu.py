@@ -60,15 +60,17 @@ def rel_l2(a, b):
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tools'))
 from decision_match import decision_matched_gradients as _dmg, assert_gradients_match as _agm, feature_reference      # noqa: E402
+from decision_match import oracle_pair, fp32_noise, plain_twin, as_f32      # noqa: E402
 
 
 def decision_matched_gradients(ref, ours, log_tag=''):
     return _dmg(ref, ours, log_tag, log=log)
 
 
-def assert_gradients_match(ref, ours, tag='', strict=False, max_flips=12, allow=None, taps=None):
-    """1e-4 against the oracle's exact gradients under the decisions this run took (tests/tools/decision_match.py)."""
-    return _agm(ref, ours, tag, strict=strict, max_flips=max_flips, log=log, allow=allow, taps=taps)
+def assert_gradients_match(ref, ours, noise, tag='', strict=False, max_flips=12, allow=None, taps=None, twin=None):
+    """Per tensor within 8 x the oracle's own float32 error (``noise``: decision_match.fp32_noise), 1e-4 at the most, of
+    the oracle's exact gradients under the decisions this run took (tests/tools/decision_match.py)."""
+    return _agm(ref, ours, noise, tag, strict=strict, max_flips=max_flips, log=log, allow=allow, taps=taps, twin=twin)
 
 
 class tapped(object):
@@ -93,8 +95,9 @@ def grads64(model, ref):
 @pytest.mark.parametrize('path', GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
 def test_logits_and_grads_match_reference_golden(M, path):
     """Logits: 1e-4 absolute (north star), every golden, against the reference's fp64 capture.
-    Gradients, every parameter, every golden: within 1e-4 (rel-l2 <= 1e-4, or max abs err <= 1e-4 * max(1, max|ref|))
-    of the EXACT gradients -- the numpy oracle's, which tests/test_oracle_golden.py pins to the reference's captured
+    Gradients, every parameter, every golden: by the suite's one yardstick (decision_match.assert_gradients_match: rel-l2
+    within 8 x the oracle's own float32 error on that tensor, 1e-4 at the most; the absolute 1e-4 rule only where float32
+    itself has no relative scale) against the EXACT gradients -- the numpy oracle's, which tests/test_oracle_golden.py pins to the reference's captured
     fp64 gradients at 1e-10 -- under the activation decisions this run took (``decision_matched_gradients``: an fp32
     forward legitimately takes the other branch of a ReLU whose pre-activation is within ~1e-6 of zero; the flips
     adopted are logged, each must be an element the oracle itself lists as within 3e-5 of the boundary, and there may
@@ -122,9 +125,8 @@ def test_logits_and_grads_match_reference_golden(M, path):
         (err, ref32, float(loss), float(g['loss64'])))
     assert err < 1e-4
     assert abs(float(loss) - float(g['loss64'])) < 1e-5
-    params64 = {k: v.astype(np.float64) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=shift).items()}
-    ref = np_ref.cnn_linear_forward_backward(params64, g['x'].astype(np.float64), g['target'].astype(np.float64),
-                                             backbone=backbone, first_pool_type=str(g['first_pool_type']))
+    ref, noise = oracle_pair(seeded_params(backbone, int(g['seed']), bn_bias_shift=shift), g['x'], g['target'],
+                             key=os.path.basename(path), backbone=backbone, first_pool_type=str(g['first_pool_type']))
     ours = {}
     for n, p in model.named_parameters():
         key = 'grad64/' + n
@@ -135,27 +137,11 @@ def test_logits_and_grads_match_reference_golden(M, path):
         d = digest(ref['grads'][n])                                     # the oracle IS the reference's fp64 capture
         body = slice(None) if p.numel() <= 1024 else slice(0, -3)
         assert np.abs(d - g[key])[body].max() <= 1e-9 * max(1.0, np.abs(g[key][body]).max()), n
-    from decision_match import hip_relu_flips, is_stem_decision
-    known = hip_relu_flips(ref['tape'], taps, log=log, tag=os.path.basename(path))
-    matched, flips, ncand = _dmg(ref, ours, os.path.basename(path), log=log, known=known, only=is_stem_decision)
-    if strict:
-        assert not [f for f in flips if not f[0].endswith('.maxpool')], flips
-    assert len(flips) <= 12, flips
-    worst, bad = 0.0, []
     for n in ours:
-        abs_err = float(np.abs(ours[n] - matched[n]).max())
-        rl2 = rel_l2(ours[n], matched[n])
-        rl2_exact = rel_l2(ours[n], ref['grads'][n])
         body = slice(None) if ours[n].size <= 1024 else slice(0, -3)
-        ref32_rl2 = rel_l2(g['grad32/' + n][body], g['grad64/' + n][body])
-        worst = max(worst, rl2)
-        log('   grad %-60s max abs err %.3e rel-l2 %.3e (no matching: %.3e; reference fp32 vs fp64: %.3e)' %
-            (n, abs_err, rl2, rl2_exact, ref32_rl2))
-        scale = max(1.0, float(np.abs(matched[n]).max()))
-        if not (rl2 <= 1e-4 or abs_err <= 1e-4 * scale):
-            bad.append((n, abs_err, rl2))
-    log('   worst grad rel-l2 %.3e with %d flips of %d candidates' % (worst, len(flips), ncand))
-    assert not bad, bad
+        log('   grad %-60s no matching: %.3e; reference fp32 vs fp64 capture: %.3e' %
+            (n, rel_l2(ours[n], ref['grads'][n]), rel_l2(g['grad32/' + n][body], g['grad64/' + n][body])))
+    assert_gradients_match(ref, ours, noise, os.path.basename(path), strict=strict, taps=taps, twin=plain_twin(path))
 
 
 def build_head(M, head, backbone, seed, first_pool_type='max', shift=0.0):
@@ -176,7 +162,8 @@ def test_sibling_heads_match_reference_golden(M, path):
     (reference models/torch_cnn_linear_network.py:7-89) and CNNLSTMNetwork (torch_cnn_lstm_combo.py:6-50; goldens from
     the reference classes,
     oracle/make_golden_heads.py): logits 1e-4 absolute; gradients by the suite's one yardstick -- the oracle (pinned to
-    the golden's digests here at 1e-9) under the decisions this run took, 1e-4, no flips on the '_active' goldens.  The
+    the golden's digests here at 1e-9) under the decisions this run took, per tensor 8 x the oracle's own float32 error and 1e-4
+    at the most, no flips on the '_active' goldens.  The
     median head keeps one decision the tape does not carry (WHICH breath is the median: fp32 / fp64 ties), so its
     parameters may fall back to rel-l2 5e-2 -- the only place left where that bound is used.  One trainer step runs."""
     from deepards_amd.functional import bce_with_logits
@@ -199,10 +186,8 @@ def test_sibling_heads_match_reference_golden(M, path):
     err = np.abs(out.detach().cpu().numpy().astype(np.float64) - g['logits64']).max()
     log(os.path.basename(path), 'logits max|hip-ref64| %.3e loss %.8f vs %.8f' % (err, float(loss), float(g['loss64'])))
     assert err < 1e-4 and abs(float(loss) - float(g['loss64'])) < 1e-5
-    params64 = {k: v.astype(np.float64) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=shift,
-                                                                   head=head).items()}
-    ref = np_ref.cnn_linear_forward_backward(params64, g['x'].astype(np.float64), g['target'].astype(np.float64),
-                                             backbone=backbone, first_pool_type=str(g['first_pool_type']), head=head)
+    ref, noise = oracle_pair(seeded_params(backbone, int(g['seed']), bn_bias_shift=shift, head=head), g['x'], g['target'],
+                             key=os.path.basename(path), backbone=backbone, first_pool_type=str(g['first_pool_type']), head=head)
     ours = {}
     for n, p in model.named_parameters():
         key = 'grad64/' + n
@@ -213,7 +198,8 @@ def test_sibling_heads_match_reference_golden(M, path):
         body = slice(None) if p.numel() <= 1024 else slice(0, -3)       # the oracle IS the reference's fp64 capture
         assert np.abs(digest(ref['grads'][n]) - g[key])[body].max() <= 1e-9 * max(1.0, np.abs(g[key][body]).max()), n
     median_slack = (lambda n: rel_l2(ours[n], ref['grads'][n]) <= 5e-2) if head == 'compr_to_rf' else None
-    assert_gradients_match(ref, ours, os.path.basename(path), strict=strict and head != 'compr_to_rf', allow=median_slack, taps=taps)
+    assert_gradients_match(ref, ours, noise, os.path.basename(path), strict=strict and head != 'compr_to_rf', allow=median_slack,
+                           taps=taps, twin=plain_twin(path))
     if strict and backbone == 'resnet18':                 # the trainer drives every head (per-breath loss included)
         tr = HotPathTrainer(model, use_graph=True)
         l = [float(tr.train_step(x, t)) for _ in range(3)]
@@ -225,7 +211,7 @@ def test_sibling_heads_match_reference_golden(M, path):
 @pytest.mark.parametrize('path', BB_GOLD, ids=[os.path.basename(p)[:-4] for p in BB_GOLD])
 def test_other_backbones_match_reference_golden(M, path):
     """resnet34 and densenet121 (the other BasicBlock / growth-32 base networks of the reference) on the same kernels:
-    logits 1e-4, loss, gradients 1e-4 under matched decisions (the oracle pinned to the golden's digests), a few trainer
+    logits 1e-4, loss, gradients by the same yardstick under matched decisions (the oracle pinned to the golden's digests), a few trainer
     steps."""
     from deepards_amd.functional import bce_with_logits
     from deepards_amd.train import HotPathTrainer
@@ -245,8 +231,7 @@ def test_other_backbones_match_reference_golden(M, path):
     err = np.abs(out.detach().cpu().numpy() - g['logits64']).max()
     log(name, 'logits err %.3e loss %.7f vs %.7f' % (err, float(loss), float(g['loss64'])))
     assert err < 1e-4 and abs(float(loss) - float(g['loss64'])) < 1e-5
-    ref = np_ref.cnn_linear_forward_backward({k: v.astype(np.float64) for k, v in seeded_params(name, int(g['seed'])).items()},
-                                             g['x'].astype(np.float64), g['target'].astype(np.float64), backbone=name)
+    ref, noise = oracle_pair(seeded_params(name, int(g['seed'])), g['x'], g['target'], key=os.path.basename(path), backbone=name)
     ours = {}
     for n, p in model.named_parameters():
         key = 'grad64/' + n
@@ -256,7 +241,7 @@ def test_other_backbones_match_reference_golden(M, path):
         ours[n] = p.grad.cpu().numpy().astype(np.float64)
         body = slice(None) if p.numel() <= 1024 else slice(0, -3)
         assert np.abs(digest(ref['grads'][n], 24) - g[key])[body].max() <= 1e-9 * max(1.0, np.abs(g[key][body]).max()), n
-    assert_gradients_match(ref, ours, name, max_flips=96, taps=taps)       # up to 7x the layers of the 18s: more decisions near zero
+    assert_gradients_match(ref, ours, noise, name, max_flips=96, taps=taps)       # up to 7x the layers of the 18s: more decisions near zero
     tr = HotPathTrainer(model, use_graph=True)
     assert all(np.isfinite(float(tr.train_step(x, t))) for _ in range(3))
 
@@ -266,7 +251,7 @@ def test_constructor_options_match_reference_golden(M, path):
     """The constructor options of SURVEY 8b that round 2 refused: densenet18(with_fft / only_fft / fft_real_only)
     (models/densenet.py:109-115: conv0 on 3 / 2 / 2 / 1 input channels, stem kernels da_stem_conv_*_g) and
     resnet18(double_conv_first=True) (models/resnet.py:90-96,142-149: conv1_alt -> bn1 -> conv2 k7 s2 -> bn2).  Goldens from
-    the reference classes (oracle/make_golden_options.py): logits 1e-4, loss 1e-5, every gradient 1e-4 under matched
+    the reference classes (oracle/make_golden_options.py): logits 1e-4, loss 1e-5, every gradient by the suite's yardstick under matched
     decisions, the live / dead parameter sets, a 3-step SGD trajectory through the captured step."""
     from deepards_amd.functional import bce_with_logits
     from deepards_amd.train import HotPathTrainer
@@ -295,10 +280,9 @@ def test_constructor_options_match_reference_golden(M, path):
     err = np.abs(out.detach().cpu().numpy().astype(np.float64) - g['logits64']).max()
     log(os.path.basename(path), 'logits max|hip-ref64| %.3e loss %.8f vs %.8f' % (err, float(loss), float(g['loss64'])))
     assert err < 1e-4 and abs(float(loss) - float(g['loss64'])) < 1e-5
-    params64 = {k: v.astype(np.float64) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=shift, in_ch=in_ch).items()}
-    ref = np_ref.cnn_linear_forward_backward(params64, g['x'].astype(np.float64), g['target'].astype(np.float64),
-                                             backbone=backbone, first_pool_type=str(g['first_pool_type']),
-                                             double_conv_first=double)
+    ref, noise = oracle_pair(seeded_params(backbone, int(g['seed']), bn_bias_shift=shift, in_ch=in_ch), g['x'], g['target'],
+                             key=os.path.basename(path), backbone=backbone, first_pool_type=str(g['first_pool_type']),
+                             double_conv_first=double)
     ours = {}
     for n, p in model.named_parameters():
         if 'grad64/' + n not in g:
@@ -309,7 +293,7 @@ def test_constructor_options_match_reference_golden(M, path):
         assert np.abs(digest(ref['grads'][n]) - g['grad64/' + n])[body].max() <= 1e-9 * max(1.0, np.abs(g['grad64/' + n][body]).max()), n
     if double:
         assert 'breath_block.conv1.weight' not in ours and 'breath_block.conv2.weight' in ours
-    assert_gradients_match(ref, ours, os.path.basename(path), strict=shift > 0, taps=taps)
+    assert_gradients_match(ref, ours, noise, os.path.basename(path), strict=shift > 0, taps=taps, twin=plain_twin(path))
     # three SGD-Nesterov steps with the clamp, through the captured step (steps 2, 3 replay the graph)
     tr = HotPathTrainer(make(), optimizer='sgd', use_graph=True)
     losses = [float(tr.train_step(x, t)) for _ in range(3)]
@@ -447,8 +431,7 @@ def test_fresh_inputs_vs_numpy_oracle(M):
     for backbone in ('resnet18', 'densenet18'):
         model = build(M, backbone, 7)
         x, t = seeded_batch(3, 20, 11, 'flow')
-        params = {k: v.astype(np.float64) for k, v in seeded_params(backbone, 7).items()}
-        ref = np_ref.cnn_linear_forward_backward(params, x.astype(np.float64), t.astype(np.float64), backbone=backbone)
+        ref, noise = oracle_pair(seeded_params(backbone, 7), x, t, backbone=backbone)
         from deepards_amd.functional import bce_with_logits
         with tapped() as taps:
             out = model(torch.from_numpy(x).cuda(), None)
@@ -456,7 +439,7 @@ def test_fresh_inputs_vs_numpy_oracle(M):
         err = np.abs(out.detach().cpu().numpy() - ref['logits']).max()
         log(backbone, 'fresh B=3 flow: logits err %.3e' % err)
         assert err < 1e-4
-        assert_gradients_match(ref, grads64(model, ref), backbone + ' fresh B=3 flow', taps=taps)
+        assert_gradients_match(ref, grads64(model, ref), noise, backbone + ' fresh B=3 flow', taps=taps)
 
 
 @pytest.mark.parametrize('nb', [40, 8])
@@ -473,8 +456,7 @@ def test_other_sub_batch_counts_vs_numpy_oracle(M, nb):
         assert not model.load_state_dict({k: torch.from_numpy(v) for k, v in p32.items()}, strict=False).unexpected_keys
         model = model.cuda().train()
         x, t = seeded_batch(3, nb, 5, 'flow')
-        ref = np_ref.cnn_linear_forward_backward({k: v.astype(np.float64) for k, v in p32.items()}, x.astype(np.float64),
-                                                 t.astype(np.float64), backbone=backbone, n_sub_batches=nb, need_grads=True)
+        ref, noise = oracle_pair(p32, x, t, backbone=backbone, n_sub_batches=nb, need_grads=True)
         xt, tt = torch.from_numpy(x).cuda(), torch.from_numpy(t).cuda()
         with tapped() as taps:
             out = model(xt, None)
@@ -484,7 +466,7 @@ def test_other_sub_batch_counts_vs_numpy_oracle(M, nb):
         log(backbone, 'nb=%d: logits err %.3e loss %.7f vs %.7f' % (nb, err, float(loss), ref['loss']))
         assert err < 1e-4 and abs(float(loss) - ref['loss']) < 1e-5
         # (nb 40: twice the rows of the (3, 20) batches the default of 12 flips was set at)
-        assert_gradients_match(ref, grads64(model, ref), '%s nb=%d' % (backbone, nb), max_flips=12 * max(1, nb // 20), taps=taps)
+        assert_gradients_match(ref, grads64(model, ref), noise, '%s nb=%d' % (backbone, nb), max_flips=12 * max(1, nb // 20), taps=taps)
         tr = HotPathTrainer(model, use_graph=True)
         assert all(np.isfinite(float(tr.train_step(xt, tt))) for _ in range(3))
 
@@ -493,7 +475,7 @@ def test_other_sub_batch_counts_vs_numpy_oracle(M, nb):
 def test_long_sequences_breath_block_vs_numpy_oracle(M, backbone):
     """BASELINE config C5's tile shape (nb 40, seq_len 512): ``breath_block((40, 1, 512))`` gives a 16-long final map,
     AvgPool1d(7, 1) leaves 10 positions and ``view(N, -1)`` flattens channel-major (resnet.py:159-160,
-    densenet.py:183-184) -> (40, F * 10).  Features (1e-4) and every weight gradient (1e-4 under matched decisions)
+    densenet.py:183-184) -> (40, F * 10).  Features (1e-4) and every weight gradient (the suite's yardstick, under matched decisions)
     against the oracle."""
     nb, L = 40, 512
     bb = M.resnet18() if backbone == 'resnet18' else M.densenet18(drop_rate=0.0)
@@ -506,6 +488,7 @@ def test_long_sequences_breath_block_vs_numpy_oracle(M, backbone):
     F = bb.n_out_filters
     w = rng.randn(nb, F * 10) / np.sqrt(nb * F * 10)
     fr = feature_reference({k: v.astype(np.float64) for k, v in p32.items()}, nb, x.astype(np.float64), w, backbone)
+    noise = fp32_noise(fr, feature_reference(as_f32(p32), nb, x, as_f32(w), backbone))
     ref = fr['feat']
     assert ref.shape == (nb, F * 10)
     with tapped() as taps:
@@ -515,7 +498,7 @@ def test_long_sequences_breath_block_vs_numpy_oracle(M, backbone):
     log(backbone, 'nb=40 L=512 features err %.3e' % err)
     assert err < 1e-4
     (feat * torch.from_numpy(w.astype(np.float32)).cuda()).sum().backward()
-    assert_gradients_match(fr, grads64(model, fr), backbone + ' nb=40 L=512', max_flips=24, taps=taps)    # 4.6x the elements of a (20, 224) tile
+    assert_gradients_match(fr, grads64(model, fr), noise, backbone + ' nb=40 L=512', max_flips=24, taps=taps)    # 4.6x the elements of a (20, 224) tile
 
 
 def test_long_sequences_bf16_convs(M):

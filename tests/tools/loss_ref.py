@@ -1,5 +1,5 @@
-"""numpy float64 restatement of the reference's two per-breath losses (deepards/loss.py) and their gradients, written
-from the formulas, not from the kernels: tests/test_losses_cpu.py pins it to the goldens captured from the reference
+"""numpy restatement (float64, or the ``dtype`` asked for: float32 gives the noise figure of decision_match.fp32_noise)
+of the reference's two per-breath losses (deepards/loss.py) and their gradients, written from the formulas, not from the kernels: tests/test_losses_cpu.py pins it to the goldens captured from the reference
 (tests/golden/loss_*.npz, 1e-10) and to central finite differences; the GPU tests chain its gradient through the
 oracle's model restatement.
 
@@ -26,17 +26,18 @@ def _repeat(logits, target):
     return np.broadcast_to(target[:, None, :], logits.shape) if logits.ndim == 3 else target
 
 
-def bce_mean(logits, target):
+def bce_mean(logits, target, dtype=np.float64):
     """torch.nn.BCEWithLogitsLoss() (mean) with the window target repeated over the breaths -> loss, d loss / d logits."""
-    x, t = np.asarray(logits, dtype=np.float64), _repeat(logits, np.asarray(target, dtype=np.float64))
+    x, t = np.asarray(logits, dtype=dtype), _repeat(logits, np.asarray(target, dtype=dtype))
     loss = (np.maximum(x, 0) - x * t + np.log1p(np.exp(-np.abs(x)))).mean()
     return float(loss), (_sigmoid(x) - t) / x.size
 
 
-def confidence(logits, target, beta):
+def confidence(logits, target, beta, dtype=np.float64):
     """ConfidencePenaltyLoss(beta), loss.py:32-35: BCE mean + beta * mean over all elements of p log p."""
-    x = np.asarray(logits, dtype=np.float64)
-    bce, dbce = bce_mean(x, target)
+    x = np.asarray(logits, dtype=dtype)
+    beta = x.dtype.type(beta)
+    bce, dbce = bce_mean(x, target, dtype)
     p, lp = _softmax(x), _log_softmax(x)
     s = (p * lp).sum(axis=-1, keepdims=True)
     loss = bce + beta * (p * lp).mean()
@@ -48,15 +49,15 @@ def class_means(logits):
     return _softmax(np.asarray(logits, dtype=np.float64)).mean(axis=1)
 
 
-def vacillating(logits, target, alpha):
+def vacillating(logits, target, alpha, dtype=np.float64):
     """VacillatingLoss(alpha), loss.py:15-23: BCE mean + mean over (W, 2) of v(x); v(x) = -log(2 (e^-alpha - 1) x + 1) for
     x < 0.5, -log(2 e^-alpha (1 - x) + 2 x - 1) for x > 0.5 (x == 0.5 -- the reference raises -- takes the left branch)."""
-    x = np.asarray(logits, dtype=np.float64)
+    x = np.asarray(logits, dtype=dtype)
     if x.ndim != 3:
         raise ValueError('the vacillating loss needs per-breath logits (W, NB, 2)')
     w, nb, _ = x.shape
-    ea = np.exp(-np.float64(alpha))
-    bce, dbce = bce_mean(x, target)
+    ea = np.exp(-x.dtype.type(alpha))
+    bce, dbce = bce_mean(x, target, dtype)
     p = _softmax(x)
     xm = p.mean(axis=1)                                               # (W, 2)
     left = xm <= 0.5

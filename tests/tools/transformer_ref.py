@@ -116,18 +116,19 @@ def rel_l2(a, b):
     return float(np.linalg.norm(np.asarray(a, np.float64) - np.asarray(b, np.float64)) / (nb if nb > 0 else 1.0))
 
 
-def model_reference(g, backbone):
+def model_reference(g, backbone, dtype=np.float64):
     """The whole cnn_transformer model of a tests/golden/tfm_model_* file in the oracle: np_ref's breath block on the
-    seeded backbone with this module's head, in the form decision_match wants (grads, tape, rebackward; + logits, loss)."""
+    seeded backbone with this module's head, in the form decision_match wants (grads, tape, rebackward; + logits, loss).
+    ``dtype``: the arithmetic of the whole run (float32: the noise figure of decision_match.fp32_noise)."""
     from oracle.weights import seeded_params
     from decision_match import feature_reference
-    x64, t64 = g['x'].astype(np.float64), g['target'].astype(np.float64)
+    x64, t64 = g['x'].astype(dtype), g['target'].astype(dtype)
     b, nb = x64.shape[:2]
-    p64 = {k: v.astype(np.float64) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=float(g['bn_bias_shift']),
+    p64 = {k: v.astype(dtype) for k, v in seeded_params(backbone, int(g['seed']), bn_bias_shift=float(g['bn_bias_shift']),
                                                              head='single_breath').items() if k.startswith('breath_block.')}
     nblocks = int(g['blocks'])
-    blocks = [[g['param/transformer.blocks.%d.%s' % (i, n)].astype(np.float64) for n in PARAM_NAMES] for i in range(nblocks)]
-    wf, bf = g['param/linear_final.weight'].astype(np.float64), g['param/linear_final.bias'].astype(np.float64)
+    blocks = [[g['param/transformer.blocks.%d.%s' % (i, n)].astype(dtype) for n in PARAM_NAMES] for i in range(nblocks)]
+    wf, bf = g['param/linear_final.weight'].astype(dtype), g['param/linear_final.bias'].astype(dtype)
 
     def head(feat):
         o = transformer_loss(feat.reshape(b, nb, -1), blocks, wf, bf, t64)
