@@ -251,9 +251,9 @@ def _own_module_classes():
     deepards_amd.models.* and torch.nn's own module classes (containers, Conv1d / BatchNorm1d / Linear / LSTM ... that
     the models hold as parameter containers)."""
     import inspect
-    from .models import densenet, resnet, senet, siamese, torch_cnn_linear_network, transformer, vgg
+    from .models import densenet, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, vgg
     allow = []
-    for mod in (resnet, densenet, senet, vgg, torch_cnn_linear_network, transformer, siamese):
+    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese):
         allow += [c for c in vars(mod).values()
                   if inspect.isclass(c) and issubclass(c, torch.nn.Module) and c.__module__ == mod.__name__]
     allow += [c for c in vars(torch.nn).values() if inspect.isclass(c) and issubclass(c, torch.nn.Module)]
@@ -330,9 +330,9 @@ def load_base_network(path, base_networks, build_args=None):
         raise ValueError('%s holds no breath_block.* weights' % path)
     build_args = build_args or {}
     name = name or build_args.get('base_network')
-    if name not in base_networks:
-        raise ValueError('base network %r of %s is not built by this package' % (name, path))
     from . import models as M
+    if name not in base_networks and name not in M.UNLISTED_BACKBONES:
+        raise ValueError('base network %r of %s is not built by this package' % (name, path))
     net = M.build_base_network(name, build_args)
     net.load_state_dict(bb, strict=True)
     return net

@@ -48,10 +48,11 @@ def training_step(model=None):
             # (the convs of a block that keeps off F(4,3): a class attribute ``precise_convs`` on the block, H._wino)
             precise = {id(c) for b in model.modules() if getattr(b, 'precise_convs', False) for c in b.children()}
             ms = [m for m in model.modules()
-                  if isinstance(m, torch.nn.Conv1d) and m.kernel_size[0] <= 3 and m.in_channels % 32 == 0
+                  if isinstance(m, torch.nn.Conv1d) and m.kernel_size[0] <= 3 and m.in_channels % 32 == 0 and m.groups == 1
                   and m.weight.is_cuda and (m.bias is None or m.kernel_size[0] == 3)]
             # (k1 with a bias: an SEModule's fc1 / fc2 -- no conv kernel reads them; k3 with a bias: the VGG stages, whose
-            # kernels never read the bias either, VGGStageFunction)
+            # kernels never read the bias either, VGGStageFunction; a grouped conv -- the ResNeXt conv2, weight (C, C / 32, 3) -- has
+            # no packed form: H.gconv3_* read torch's layout)
             ws = [m.weight for m in ms]
             forms = [H.step_pack_form(*m.weight.shape, m.stride[0], m.padding[0], id(m) in precise or getattr(m, 'precise_conv', False))
                      for m in ms]                      # (``precise_conv`` on the conv itself: the VGG stages, models/vgg.py)
@@ -708,13 +709,32 @@ def _se_tail_bwd(fam, dout, mask, y, R, mean, invstd, gamma, beta, pool, hid, ga
     return g, dz, (None,) * 4 if direct else se_g
 
 
+def _gconv_wgrad(dy, x, stride, tw):
+    """Weight gradient of a grouped k3 conv: always its own launch pair (the batched weight-gradient jobs and their plan know
+    nothing of groups), written or accumulated straight into a trainer's destination ``tw`` as the SE gate gradients are."""
+    if tw is None:
+        return H.gconv3_wgrad(dy, x, stride)
+    H.gconv3_wgrad(dy, x, stride, out=tw, accumulate=_acc())
+    return None
+
+
+def _se_unit(units, i, stride):
+    """(k, precise, BNState, stride, groups) of conv unit i.  The three-field form is the plain blocks': the block's stride sits
+    on unit 0 and no conv is grouped."""
+    u = tuple(units[i])
+    return u + (stride if i == 0 else 1, 1) if len(u) == 3 else u
+
+
 class SEBlockFunction(Function):
     """An SE residual block over its conv units: conv(s) -> [BN -> ReLU -> conv]* -> BN -> * gate (+ identity | BN(conv1x1(s)))
     -> ReLU with gate = sigmoid(fc2(relu(fc1(mean_L(bn(..)))))) per row and channel.  Two units k3, k3: SEBasicBlock (reference
     models/senet.py:52-68); three units k1, k3, k1 with the stride on the first: SEResNetBottleneck (:75-95, :122-144);
     :27-34 (SEModule.forward), :295-300 (downsample; a bottleneck net's layer1.0 has one with stride 1).
 
-    ``units``: (kernel size, precise, BNState) of every conv unit; ``params``: (conv weight, BN weight, BN bias) of every
+    ``units``: (kernel size, precise, BNState) of every conv unit -- the block's ``stride`` is then the first unit's -- or
+    (kernel size, precise, BNState, stride, groups) where a unit carries its own: the ResNeXt form (SEResNeXtBottleneck,
+    :147-168) is k1 s1, grouped k3 with the block's stride on H.gconv3_*, k1; the downsample conv always takes the block's
+    stride and reads the block's input, as conv1 does.  ``params``: (conv weight, BN weight, BN bias) of every
     unit, fc1 / fc2 weight and bias, then the downsample's (conv weight, BN weight, BN bias) where there is one (``std``:
     its BNState).  ``family``: the gate kernels' (H.SE_NARROW / H.SE_WIDE), named by the block.
 
@@ -734,15 +754,20 @@ class SEBlockFunction(Function):
         convs = [params[3 * i:3 * i + 3] for i in range(n)]
         f1w, f1b, f2w, f2b = params[3 * n:3 * n + 4]
         wd, gd, bd = params[3 * n + 4:] or (None, None, None)
-        w1, (k1, precise1, _) = convs[0][0], units[0]
+        units = [_se_unit(units, i, stride) for i in range(n)]
+        w1, (k1, precise1, _, s1, g1) = convs[0][0], units[0]
+        if g1 != 1 or any(g != 1 and k != 3 for k, _, _, _, g in units) or (k1 == 3 and s1 != stride):
+            raise NotImplementedError('a grouped conv is a k3 unit behind the first (H.gconv3_ok); a k3 first unit carries the '
+                                      "block's stride")
         # conv1 and the downsample conv in one launch where the entry has that form; else separate convs
-        ctx.entry = H.s2_entry_kernel(w1.shape, None if wd is None else wd.shape, stride, x.shape[1], False) if k1 == 3 else None
+        ctx.entry = H.s2_entry_kernel(w1.shape, None if wd is None else wd.shape, stride, x.shape[1], False) \
+            if k1 == 3 and s1 == stride else None
         if ctx.entry is not None:
             y, yd = _entry_fwd(ctx.entry, x, None, w1, wd, stride)
         elif k1 == 1 and wd is not None:
-            y, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], stride, 0), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
+            y, yd = H.conv_fwd_multi([(x, _pack(w1, H.DIRECT)[0], s1, 0), (x, _pack(wd, H.DIRECT)[0], stride, 0)])
         else:
-            y = _conv_fwd(x, w1, stride, k1 // 2, precise=precise1)
+            y = _conv_fwd(x, w1, s1, k1 // 2, precise=precise1)
             yd = None if wd is None else _conv_fwd(x, wd, stride, 0)
         sd = _Stats()
         res = x if wd is None else _bn_apply(yd, R, sd, std, gd, bd, False)
@@ -751,13 +776,13 @@ class SEBlockFunction(Function):
             s = _Stats()
             h = _bn_apply(ys[-1], R, s, units[i - 1][2], convs[i - 1][1], convs[i - 1][2], True)
             _tap(h)
-            k, precise, _ = units[i]
-            ys.append(_conv_fwd(h, convs[i][0], 1, k // 2, precise=precise))
+            k, precise, _, si, g = units[i]
+            ys.append(H.gconv3_fwd(h, convs[i][0], si) if g != 1 else _conv_fwd(h, convs[i][0], si, k // 2, precise=precise))
             hs.append(h)
             ms += [s.mean, s.invstd]
         out, mask, tail = _se_tail_fwd(family, ys[-1], R, units[-1][2], convs[-1][1], convs[-1][2], f1w, f1b, f2w, f2b, res)
         _tap(out)
-        ctx.meta = [(k, precise) for k, precise, _ in units]
+        ctx.meta = [(k, precise, s, g) for k, precise, _, s, g in units]
         ctx.family, ctx.stride, ctx.R = family, stride, R
         ctx.gt = _tgt(*params)
         saved = [x, f1w, f2w, mask, *tail] + [t for c in convs for t in c] + ys + hs + ms
@@ -785,22 +810,28 @@ class SEBlockFunction(Function):
             wd, gd, bd, yd, md, idd = ds
             dyd, dgd, dbd = _bn_bwd(g, yd, R, md, idd, gd, bd, 0, t[3 * n + 5], t[3 * n + 6], dx=g)
         for i in range(n - 1, 0, -1):
-            k, precise = ctx.meta[i]
-            grads[3 * i] = _wgrad(dy, hs[i], k, 1, k // 2, t[3 * i], precise=precise)
-            dh = _conv_dgrad(dy, convs[i][0], 1, k // 2, ys[i - 1].shape[1], precise=precise)
+            k, precise, si, grp = ctx.meta[i]
+            if grp != 1:
+                grads[3 * i] = _gconv_wgrad(dy, hs[i], si, t[3 * i])
+                dh = H.gconv3_dgrad(dy, convs[i][0], si, ys[i - 1].shape[1])
+            else:
+                grads[3 * i] = _wgrad(dy, hs[i], k, si, k // 2, t[3 * i], precise=precise)
+                dh = _conv_dgrad(dy, convs[i][0], si, k // 2, ys[i - 1].shape[1], precise=precise)
             dy, grads[3 * i - 2], grads[3 * i - 1] = _bn_bwd(dh, ys[i - 1], R, ms[2 * i - 2], ms[2 * i - 1], convs[i - 1][1],
                                                              convs[i - 1][2], 1, t[3 * i - 2], t[3 * i - 1], dx=dh)
-        (k1, precise1), w1 = ctx.meta[0], convs[0][0]
-        grads[0] = _wgrad(dy, x, k1, stride, k1 // 2, t[0], precise=precise1)
+        (k1, precise1, s1, _), w1 = ctx.meta[0], convs[0][0]
+        grads[0] = _wgrad(dy, x, k1, s1, k1 // 2, t[0], precise=precise1)
         if not ds:
-            dx = _conv_dgrad(dy, w1, stride, k1 // 2, lin, out=g, accumulate=True, precise=precise1)   # identity grad + conv path
+            dx = _conv_dgrad(dy, w1, s1, k1 // 2, lin, out=g, accumulate=True, precise=precise1)   # identity grad + conv path
             return (dx, None, None, None, None, None, *grads, *dgate)
         dwd = _wgrad(dyd, x, 1, stride, 0, t[3 * n + 4])
         if k1 == 3:
             dx = _entry_dgrad(ctx.entry, dy, w1, dyd, wd, stride, lin, precise=precise1)
-        else:                 # both k1 data gradients land on the same (every stride-th) positions: the second launch accumulates
+        else:                 # the downsample's data gradient FIRST: its non-accumulating form writes every position of dx, zeros
+            # where its stride does not reach.  conv1's then accumulates -- on the same every stride-th positions in the
+            # SE-ResNet bottleneck (conv1 carries the block's stride), on ALL positions in the ResNeXt one (conv1 is stride 1)
             dx = _conv_dgrad(dyd, wd, stride, 0, lin)
-            dx = _conv_dgrad(dy, w1, stride, 0, lin, out=dx, accumulate=True)
+            dx = _conv_dgrad(dy, w1, s1, 0, lin, out=dx, accumulate=True)
         return (dx, None, None, None, None, None, *grads, *dgate, dwd, dgd, dbd)
 
 

@@ -1784,3 +1784,4 @@ from .se_ops import NARROW as SE_NARROW, WIDE as SE_WIDE        # noqa: E402,F40
 from .vgg_ops import (vgg_stats, bn_relu_maxpool2_fwd, bn_relu_maxpool2_bwd, bn_mean_bias,   # noqa: E402,F401
                       adaptive_avgpool_flat_fwd, adaptive_avgpool_flat_bwd)
 from .gradcam_ops import GradCamOutputs, gradcam, gradcam_shape_ok, gradcam_workspace   # noqa: E402,F401
+from .gconv_ops import gconv3_ok, gconv3_plan, gconv3_fwd, gconv3_dgrad, gconv3_wgrad   # noqa: E402,F401

@@ -1,13 +1,16 @@
-"""1-D SE-ResNet breath blocks (se_resnet18 / 50 / 101 / 152) on MI355X.
+"""1-D SE-ResNet / SE-ResNeXt breath blocks (se_resnet18 / 50 / 101 / 152, se_resnext50_32x4d / 101_32x4d) on MI355X.
 
 Operator surface of reference ``deepards/models/senet.py`` (SEModule :15-34, SEBasicBlock :37-68, Bottleneck :71-95,
-SEResNetBottleneck :122-144, SENet :171-328, se_resnet18 :343-348, se_resnet50 / 101 / 152 :351-372): same constructor arguments, sub-module / parameter names and their order (so ``state_dict`` keys
+SEResNetBottleneck :122-144, SEResNeXtBottleneck :147-168, SENet :171-328, se_resnet18 :343-348, se_resnet50 / 101 / 152
+:351-372, se_resnext50_32x4d / se_resnext101_32x4d :375-388): same constructor arguments, sub-module / parameter names and their order (so ``state_dict`` keys
 match), ``n_out_filters`` and ``network_name``.  As in ``resnet.py`` the torch.nn leaf modules are only parameter containers:
 ``forward`` runs the HIP kernels through ``deepards_amd.functional`` on a whole batch of windows.
 
 Built: the BasicBlock and the SE-ResNet Bottleneck variants on the k7 stem (``se_resnet18``, ``se_resnet50`` / ``101`` /
-``152`` and other ``layers`` lists).  The grouped-conv / 3x3-stem nets (``senet18``, ``senet154``) and the SENet-154 /
-ResNeXt bottlenecks (``SEBottleneck``, ``SEResNeXtBottleneck``) are refused in the constructor.  Initialisation is
+``152`` and other ``layers`` lists), and the ResNeXt 32x4d bottleneck on the same stem (``se_resnext50_32x4d`` /
+``se_resnext101_32x4d``: 32 groups, base width 4; its grouped conv2 runs on ``H.gconv3_*``; the block class and the two
+factories live in ``models/seresnext.py``).  The 3x3-stem nets (``senet18``,
+``senet154``), the SENet-154 bottleneck (``SEBottleneck``, 64 groups) and every other group count are refused in the constructor.  Initialisation is
 torch's defaults: the reference's SENet has no init loop.
 """
 from collections import OrderedDict
@@ -30,15 +33,17 @@ class SEModule(nn.Module):
         self.sigmoid = nn.Sigmoid()
 
 
-def _se_block(blk, x, R, units, family):
-    """F_.SEBlockFunction on block ``blk``: ``units`` = its (conv, BatchNorm, precise) in order, ``family`` its gate kernels'."""
+def _se_block(blk, x, R, units, family, own=False):
+    """F_.SEBlockFunction on block ``blk``: ``units`` = its (conv, BatchNorm, precise) in order, ``family`` its gate kernels'.
+    own: every unit carries its conv's own stride and group count (the ResNeXt form) instead of the block's stride on the first."""
     ds, se = blk.downsample, blk.se_module
     params = [t for conv, bn, _ in units for t in (conv.weight, bn.weight, bn.bias)]
     params += [se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias]
     if ds is not None:
         params += [ds[0].weight, ds[1].weight, ds[1].bias]
     return F_.SEBlockFunction.apply(x, blk.stride, R, family,
-                                    [(conv.kernel_size[0], precise, F_.BNState(bn)) for conv, bn, precise in units],
+                                    [(conv.kernel_size[0], precise, F_.BNState(bn)) + ((conv.stride[0], conv.groups) if own else ())
+                                     for conv, bn, precise in units],
                                     None if ds is None else F_.BNState(ds[1]), *params)
 
 
@@ -105,7 +110,7 @@ class SEResNetBottleneck(nn.Module):
 
 
 class SENet(Backbone):
-    """Four stages of SEBasicBlocks or SEResNetBottlenecks behind layer0 = conv k7 s2 -> BN -> ReLU -> MaxPool1d(3, 2, ceil_mode=True).  The module
+    """Four stages of SEBasicBlocks, SEResNetBottlenecks or SEResNeXtBottlenecks behind layer0 = conv k7 s2 -> BN -> ReLU -> MaxPool1d(3, 2, ceil_mode=True).  The module
     tree (names, order, shapes) is the reference's (senet.py:219-289)."""
 
     f32_only = ('SE-ResNets', 'the SE tail has no bf16 / f32x3p forms')
@@ -113,10 +118,14 @@ class SENet(Backbone):
     def __init__(self, block, layers, groups, reduction, dropout_p=0.2, inplanes=128, input_3x3=True, downsample_kernel_size=3,
                  downsample_padding=1):
         super(SENet, self).__init__()
-        if block not in (SEBasicBlock, SEResNetBottleneck):
-            raise NotImplementedError('only SEBasicBlock (se_resnet18 style) and SEResNetBottleneck (se_resnet50 style) are on '
-                                      'the accelerated path')
-        if groups != 1:
+        from .seresnext import SEResNeXtBottleneck      # (imported here: that module builds on this one)
+        if block not in (SEBasicBlock, SEResNetBottleneck, SEResNeXtBottleneck):
+            raise NotImplementedError('only SEBasicBlock (se_resnet18 style), SEResNetBottleneck (se_resnet50 style) and '
+                                      'SEResNeXtBottleneck (se_resnext50_32x4d style) are on the accelerated path')
+        if block is SEResNeXtBottleneck:
+            if groups != 32:
+                raise NotImplementedError('SEResNeXtBottleneck runs with groups = 32 (the 32x4d nets), got groups = %r' % (groups,))
+        elif groups != 1:
             raise NotImplementedError('grouped convolutions (senet18 / senet154, the ResNeXt nets) are not on the accelerated path')
         if input_3x3:
             raise NotImplementedError('the three-conv 3x3 stem (senet18 / senet154) is not on the accelerated path')
@@ -125,7 +134,7 @@ class SENet(Backbone):
         if (downsample_kernel_size, downsample_padding) != (1, 0):
             raise NotImplementedError('downsample convolutions other than k1 p0 (senet154) are not on the accelerated path')
         if inplanes != 64:
-            raise NotImplementedError('inplanes must be 64 (the SE-ResNets) on the accelerated path')
+            raise NotImplementedError('inplanes must be 64 (the SE-ResNets and SE-ResNeXts) on the accelerated path')
         self.inplanes = inplanes
         self.layer0 = nn.Sequential(OrderedDict([
             ('conv1', nn.Conv1d(1, inplanes, kernel_size=7, stride=2, padding=3, bias=False)),

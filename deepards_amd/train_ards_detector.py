@@ -1061,7 +1061,7 @@ def build_parser():
     true_false_flag('--cuda', 'run on the GPU(s): one process per GPU under torch.distributed.run')
     true_false_flag('--cuda-no-dp', 'run on the single GPU --cuda-device')
     parser.add_argument('-b', '--batch-size', type=int)
-    parser.add_argument('--base-network', choices=sorted(base_networks))
+    parser.add_argument('--base-network', choices=sorted(base_networks) + sorted(M.UNLISTED_BACKBONES))
     parser.add_argument('-nb', '--n-sub-batches', type=int)
     true_false_flag('--no-print-progress', '')
     parser.add_argument('--kfolds', type=int)

@@ -773,6 +773,33 @@ int da_siamese_head_bwd(const float* fa_pos, const float* fc_pos, const float* f
                         float* dfc_neg, int ldg, float* dW1, float* db1, float* dW2, float* db2, float* workspace, float gscale,
                         int accumulate, int B, int NB, int D, da_stream_t stream);
 
+/* ---- grouped k3 convolution (csrc/conv_grouped.hip): conv2 of the SE-ResNeXt 32x4d bottleneck, models/senet.py:147-168 ----
+ *     y[r][lo][co] = sum_{k < 3, j < cg} w[co][j][k] x[r][lo stride + k - 1][(co / cg) cg + j],   cg = C / 32, pad 1
+ * float32, channels-last maps x (rows, L, C), y (rows, Lo, C) with Lo = (L - 1) / stride + 1, without a channel pitch; the
+ * weight in torch's layout (C, cg, 3), no pack.  Shapes (da_gconv3_shape_ok): groups == 32, C in {128, 256, 512, 1024},
+ * stride 1 / 2; any rows >= 1, L >= 1 with rows L C < 2^31.  Every pointer 16-byte aligned.  Pads are predicated, nothing
+ * outside a map is read or written.  Each entry launches on `stream` only, allocates nothing and never synchronises.
+ *   da_gconv3_plan    which = 0 forward, 1 data gradient, 2 weight gradient: grid[3], block[3], static LDS bytes and workspace
+ *                     bytes of the launch, from the expressions the launch itself uses; launches nothing.  DA_EINVAL -- and
+ *                     from the launch entries too, before anything is launched -- for a shape without a legal launch (not
+ *                     shape_ok, rows or L < 1, a map of 2^31 elements or more, a grid dimension or LDS over the limits).
+ *   da_gconv3_tiling  the same plan's tiles: positions of the destination map per tile (of one row), tiles a block walks (for
+ *                     which = 2: tiles per partial chunk), tiles in all (rows * ceil(Ldst / positions)).
+ *   da_gconv3_fwd     y, every element written.
+ *   da_gconv3_dgrad   dx (rows, Lin, C) from dy (rows, Lo, C): every element written (zero where no tap reaches), or -- accumulate
+ *                     -- added to.
+ *   da_gconv3_wgrad   dw (C, cg, 3) (+)= sum over rows Lo positions: one partial per chunk of tiles into `workspace` (plan bytes,
+ *                     written before it is read), folded by a second launch in an order fixed by the chunk count.  No atomics: the order is a function
+ *                     of (rows, Lin, C, stride) alone, the same input gives the same bits. */
+int da_gconv3_shape_ok(int C, int groups, int stride);
+int da_gconv3_plan(int which, int rows, int L, int C, int stride, int* grid, int* block, size_t* lds, size_t* workspace);
+int da_gconv3_tiling(int which, int rows, int L, int C, int stride, int* tile_positions, int* tiles_per_block, int* tiles);
+int da_gconv3_fwd(const float* x, const float* w, float* y, int rows, int L, int C, int stride, da_stream_t stream);
+int da_gconv3_dgrad(const float* dy, const float* w, float* dx, int rows, int Lin, int C, int stride, int accumulate,
+                    da_stream_t stream);
+int da_gconv3_wgrad(const float* dy, const float* x, float* dw, float* workspace, int rows, int Lin, int C, int stride,
+                    int accumulate, da_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
