@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
            'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip',
-           'siamese.hip', 'conv_grouped.hip']
+           'siamese.hip', 'conv_grouped.hip', 'autoencoder.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -240,6 +240,16 @@ SIGNATURES = {
     'da_gconv3_fwd': (_I, [_P] * 3 + [_I] * 4 + [_P]),
     'da_gconv3_dgrad': (_I, [_P] * 3 + [_I] * 5 + [_P]),
     'da_gconv3_wgrad': (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    'da_bn_maxpool2_idx_fwd': (_I, [_P, _I, _P, _P, _P] + [_I] * 4 + [_P] * 5),
+    'da_bn_maxpool2_idx_plan': (_I, [_I] * 4 + [_IP, _IP, ctypes.POINTER(_Z)]),
+    'da_bn_maxpool2_idx_bwd_workspace': (_Z, [_I] * 4),
+    'da_bn_maxpool2_idx_bwd': (_I, [_P, _P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P] * 5),
+    'da_unpool2_fwd': (_I, [_P] * 4 + [_I] * 3 + [_P]),
+    'da_unpool2_bwd': (_I, [_P] * 3 + [_I] * 3 + [_P]),
+    'da_ae_out_fwd_workspace': (_Z, [_I, _I]),
+    'da_ae_out_bwd_workspace': (_Z, [_I, _I]),
+    'da_ae_out_fwd': (_I, [_P] * 10 + [_I, _I, _P]),
+    'da_ae_out_bwd': (_I, [_P] * 9 + [_I, _I, _I, _P]),
 }
 
 

@@ -1,0 +1,161 @@
+"""Autoencoder pretraining on MI355X: the trainer and the command line.
+
+The reference's ``network_map['autoencoder']`` (``AutoencoderModel``, train_ards_detector.py:1102-1116): an ``AutoencoderNetwork``
+(models/autoencoder_cnn.py, models/autoencoder_network.py) trained to reproduce its input rows under ``MSELoss``; the test epoch
+books ``test_mae``, ``r2`` and ``test_mse`` per batch (``RegressorMixin``, :661-677).
+
+    python -m deepards_amd.autoencoder -n autoencoder --base-network basic_cnn_ae --cuda-no-dp -p <dataset.pkl | .npz> \\
+           --test-from-pickle <...> --save-model pretrained_ae.pth
+
+* ``AutoencoderTrainer``: one step = the whole network and its loss as one autograd node (``functional.AutoencoderFunction``),
+  the batched parameter-gradient folds and the fused optimiser -- eager, or a captured graph per input shape, the loss on the
+  device.  ``test_step`` runs under ``model.eval()`` (BatchNorm on its running statistics) and returns the reconstruction.
+* any prepared ``ARDSRawDataset`` pickle or ``.npz`` serves; targets are ignored (the reference's ``_autoencoder_target`` is NaN).
+
+Refused: more than one GPU and folds in flight (BatchNorm runs over the WHOLE batch, so a split batch is another function), bf16 /
+f32x3p arithmetic, ``--load-base-network`` / ``--freeze-base-network`` (the second stage is not built), lengths that are no
+multiple of 16.  A saved autoencoder is not accepted as a base network (``checkpoint.load_autoencoder`` reads it back).
+"""
+import torch
+
+from . import functional as F_
+from .models.autoencoder import AutoencoderCNN, AutoencoderNetwork
+from .train import HotPathTrainer, epoch_shards_on_device
+
+AUTOENCODER_NETWORKS = ('autoencoder',)
+AUTOENCODER_BASE_NETWORK = 'basic_cnn_ae'
+AUTOENCODER_DATASET_TYPE = 'unpadded_downsampled_autoencoder_sequences'
+
+
+class AutoencoderTrainer(HotPathTrainer):
+    """One autoencoder on one GPU.  ``train_step(inputs)``: one iteration of the reference's batch loop on windows (B, NB, 1, L)
+    (an ``AutoencoderNetwork``) or rows (N, 1, L) (an ``AutoencoderCNN``) -- eager, or a captured graph per input shape -- with the
+    optimiser and clamp of ``HotPathTrainer``; returns the device-resident loss (``last_loss``; ``last_logits`` is the
+    reconstruction).  ``test_step(inputs)``: the forward under ``model.eval()`` -> recon (N, 1, L); ``last_test_loss`` its MSE."""
+
+    def __init__(self, model, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9, clip_grad=True, clip_val=0.01,
+                 world_size=1, rank=0, process_group=None, use_graph=True, folds_in_flight=None):
+        if not isinstance(model, (AutoencoderNetwork, AutoencoderCNN)):
+            raise TypeError('AutoencoderTrainer trains an AutoencoderNetwork / AutoencoderCNN, got %s' % type(model).__name__)
+        if world_size != 1:
+            raise NotImplementedError('the autoencoder trainer runs on one GPU: its BatchNorm takes its statistics over the whole '
+                                      'batch, so a batch sharded over %d ranks is a different function' % world_size)
+        if folds_in_flight is not None and int(folds_in_flight) > 1:
+            raise NotImplementedError('folds in flight with the autoencoder trainer: one model, one whole-batch BatchNorm per step')
+        F_._ae_f32_only()
+        super(AutoencoderTrainer, self).__init__(model, optimizer=optimizer, learning_rate=learning_rate, weight_decay=weight_decay,
+                                                 momentum=momentum, clip_grad=clip_grad, clip_val=clip_val, world_size=1, rank=0,
+                                                 process_group=None, use_graph=use_graph)
+        self.eval_test = True                             # BatchNorm on running statistics: built for this network
+        self.last_test_loss = None
+        self._no_target = None
+
+    def _placeholder(self, inputs):
+        """The base class's steps carry a target; there is none here (the input is its own target)."""
+        ent = self._graphs.get(tuple(inputs.shape))
+        if ent is not None:
+            return ent[1][1]
+        if self._no_target is None or self._no_target.device != inputs.device:
+            self._no_target = torch.zeros(1, device=inputs.device, dtype=torch.float32)
+        return self._no_target
+
+    def _check_batch(self, batch):
+        want = 4 if isinstance(self.model, AutoencoderNetwork) else 3
+        if batch.dim() != want or batch.shape[0] == 0:
+            raise ValueError('an autoencoder step takes %s, got %s' %
+                             ('(B, NB, 1, L) windows' if want == 4 else '(N, 1, L) rows', tuple(batch.shape)))
+
+    def _forward_backward(self, inputs, target, zero_grad=False):
+        if zero_grad:
+            self.bucket.zero_grad()
+        with F_.training_step(self.model):
+            loss, recon = self.model.forward_loss(inputs)
+            F_.flush_forward(defer=True)
+            torch.autograd.backward(loss, grad_tensors=self._one(loss))
+            F_.flush_backward()
+        return loss.detach(), recon
+
+    def train_step(self, batch, target=None, reset=None):
+        if target is not None or reset is not None:
+            raise ValueError('an autoencoder step takes the batch alone: the input is its own target')
+        self._check_batch(batch)
+        return super(AutoencoderTrainer, self).train_step(batch, self._placeholder(batch))
+
+    def _test_forward(self, inputs, target):
+        with torch.no_grad(), F_.training_step(self.model):
+            loss, recon = self.model.forward_loss(inputs)
+            F_.flush_forward()
+        return loss, recon
+
+    def test_step(self, batch, target=None, reset=None):
+        if target is not None or reset is not None:
+            raise ValueError('an autoencoder step takes the batch alone: the input is its own target')
+        self._check_batch(batch)
+        if not self.use_graph:
+            if self.model.training:
+                self.model.eval()
+            loss, recon = self._test_forward(batch, None)
+        else:
+            ent = self._test_graphs.get((tuple(batch.shape), (1,)))
+            loss, recon = super(AutoencoderTrainer, self).test_step(batch, ent[1][1] if ent is not None else self._placeholder(batch))
+        self.last_test_loss = loss
+        return recon
+
+
+def run_autoencoder_train_epoch(trainer, store, batch_size=16, shuffle=True, generator=None):
+    """Yields the (cloned, device-resident) loss of every batch: a gather launch and the step."""
+    for idx in epoch_shards_on_device(store, batch_size, shuffle, generator):
+        x, _ = store.batch_from_device(idx)
+        yield trainer.train_step(x).clone()
+
+
+def run_autoencoder_test_epoch(trainer, store, batch_size=16, shuffle=True, generator=None):
+    """Yields (inputs (B, NB, 1, L), recon (B NB, 1, L), loss (1,)) of every batch, on the device."""
+    for idx in epoch_shards_on_device(store, batch_size, shuffle, generator):
+        x, _ = store.batch_from_device(idx)
+        recon = trainer.test_step(x)
+        yield x, recon, trainer.last_test_loss.clone()
+
+
+def build_parser():
+    """The driver's parser with this stage's own ``-n`` / ``--base-network`` choices and its dataset type."""
+    from . import train_ards_detector as T
+    parser = T.build_parser()
+    parser.prog = 'deepards_amd.autoencoder'
+    for action in parser._actions:
+        if action.dest == 'network':
+            action.choices = list(AUTOENCODER_NETWORKS)
+        elif action.dest == 'base_network':
+            action.choices = list(action.choices) + [AUTOENCODER_BASE_NETWORK]
+    return parser
+
+
+def main(argv=None):
+    """``python -m deepards_amd.autoencoder -n autoencoder <the driver's flags>``."""
+    import sys
+    from . import train_ards_detector as T
+    from .config import Configuration
+    argv = sys.argv[1:] if argv is None else list(argv)
+    for a in argv:
+        if a.split('=')[0] in T.OUT_OF_SCOPE_FLAGS:
+            raise SystemExit('%s steers code outside the accelerated hot path and is not accepted by this build' % a.split('=')[0])
+    args = Configuration(build_parser().parse_args(argv), dict(T.BUILD_DEFAULTS))
+    if args.network not in AUTOENCODER_NETWORKS:
+        raise SystemExit('-n must be one of %s' % ', '.join(AUTOENCODER_NETWORKS))
+    if args.save_model_per_epoch and not args.save_model:
+        raise Exception('Must specify a filename to save your model using --save-model')
+    cls = T.autoencoder_network_map[args.network](args)
+    results = cls.train_and_test()
+    cls.perform_post_modeling_actions()
+    return cls, results
+
+
+def __getattr__(name):
+    if name == 'autoencoder_network_map':                 # (lives beside the driver's other maps; importing it here would be circular)
+        from . import train_ards_detector as T
+        return T.autoencoder_network_map
+    raise AttributeError(name)
+
+
+if __name__ == '__main__':
+    main()

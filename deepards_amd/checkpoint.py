@@ -251,9 +251,9 @@ def _own_module_classes():
     deepards_amd.models.* and torch.nn's own module classes (containers, Conv1d / BatchNorm1d / Linear / LSTM ... that
     the models hold as parameter containers)."""
     import inspect
-    from .models import densenet, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, vgg
+    from .models import autoencoder, densenet, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, vgg
     allow = []
-    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese):
+    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese, autoencoder):
         allow += [c for c in vars(mod).values()
                   if inspect.isclass(c) and issubclass(c, torch.nn.Module) and c.__module__ == mod.__name__]
     allow += [c for c in vars(torch.nn).values() if inspect.isclass(c) and issubclass(c, torch.nn.Module)]
@@ -290,10 +290,12 @@ def load_model_weights(path, build_model):
 
 
 # The reference's other pretraining route saves an AutoencoderNetwork (models/autoencoder_network.py: ``base_network`` an
-# AutoencoderCNN, ``breath_block`` its nn.Sequential encoder).  Neither that network nor the second stage is built here.
-AUTOENCODER_CHECKPOINT = ('%s is an autoencoder checkpoint: autoencoder pretraining is not built in this package, and neither is its '
-                          'second stage, loading the breath_block (the encoder) into a classifier -- which the reference cannot run '
-                          'either: its get_base_network reads network_name off the nn.Sequential that breath_block is')
+# AutoencoderCNN, ``breath_block`` its nn.Sequential encoder).  The network is built (models/autoencoder.py, ``load_autoencoder``
+# below); the second stage is not, so such a file is not accepted as a base network.
+AUTOENCODER_CHECKPOINT = ('%s is an autoencoder checkpoint: taking one as a base network is not built in this package -- that is the '
+                          'second stage, loading the breath_block (the encoder) into a classifier, which the reference cannot run '
+                          'either: its get_base_network reads network_name off the nn.Sequential that breath_block is.  '
+                          'checkpoint.load_autoencoder reads it for evaluation or for resuming the pretraining')
 
 
 def _refuse_autoencoder(path, class_name=None, keys=()):
@@ -316,6 +318,7 @@ def load_base_network(path, base_networks, build_args=None):
         saved = load_own_module(path)
         if isinstance(saved, torch.nn.DataParallel):
             saved = saved.module
+        _refuse_autoencoder(path, '%s.%s' % (type(saved).__module__, type(saved).__name__))
         return saved.breath_block
     if kind == 'state_dict':
         sd, name = torch.load(path, weights_only=True, map_location='cpu'), None
@@ -336,6 +339,31 @@ def load_base_network(path, base_networks, build_args=None):
     net = M.build_base_network(name, build_args)
     net.load_state_dict(bb, strict=True)
     return net
+
+
+def load_autoencoder(path):
+    """An ``AutoencoderNetwork`` from a saved autoencoder, for evaluation and for resuming: a whole module this package saved
+    (restricted unpickler), a module the reference pickled (read without unpickling) or a state_dict file with the reference's
+    keys.  A state_dict may leave out BatchNorm's buffers (they keep torch's initial values); any other missing or unknown key
+    raises."""
+    from .models.autoencoder import AutoencoderCNN, AutoencoderNetwork
+    kind = checkpoint_kind(path)
+    if kind == 'own':
+        model = load_own_module(path)
+        if isinstance(model, torch.nn.DataParallel):
+            model = model.module
+        if not isinstance(model, AutoencoderNetwork):
+            raise ValueError('%s holds a %s, not an AutoencoderNetwork' % (path, type(model).__name__))
+        return model
+    sd = torch.load(path, weights_only=True, map_location='cpu') if kind == 'state_dict' else \
+        read_module_checkpoint(path)['state_dict']
+    sd = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in sd.items())
+    model = AutoencoderNetwork(AutoencoderCNN())
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    missing = [k for k in missing if k.split('.')[-1] not in ('running_mean', 'running_var', 'num_batches_tracked')]
+    if missing or unexpected:
+        raise ValueError('%s is not an autoencoder checkpoint: missing keys %s, unknown keys %s' % (path, missing[:4], list(unexpected)[:4]))
+    return model
 
 
 def model_save_path(save_model, saved_models_dir, n_kfolds, fold_num, epoch_num=None):

@@ -911,6 +911,130 @@ class AdaptiveAvgPoolFlatFunction(Function):
         return H.adaptive_avgpool_flat_bwd(dfeat.contiguous(), ctx.lin, ctx.lout), None
 
 
+def _ae_f32_only():
+    if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
+        raise NotImplementedError('the autoencoder runs with fp32 conv arithmetic and float activation storage only: its pool-with-'
+                                  'index, unpool and output-stage kernels have no bf16 / f32x3p forms (DA_CONV_DTYPE=%s, storage %s)'
+                                  % (H.CONV_DTYPE, H.act_dtype()))
+
+
+def _ae_down_conv(h, k, w, precise):
+    """The conv of down stage k (0-based) WITHOUT its bias: the (1, 3, 1) stem conv on the raw rows, then k3 p1 convs."""
+    return H.stem_conv_fwd(h, w, stride=1) if k == 0 else _conv_fwd(h, w, 1, 1, precise=precise)
+
+
+def ae_encode(x, down, sts, training, sels=None, precise=False):
+    """The four down stages, forward only (no autograd node): x (rows, L) -> (h4 (rows, L / 16, 512), the four decision
+    tensors).  ``down``: (w, bias, gamma, beta) per stage, ``sts`` their BNState.  training: batch statistics over ALL rows as one
+    window, and the running update; else BatchNorm is the per-channel affine of the running statistics -- mean = running_mean -
+    conv bias (the stored conv output has no bias), invstd = rsqrt(running_var + eps) -- with no statistics launch."""
+    _ae_f32_only()
+    rows, h, out_sels = x.shape[0], x, []
+    for k, ((w, b, g, be), st) in enumerate(zip(down, sts)):
+        y = _ae_down_conv(h, k, w, precise)
+        if training:
+            mean, invstd = H.vgg_stats(y, rows, st.eps)
+            if st.running_mean is not None:
+                _running(H.bn_mean_bias(mean, b), invstd, rows * y.shape[1], st)
+        else:
+            mean = (st.running_mean - b).view(1, -1).contiguous()
+            invstd = torch.rsqrt(st.running_var + st.eps).view(1, -1).contiguous()
+        h, sel = H.bn_maxpool2_idx_fwd(y, rows, mean, invstd, g, be, sel_in=None if sels is None else sels[k])
+        out_sels.append(sel)
+    return h, out_sels
+
+
+def ae_decode(h4, sels, up, x, precise=False):
+    """The four up stages and the loss, forward only: -> recon (rows, L), dr, loss (1,), and what a backward reads (u1..u3, c3)."""
+    u, c, bias, us = None, h4, None, []
+    for k in range(3):
+        w = up[k][0]
+        u = H.unpool2_fwd(c, sels[3 - k], bias)                       # (the ConvT in front stored no bias: added here)
+        c = _conv_dgrad(u, w, 1, 1, u.shape[1], precise=precise)      # ConvTranspose1d(k3, p1) = the data gradient of a Conv1d
+        bias = up[k][1]
+        us.append(u)
+    recon, dr, loss = H.ae_out_fwd(c, bias, sels[0], up[3][0], up[3][1], x)
+    return recon, dr, loss, us, c
+
+
+class AutoencoderFunction(Function):
+    """The whole autoencoder (reference models/autoencoder_cnn.py:43-66) and its MSE against the input as ONE autograd node:
+    four Conv1d(k3, p1, bias) -> BatchNorm1d -> MaxPool1d(2, return_indices) stages, four MaxUnpool1d(2) -> ConvTranspose1d(k3,
+    p1, bias) stages, NO ReLU; all rows are one BatchNorm window.  x (rows, L) -> (recon (rows, L), loss (1,)); the gradient is the
+    loss's (recon is marked non-differentiable, the incoming gradient of the loss is taken as 1, as HeadLossFunction does).
+
+    The down convs' biases are handled as VGGStageFunction handles its own (never added to the stored conv output,
+    H.bn_mean_bias in front of the running update, gradient exactly 0).  A ConvTranspose1d is the data gradient of the Conv1d
+    whose weight is its own (Ci, Co, 3) read as (Cout, Cin, 3): forward _conv_dgrad, input gradient _conv_fwd, weight gradient
+    _wgrad with the operands swapped.  Its stored output has no bias: the unpool (or the output stage) behind it adds it, and the
+    bias gradient is the column sum of the gradient at that output.  ``sels``: four decision tensors to take instead of deciding
+    (teacher forcing); ``tap``: a list that receives the four decision tensors of this run, or None.  params: (w, bias, gamma,
+    beta) x 4, then (w, bias) x 4."""
+
+    @staticmethod
+    def forward(ctx, x, sts, sels, precise, tap, *params):
+        _ae_f32_only()
+        rows = x.shape[0]
+        down, up = [params[4 * k:4 * k + 4] for k in range(4)], [params[16 + 2 * k:18 + 2 * k] for k in range(4)]
+        h, ys, hs, stats, out_sels = x, [], [], [], []
+        for k, ((w, b, g, be), st) in enumerate(zip(down, sts)):
+            y = _ae_down_conv(h, k, w, precise)
+            mean, invstd = H.vgg_stats(y, rows, st.eps)
+            hs.append(h)
+            h, sel = H.bn_maxpool2_idx_fwd(y, rows, mean, invstd, g, be, sel_in=None if sels is None else sels[k])
+            tb = _tgt(b)[0]
+            zero_bias = tb is not None and _OV['on']    # no zero-fill in this step: the bias gradient's 0 is written here
+            if st.running_mean is not None or zero_bias:
+                _running(H.bn_mean_bias(mean, b, dbias=tb if zero_bias else None), invstd, rows * y.shape[1], st)
+            ys.append(y)
+            stats += [mean, invstd]
+            out_sels.append(sel)
+        recon, dr, loss, us, c3 = ae_decode(h, out_sels, up, x, precise)
+        ctx.precise, ctx.gt = bool(precise), [_tgt(*p) for p in down] + [_tgt(*p) for p in up]
+        ctx.save_for_backward(x, *params, *ys, *hs[1:], *stats, *out_sels, *us, c3, dr)
+        ctx.mark_non_differentiable(recon)
+        if tap is not None:                                # (the decisions this run took or was given, for the caller)
+            tap[:] = out_sels
+        return recon, loss
+
+    @staticmethod
+    def backward(ctx, _drecon, _dloss):
+        s = ctx.saved_tensors
+        x, params = s[0], s[1:25]
+        ys, hs, stats, sels, us, c3, dr = s[25:29], (x,) + tuple(s[29:32]), s[32:40], s[40:44], s[44:47], s[47], s[48]
+        down, up = [params[4 * k:4 * k + 4] for k in range(4)], [params[16 + 2 * k:18 + 2 * k] for k in range(4)]
+        gt, precise, rows = ctx.gt, ctx.precise, x.shape[0]
+        gup = [None] * 8
+        # the output stage: conv_up4 and, through the unpool it forms on the fly, the gradient at conv_up3's output
+        tw, tb = gt[7]
+        direct = tw is not None and tb is not None
+        dc, dw4, db4 = H.ae_out_bwd(dr, c3, up[2][1], sels[0], up[3][0], dw4=tw if direct else None, db4=tb if direct else None,
+                                    accumulate=direct and _acc())
+        gup[6:8] = (None, None) if direct else (dw4, db4)
+        for k in (2, 1, 0):
+            (w, b), (tw, tb) = up[k], gt[4 + k]
+            db = H.reduce_rows(dc.view(-1, dc.shape[2]), out=tb, accumulate=tb is not None and _acc())
+            dw = _wgrad(us[k], dc, 3, 1, 1, tw, precise=precise)     # (the operands swapped: the result is (Ci, Co, 3))
+            du = _conv_fwd(dc, w, 1, 1, precise=precise)
+            dc = H.unpool2_bwd(du, sels[3 - k])
+            gup[2 * k:2 * k + 2] = dw, None if tb is not None else db
+        gdown, dh = [None] * 16, dc
+        for k in (3, 2, 1, 0):
+            (w, b, g, be), (tw, tb, tg, tbe) = down[k], gt[k]
+            dy, ds = H.bn_maxpool2_idx_bwd(dh, sels[k], ys[k], rows, stats[2 * k], stats[2 * k + 1], g, be)
+            dg, dbe = _bn_pgrad(ds, g, be, tg, tbe)
+            dbias = None if tb is not None else torch.zeros_like(b)
+            if k == 0:
+                direct = tw is not None
+                dw = H.stem_conv_wgrad(dy, x, out=tw, accumulate=direct and _acc(), k=3, stride=1)
+                dw = None if direct else dw
+            else:
+                dw = _wgrad(dy, hs[k], 3, 1, 1, tw, precise=precise)
+                dh = _conv_dgrad(dy, w, 1, 1, hs[k].shape[1], precise=precise)
+            gdown[4 * k:4 * k + 4] = dw, dbias, dg, dbe
+        return (None, None, None, None, None) + tuple(gdown) + tuple(gup)
+
+
 _STEM_TAIL = True         # inside a training step the stem's last weight-gradient fold rides on the tail launch
 _BF16_DGRAD_PAIR = True   # conv dtype bf16: a stride-2 block entry's two data gradients in one launch (tests compare with the two launches)
 _BN_PAIR = True           # a block entry's two independent BatchNorms (forward: bn1 | downsample; backward: bn2 | downsample) share a launch

@@ -1785,3 +1785,5 @@ from .vgg_ops import (vgg_stats, bn_relu_maxpool2_fwd, bn_relu_maxpool2_bwd, bn_
                       adaptive_avgpool_flat_fwd, adaptive_avgpool_flat_bwd)
 from .gradcam_ops import GradCamOutputs, gradcam, gradcam_shape_ok, gradcam_workspace   # noqa: E402,F401
 from .gconv_ops import gconv3_ok, gconv3_plan, gconv3_fwd, gconv3_dgrad, gconv3_wgrad   # noqa: E402,F401
+from .autoencoder_ops import (sel_from_bool, sel_to_bool, bn_maxpool2_idx_plan, bn_maxpool2_idx_fwd,   # noqa: E402,F401
+                              bn_maxpool2_idx_bwd, unpool2_fwd, unpool2_bwd, ae_out_fwd, ae_out_bwd)

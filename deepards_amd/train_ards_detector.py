@@ -1001,7 +1001,7 @@ def regression_scores(target, preds):
     (n_samples, n_outputs) arrays, in float64 numpy: the errors are averaged over the samples per output column, then over
     the columns; r2 per column is 1 - SS_res / SS_tot, and a constant column scores 1 when it is matched exactly, else 0
     (sklearn's ``force_finite``).  What the reference's RegressorMixin (:661-677) books as ``test_mae``, ``r2`` and ``test_mse``
-    per test batch, without importing sklearn; no model class of this package calls it yet."""
+    per test batch, without importing sklearn (``RegressorMixin.record_testing_results`` below)."""
     import numpy as np
     t, p = np.asarray(target, dtype=np.float64), np.asarray(preds, dtype=np.float64)
     if t.ndim == 1:
@@ -1017,6 +1017,121 @@ def regression_scores(target, preds):
     r2[ok] = 1.0 - num[ok] / den[ok]
     r2[~ok & (num != 0)] = 0.0
     return mae, float(np.mean(r2)), mse
+
+
+class RegressorMixin(object):
+    """:661-677: a test batch's (n_samples, n_outputs) targets and predictions booked as ``test_mae``, ``r2`` and ``test_mse``."""
+
+    def record_testing_results(self, target, batch_preds, fold_num):
+        mae, r2, mse = regression_scores(target, batch_preds)
+        self.results.update_meter('test_mae', fold_num, mae)
+        self.results.update_meter('r2', fold_num, r2)
+        self.results.update_meter('test_mse', fold_num, mse)
+
+    def record_final_epoch_testing_results(self, fold_num, epoch_num, test_dataset):
+        return self.results.get_meter('test_mae', fold_num)
+
+    def set_loss_criterion(self):
+        self.criterion = torch.nn.MSELoss()        # (for calc_loss on tensors somebody already has; the step computes it in-kernel)
+
+    def perform_post_modeling_actions(self):
+        """:676-677 saves the results object; here: the meters' means, returned and kept as ``self.summary``."""
+        self.summary = {}
+        for (name, fold), vals in self.results.meters.items():
+            host = [float(v.detach()) if isinstance(v, torch.Tensor) else float(v) for v in vals]
+            self.summary['%s/%s' % (name, fold)] = sum(host) / len(host) if host else None
+        return self.summary
+
+
+class AutoencoderModel(BaseTraining, RegressorMixin):
+    """:1102-1116.  NOT in ``network_map`` (its key set is pinned): reached through ``python -m deepards_amd.autoencoder -n
+    autoencoder`` (``autoencoder_network_map``) or built directly.  The network is ``AutoencoderNetwork(AutoencoderCNN())``
+    whatever ``--base-network`` says (the reference's ``basic_cnn_ae``); any prepared dataset serves, its targets are ignored.
+    ``get_optimizer`` returns an ``AutoencoderTrainer``; the test epoch runs under ``model.eval()`` and books ``test_loss``,
+    ``test_mae``, ``r2`` and ``test_mse`` per batch.  One GPU, no folds in flight (BatchNorm over the whole batch is a different
+    function when the batch is split); ``--load-base-network`` / ``--freeze-base-network`` are refused: they belong to the second
+    stage -- a classifier on the pretrained encoder -- which is not built."""
+
+    def __init__(self, args):
+        if getattr(args, 'load_base_network', None):
+            raise NotImplementedError('--load-base-network with -n autoencoder: the network is always a fresh AutoencoderCNN; a saved '
+                                      'autoencoder resumes through --load-checkpoint, and a classifier\'s breath_block has no '
+                                      'decoder to load')
+        if _flag(args, 'freeze_base_network'):
+            raise NotImplementedError('--freeze-base-network with -n autoencoder: the base network IS the model being pretrained; '
+                                      'freezing it leaves nothing to train')
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise NotImplementedError('autoencoder pretraining runs on one GPU: its BatchNorm takes its statistics over the whole '
+                                      'batch, which a batch sharded over ranks changes')
+        n_flight = getattr(args, 'folds_in_flight', None)
+        if n_flight is not None and int(n_flight) > 1:
+            raise NotImplementedError('--folds-in-flight > 1 with -n autoencoder: the folds run one after the other')
+        args.folds_in_flight = 1
+        super(AutoencoderModel, self).__init__(args)
+
+    def _process_test_batch_results(self, outputs, target, inputs, fold_num):
+        batch_preds = outputs.detach().cpu().numpy().squeeze(1)
+        target = inputs.reshape(inputs.shape[0] * inputs.shape[1], inputs.shape[2], inputs.shape[3]).squeeze(1).cpu().numpy()
+        self.record_testing_results(target, batch_preds, fold_num)
+        return batch_preds.tolist()
+
+    def calc_loss(self, outputs, target, inputs):
+        return self.criterion(outputs, inputs.reshape(inputs.shape[0] * inputs.shape[1], inputs.shape[2], inputs.shape[3]))
+
+    def get_base_network(self):
+        return M.AutoencoderCNN()
+
+    def get_network(self, base_network):
+        return M.AutoencoderNetwork(base_network)
+
+    def get_model(self):
+        if self.args.load_checkpoint:
+            from .checkpoint import load_autoencoder
+            return self.model_cuda_wrapper(load_autoencoder(self.args.load_checkpoint))
+        return super(AutoencoderModel, self).get_model()
+
+    def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
+        from .autoencoder import AutoencoderTrainer
+        a = self.args
+        if a.optimizer not in ('adam', 'sgd'):
+            raise ValueError('optimizer must be adam or sgd')
+        return AutoencoderTrainer(model, optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
+                                  clip_grad=bool(_flag(a, 'clip_grad')), clip_val=a.clip_val, world_size=world_size, rank=rank,
+                                  process_group=process_group, use_graph=_flag(a, 'use_graph', True))
+
+    def _generator(self, fold_num, epoch_num, salt=0):
+        if self.args.seed is None:
+            return None
+        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + salt)
+
+    def run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num):
+        from .autoencoder import run_autoencoder_train_epoch
+        store, batch_size, shuffle = train_loader
+        if optimizer.model is not model:
+            raise ValueError('optimizer was built for another model')
+        for loss in run_autoencoder_train_epoch(optimizer, store, batch_size=batch_size, shuffle=shuffle,
+                                                generator=self._generator(fold_num, epoch_num)):
+            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
+            self.results.update_meter('loss', fold_num, loss)
+            if _flag(self.args, 'debug'):
+                break
+
+    def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
+        from .autoencoder import run_autoencoder_test_epoch
+        store, batch_size, shuffle = test_loader
+        made = optimizer is None
+        trainer = self.get_optimizer(model) if made else optimizer
+        self.preds = []
+        for x, recon, loss in run_autoencoder_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
+                                                         generator=self._generator(fold_num, epoch_num, 500009)):
+            self.results.update_meter('test_loss', fold_num, loss)
+            self.preds += self._process_test_batch_results(recon, None, x, fold_num)
+        if made:
+            trainer.release_graphs()
+        return {k: self.results.get_meter(k, fold_num) for k in ('test_mae', 'r2', 'test_mse')}
+
+
+autoencoder_network_map = {'autoencoder': AutoencoderModel}
 
 
 network_map = {
@@ -1072,7 +1187,8 @@ def build_parser():
     parser.add_argument('--optimizer', choices=['adam', 'sgd'])
     parser.add_argument('-dt', '--dataset-type', choices=['unpadded_centered_sequences', 'padded_breath_by_breath',
                                                           'padded_breath_by_breath_with_flow_time_features',
-                                                          'unpadded_centered_with_bm'])
+                                                          'unpadded_centered_with_bm',
+                                                          'unpadded_downsampled_autoencoder_sequences'])
     parser.add_argument('-lr', '--learning-rate', type=float)
     parser.add_argument('--loader-threads', type=int, help='accepted and ignored: batches are gathered on the device')
     parser.add_argument('--save-model', help='save the model to a specific file')

@@ -653,6 +653,44 @@ int da_bn_mean_bias(const float* mean, const float* bias, float* mean_b, int W, 
 int da_adaptive_avgpool_flat_fwd(const float* x, float* feat, int rows, int Lin, int Lout, int C, da_stream_t stream);
 int da_adaptive_avgpool_flat_bwd(const float* dfeat, float* dx, int rows, int Lin, int Lout, int C, da_stream_t stream);
 
+/* ---- the autoencoder's own layers (csrc/autoencoder.hip; reference models/autoencoder_cnn.py): BatchNorm + MaxPool1d(2) that
+ * keeps its decisions, MaxUnpool1d(2), and ConvTranspose1d(64, 1, 3, padding=1) + MSELoss.  NO ReLU anywhere.
+ * float activations [rows][L][C] channels-last, float storage only.  A pool decision is one bit per pooled element, set where
+ * the SECOND member of the pair is strictly greater (a tie, -0.0 against +0.0 included, keeps the first), 32 channels to a
+ * uint32: word ((row Lo + j) C + c) / 32, bit c % 32.  Shapes: C a multiple of 32, Lin even and >= 2, R dividing rows, ldy >= C a
+ * multiple of 4, rows Lin ldy < 2^32; anything else, or a NULL operand, -> DA_EINVAL before any launch.  Every sum runs in an
+ * order fixed by the shape (no atomics); each entry launches on `stream` only, allocates nothing and never synchronises.
+ *   da_bn_maxpool2_idx_fwd   z = fmaf(y, gamma invstd, beta - mean gamma invstd) (never stored); out[j] = sel ? z[2j+1] : z[2j].
+ *                            sel_in NULL: decides on z and writes sel; else takes sel_in's bits (sel NULL or a copy's destination)
+ *   da_bn_maxpool2_idx_plan  chunk geometry of the backward, launching nothing: a window's R Lin / 2 pairs in `chunks` runs of
+ *                            `chunk_pairs` (the last shorter), and the workspace bytes
+ *   da_bn_maxpool2_idx_bwd   dz[2j + sel] = dout[j], the partner 0; then BatchNorm's backward: dy [rows][Lin][C] and
+ *                            ds [2][W][C] (for da_bn_param_grad_multi), the window sums as chunk partials folded in chunk order
+ *   da_unpool2_fwd / _bwd    out[2j + sel] = v[j] + bias[c] (bias NULL: none), the partner exactly +0.0, every element written;
+ *                            dv[j] = dout[2j + sel]
+ *   da_ae_out_fwd            v [rows][L / 2][64], u = unpool(v + bias3, sel1) formed on the fly:
+ *                            recon[n][l] = bias4 + sum_{c,t} u[n][l + 1 - t][c] w4[c][0][t];  dr = 2 (recon - x) / (rows L);
+ *                            loss[0] = mean (recon - x)^2 from per-block partials (da_ae_out_fwd_workspace bytes) in block order
+ *   da_ae_out_bwd            dv[n][j][c] = sum_t dr[n][2j + sel - 1 + t] w4[c][t] (the gradient at v + bias3),
+ *                            dw4[c][t] (+)= sum_{n,j} (v + bias3)[n][j][c] dr[n][2j + sel - 1 + t],  db4 (+)= sum dr; dr outside a
+ *                            row counts as 0; block records (da_ae_out_bwd_workspace bytes) folded in block order */
+int da_bn_maxpool2_idx_fwd(const float* y, int ldy, float* out, uint32_t* sel, const uint32_t* sel_in, int rows, int R, int Lin,
+                           int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                           da_stream_t stream);
+int da_bn_maxpool2_idx_plan(int rows, int R, int Lin, int C, int* chunks, int* chunk_pairs, size_t* workspace);
+size_t da_bn_maxpool2_idx_bwd_workspace(int rows, int R, int Lin, int C);
+int da_bn_maxpool2_idx_bwd(const float* dout, const uint32_t* sel, const float* y, int ldy, float* dy, float* ds, float* workspace,
+                           int rows, int R, int Lin, int C, const float* mean, const float* invstd, const float* gamma,
+                           const float* beta, da_stream_t stream);
+int da_unpool2_fwd(const float* v, const float* bias, const uint32_t* sel, float* out, int rows, int Lo, int C, da_stream_t stream);
+int da_unpool2_bwd(const float* dout, const uint32_t* sel, float* dv, int rows, int Lo, int C, da_stream_t stream);
+size_t da_ae_out_fwd_workspace(int rows, int L);
+size_t da_ae_out_bwd_workspace(int rows, int L);
+int da_ae_out_fwd(const float* v, const float* bias3, const uint32_t* sel1, const float* w4, const float* bias4, const float* x,
+                  float* recon, float* dr, float* partials, float* loss, int rows, int L, da_stream_t stream);
+int da_ae_out_bwd(const float* dr, const float* v, const float* bias3, const uint32_t* sel1, const float* w4, float* dv, float* dw4,
+                  float* db4, float* workspace, int rows, int L, int accumulate, da_stream_t stream);
+
 int da_gather_rows(const float* src, const int64_t* idx, float* out, int B, int width, da_stream_t stream);
 
 /* ---- batched Grad-CAM of a cnn_linear + DenseNet model from the norm5 map alone (gradcam.py:28-205) ----------------------
