@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
            'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip',
-           'siamese.hip', 'conv_grouped.hip', 'autoencoder.hip']
+           'siamese.hip', 'conv_grouped.hip', 'autoencoder.hip', 'unet.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -250,6 +250,15 @@ SIGNATURES = {
     'da_ae_out_bwd_workspace': (_Z, [_I, _I]),
     'da_ae_out_fwd': (_I, [_P] * 10 + [_I, _I, _P]),
     'da_ae_out_bwd': (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    'da_unet_plan': (_I, [_I] * 5 + [_IP, ctypes.POINTER(_Z)]),
+    'da_unet_bias_relu': (_I, [_P, _I, _P] + [_I] * 3 + [_P]),
+    'da_unet_bias_relu_pool2_fwd': (_I, [_P, _I, _P, _P] + [_I] * 3 + [_P]),
+    'da_unet_relu_upsample2_fwd': (_I, [_P, _P, _P] + [_I] * 4 + [_P]),
+    'da_unet_relu_upsample2_bwd': (_I, [_P, _I, _P, _P, _P] + [_I] * 3 + [_P]),
+    'da_unet_pool2_skip_bwd': (_I, [_P, _P, _I, _P, _I, _P] + [_I] * 3 + [_P]),
+    'da_unet_relu_bwd': (_I, [_P, _P, _I, _P] + [_I] * 3 + [_P]),
+    'da_unet_out_fwd': (_I, [_P] * 8 + [_I, _I, _P]),
+    'da_unet_out_bwd': (_I, [_P] * 7 + [_I, _I, _I, _P]),
 }
 
 

@@ -4,13 +4,16 @@ The reference's ``network_map['autoencoder']`` (``AutoencoderModel``, train_ards
 (models/autoencoder_cnn.py, models/autoencoder_network.py) trained to reproduce its input rows under ``MSELoss``; the test epoch
 books ``test_mae``, ``r2`` and ``test_mse`` per batch (``RegressorMixin``, :661-677).
 
-    python -m deepards_amd.autoencoder -n autoencoder --base-network basic_cnn_ae --cuda-no-dp -p <dataset.pkl | .npz> \\
+    python -m deepards_amd.autoencoder -n autoencoder --base-network basic_cnn_ae | unet --cuda-no-dp -p <dataset.pkl | .npz> \\
            --test-from-pickle <...> --save-model pretrained_ae.pth
 
 * ``AutoencoderTrainer``: one step = the whole network and its loss as one autograd node (``functional.AutoencoderFunction``),
   the batched parameter-gradient folds and the fused optimiser -- eager, or a captured graph per input shape, the loss on the
   device.  ``test_step`` runs under ``model.eval()`` (BatchNorm on its running statistics) and returns the reconstruction.
 * any prepared ``ARDSRawDataset`` pickle or ``.npz`` serves; targets are ignored (the reference's ``_autoencoder_target`` is NaN).
+* ``--base-network unet``: the same trainer on ``AutoencoderNetwork(UNet(1))`` (models/unet.py, ``functional.UNetFunction``).  It has
+  no BatchNorm; more than one GPU and folds in flight are refused for it too -- not built, not run -- as are lengths that are no
+  multiple of 8.
 
 Refused: more than one GPU and folds in flight (BatchNorm runs over the WHOLE batch, so a split batch is another function), bf16 /
 f32x3p arithmetic, ``--load-base-network`` / ``--freeze-base-network`` (the second stage is not built), lengths that are no
@@ -20,10 +23,12 @@ import torch
 
 from . import functional as F_
 from .models.autoencoder import AutoencoderCNN, AutoencoderNetwork
+from .models.unet import UNet
 from .train import HotPathTrainer, epoch_shards_on_device
 
 AUTOENCODER_NETWORKS = ('autoencoder',)
 AUTOENCODER_BASE_NETWORK = 'basic_cnn_ae'
+AUTOENCODER_BASE_NETWORKS = (AUTOENCODER_BASE_NETWORK, 'unet')       # the reference's two (base_networks of its driver)
 AUTOENCODER_DATASET_TYPE = 'unpadded_downsampled_autoencoder_sequences'
 
 
@@ -35,14 +40,20 @@ class AutoencoderTrainer(HotPathTrainer):
 
     def __init__(self, model, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9, clip_grad=True, clip_val=0.01,
                  world_size=1, rank=0, process_group=None, use_graph=True, folds_in_flight=None):
-        if not isinstance(model, (AutoencoderNetwork, AutoencoderCNN)):
-            raise TypeError('AutoencoderTrainer trains an AutoencoderNetwork / AutoencoderCNN, got %s' % type(model).__name__)
+        if not isinstance(model, (AutoencoderNetwork, AutoencoderCNN, UNet)):
+            raise TypeError('AutoencoderTrainer trains an AutoencoderNetwork / AutoencoderCNN / UNet, got %s' % type(model).__name__)
+        unet = isinstance(model.base_network if isinstance(model, AutoencoderNetwork) else model, UNet)
         if world_size != 1:
+            if unet:
+                raise NotImplementedError('the autoencoder trainer runs on one GPU: a UNet step sharded over %d ranks (the gradient '
+                                          'all-reduce of this trainer) is not built and was not run' % world_size)
             raise NotImplementedError('the autoencoder trainer runs on one GPU: its BatchNorm takes its statistics over the whole '
                                       'batch, so a batch sharded over %d ranks is a different function' % world_size)
         if folds_in_flight is not None and int(folds_in_flight) > 1:
+            if unet:
+                raise NotImplementedError('folds in flight with the autoencoder trainer: not built and not run for the UNet')
             raise NotImplementedError('folds in flight with the autoencoder trainer: one model, one whole-batch BatchNorm per step')
-        F_._ae_f32_only()
+        (F_._unet_f32_only if unet else F_._ae_f32_only)()
         super(AutoencoderTrainer, self).__init__(model, optimizer=optimizer, learning_rate=learning_rate, weight_decay=weight_decay,
                                                  momentum=momentum, clip_grad=clip_grad, clip_val=clip_val, world_size=1, rank=0,
                                                  process_group=None, use_graph=use_graph)
@@ -126,7 +137,7 @@ def build_parser():
         if action.dest == 'network':
             action.choices = list(AUTOENCODER_NETWORKS)
         elif action.dest == 'base_network':
-            action.choices = list(action.choices) + [AUTOENCODER_BASE_NETWORK]
+            action.choices = list(action.choices) + list(AUTOENCODER_BASE_NETWORKS)
     return parser
 
 

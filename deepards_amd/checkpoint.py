@@ -251,9 +251,9 @@ def _own_module_classes():
     deepards_amd.models.* and torch.nn's own module classes (containers, Conv1d / BatchNorm1d / Linear / LSTM ... that
     the models hold as parameter containers)."""
     import inspect
-    from .models import autoencoder, densenet, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, vgg
+    from .models import autoencoder, densenet, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, unet, vgg
     allow = []
-    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese, autoencoder):
+    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese, autoencoder, unet):
         allow += [c for c in vars(mod).values()
                   if inspect.isclass(c) and issubclass(c, torch.nn.Module) and c.__module__ == mod.__name__]
     allow += [c for c in vars(torch.nn).values() if inspect.isclass(c) and issubclass(c, torch.nn.Module)]
@@ -298,12 +298,16 @@ AUTOENCODER_CHECKPOINT = ('%s is an autoencoder checkpoint: taking one as a base
                           'checkpoint.load_autoencoder reads it for evaluation or for resuming the pretraining')
 
 
+UNET_KEY = 'base_network.dconv_down1.0.weight'        # a key only an AutoencoderNetwork on a UNet has
+
+
 def _refuse_autoencoder(path, class_name=None, keys=()):
     """Raise for a file of the reference's AutoencoderNetwork: by its class (a pickled module), or by the parameter names of
     both halves of AutoencoderCNN under ``base_network.`` (a state_dict)."""
     keys = set(keys)
     if (class_name or '').split('.')[-1] == 'AutoencoderNetwork' or \
-            {'base_network.conv_down1.weight', 'base_network.conv_up4.weight', 'breath_block.0.weight'} <= keys:
+            {'base_network.conv_down1.weight', 'base_network.conv_up4.weight', 'breath_block.0.weight'} <= keys or \
+            {UNET_KEY, 'base_network.conv_last.weight', 'breath_block.0.0.weight'} <= keys:          # (its UNet form)
         raise ValueError(AUTOENCODER_CHECKPOINT % path)
 
 
@@ -344,8 +348,8 @@ def load_base_network(path, base_networks, build_args=None):
 def load_autoencoder(path):
     """An ``AutoencoderNetwork`` from a saved autoencoder, for evaluation and for resuming: a whole module this package saved
     (restricted unpickler), a module the reference pickled (read without unpickling) or a state_dict file with the reference's
-    keys.  A state_dict may leave out BatchNorm's buffers (they keep torch's initial values); any other missing or unknown key
-    raises."""
+    keys.  The base network is the file's: an AutoencoderCNN, or -- a file with ``base_network.dconv_down1.0.weight`` -- a UNet.
+    A state_dict may leave out BatchNorm's buffers (they keep torch's initial values); any other missing or unknown key raises."""
     from .models.autoencoder import AutoencoderCNN, AutoencoderNetwork
     kind = checkpoint_kind(path)
     if kind == 'own':
@@ -358,7 +362,11 @@ def load_autoencoder(path):
     sd = torch.load(path, weights_only=True, map_location='cpu') if kind == 'state_dict' else \
         read_module_checkpoint(path)['state_dict']
     sd = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in sd.items())
-    model = AutoencoderNetwork(AutoencoderCNN())
+    if UNET_KEY in sd:                                   # AutoencoderNetwork(UNet(1)): no buffers, every key must be there
+        from .models.unet import UNet
+        model = AutoencoderNetwork(UNet(1))
+    else:
+        model = AutoencoderNetwork(AutoencoderCNN())
     missing, unexpected = model.load_state_dict(sd, strict=False)
     missing = [k for k in missing if k.split('.')[-1] not in ('running_mean', 'running_var', 'num_batches_tracked')]
     if missing or unexpected:

@@ -184,13 +184,18 @@ def _pack(w, code):
     return e
 
 
-def _conv_fwd(x, w, stride, pad, precise=False):
+def _conv_fwd(x, w, stride, pad, precise=False, out=None):
+    """out: a destination of the fp32 kernels (direct / Winograd) -- it may be a channel slice of a pitched buffer."""
     kern = H.conv_kernel(*w.shape, stride, pad, H.is_x3(x), x.shape[1], precise)
+    if out is not None and kern not in (H.DIRECT, H.WINO2, H.WINO4):
+        raise NotImplementedError('_conv_fwd: a destination belongs to the fp32 conv kernels')
     if kern == H.DIRECT:
-        return H.conv_fwd(x, _pack(w, kern)[0], stride, pad)
+        return H.conv_fwd(x, _pack(w, kern)[0], stride, pad, out=out)
     pk = _pack(w, kern)[2]
     if kern == H.BF16 and stride == 2:
         return H.conv_fwd_bf16_s2(x, pk)
+    if out is not None:
+        return H.conv3_winograd(x, pk, out=out)
     fn = H.conv3_x3p if kern == H.X3 else H.conv3_bf16 if kern == H.BF16 else H.conv3_winograd
     return fn(x, pk)
 
@@ -1033,6 +1038,146 @@ class AutoencoderFunction(Function):
                 dh = _conv_dgrad(dy, w, 1, 1, hs[k].shape[1], precise=precise)
             gdown[4 * k:4 * k + 4] = dw, dbias, dg, dbe
         return (None, None, None, None, None) + tuple(gdown) + tuple(gup)
+
+
+def _unet_f32_only():
+    if H.CONV_DTYPE != 'f32' or H.act_dtype() != 'f32':
+        raise NotImplementedError('the UNet runs with fp32 conv arithmetic and float activation storage only: its ReLU / pool / '
+                                  'upsample / output-stage kernels have no bf16 / f32x3p forms (DA_CONV_DTYPE=%s, storage %s)'
+                                  % (H.CONV_DTYPE, H.act_dtype()))
+
+
+def _unet_run(x, dcs, last, precise):
+    """The UNet's forward and loss on rows x (rows, L): ``dcs`` the seven double_convs (w1, b1, w2, b2) in the order down1..4,
+    up3, up2, up1, ``last`` conv_last's (w, b).  -> recon, dr, loss, and what a backward reads: per double_conv (its input,
+    the activated output a1 of its first conv, what stands for its second ReLU -- the stored activated map, or the raw conv
+    output y2 whose ReLU the upsample behind it applies on the fly).
+
+    The concat of level k is one pitched buffer (rows, L_k, 3 C_k): the second conv of down_k writes its raw output into the last
+    C_k channels, the pool kernel activates it in place (that IS the skip), the upsample writes the first 2 C_k."""
+    _unet_f32_only()
+    rows = x.shape[0]
+    h, cats, keep = x, [], []
+    for k in range(4):
+        w1, b1, w2, b2 = dcs[k]
+        c = w2.shape[0]
+        a1 = H.unet_bias_relu(H.stem_conv_fwd(h, w1, stride=1) if k == 0 else _conv_fwd(h, w1, 1, 1, precise=precise), b1)
+        _tap(a1)
+        if k == 3:
+            y2 = _conv_fwd(a1, w2, 1, 1, precise=precise)
+            _tap((y2, b2))
+            keep.append((h, a1, y2))
+            break
+        cat = torch.empty((rows, a1.shape[1], 3 * c), device=x.device, dtype=torch.float32)
+        skip = cat[:, :, 2 * c:]
+        _conv_fwd(a1, w2, 1, 1, precise=precise, out=skip)
+        p = H.unet_bias_relu_pool2_fwd(skip, b2)
+        _tap(skip)
+        cats.append(cat)
+        keep.append((h, a1, skip))
+        h = p
+    bprev = dcs[3][3]
+    for k in (2, 1, 0):
+        w1, b1, w2, b2 = dcs[6 - k]
+        cat = cats[k]
+        H.unet_relu_upsample2_fwd(y2, bprev, cat[:, :, :y2.shape[2]])
+        a1 = H.unet_bias_relu(_conv_fwd(cat, w1, 1, 1, precise=precise), b1)
+        _tap(a1)
+        y2 = _conv_fwd(a1, w2, 1, 1, precise=precise)
+        if k:
+            _tap((y2, b2))
+        keep.append((cat, a1, y2))
+        bprev = b2
+    a_last = H.unet_bias_relu(y2, bprev)
+    _tap(a_last)
+    recon, dr, loss = H.unet_out_fwd(a_last, last[0], last[1], x)
+    return recon, dr, loss, keep
+
+
+def unet_forward(x, dcs, last, precise=False):
+    """The UNet forward only (eval() / test_step; the network has no BatchNorm and no dropout, so this is the function the
+    training pass computes): rows x (rows, L) -> (recon (rows, L), loss (1,))."""
+    recon, _, loss, _ = _unet_run(x, dcs, last, precise)
+    return recon, loss
+
+
+def unet_encode(x, dcs, precise=False):
+    """The UNet's encoder, forward only: rows x (rows, L) -> the activated output of dconv_down4 (rows, L / 8, 512)."""
+    _unet_f32_only()
+    h = x
+    for k in range(4):
+        w1, b1, w2, b2 = dcs[k]
+        a1 = H.unet_bias_relu(H.stem_conv_fwd(h, w1, stride=1) if k == 0 else _conv_fwd(h, w1, 1, 1, precise=precise), b1)
+        y2 = _conv_fwd(a1, w2, 1, 1, precise=precise)
+        h = H.unet_bias_relu(y2, b2) if k == 3 else H.unet_bias_relu_pool2_fwd(y2, b2)
+    return h
+
+
+class UNetFunction(Function):
+    """The whole UNet (reference models/unet.py:42-69) and its MSE against the input as ONE autograd node: seven double_convs
+    (Conv1d(k3, p1, bias) -> ReLU, twice), three MaxPool1d(2), three Upsample(x2, linear, align_corners=True) + cat, Conv1d(64, 1,
+    1).  x (rows, L) -> (recon (rows, L), loss (1,)); the gradient is the loss's (recon is marked non-differentiable, the incoming
+    gradient of the loss is taken as 1, as AutoencoderFunction does).
+
+    Never stored: the concat as a copy, the activated low-resolution maps in front of the upsamples, pool decisions, an
+    unmasked gradient at a conv output.  The conv biases are real (no BatchNorm cancels them): a bias gradient is the column sum of
+    the masked gradient at its conv's output (H.reduce_rows).  params: (w1, b1, w2, b2) x 7 in the order down1..4, up3, up2, up1,
+    then conv_last's (w, b)."""
+
+    @staticmethod
+    def forward(ctx, x, precise, *params):
+        dcs, last = [params[4 * k:4 * k + 4] for k in range(7)], params[28:30]
+        recon, dr, loss, keep = _unet_run(x, dcs, last, precise)
+        ctx.precise, ctx.gt = bool(precise), [_tgt(*p) for p in dcs] + [_tgt(*last)]
+        ctx.save_for_backward(x, dr, *params, *[t for k, kp in enumerate(keep) for t in (kp[1:] if k == 0 else kp)])
+        ctx.mark_non_differentiable(recon)
+        return recon, loss
+
+    @staticmethod
+    def backward(ctx, _drecon, _dloss):
+        s = ctx.saved_tensors
+        x, dr, params, rest = s[0], s[1], s[2:32], s[32:]
+        dcs, last = [params[4 * k:4 * k + 4] for k in range(7)], params[28:30]
+        keep = [(x,) + tuple(rest[0:2])] + [tuple(rest[2 + 3 * (k - 1):5 + 3 * (k - 1)]) for k in range(1, 7)]
+        gt, precise = ctx.gt, ctx.precise
+        grads = [None] * 30
+
+        def double_conv_bwd(i, dy2):
+            """dy2: the masked gradient at the output of double_conv i's second conv -> the gradient at its input."""
+            (w1, b1, w2, b2), (tw1, tb1, tw2, tb2), (xin, a1, _) = dcs[i], gt[i], keep[i]
+            db2 = H.reduce_rows(dy2.view(-1, dy2.shape[2]), out=tb2, accumulate=tb2 is not None and _acc())
+            dw2 = _wgrad(dy2, a1, 3, 1, 1, tw2, precise=precise)
+            da1 = _conv_dgrad(dy2, w2, 1, 1, a1.shape[1], precise=precise)
+            dy1 = H.unet_relu_bwd(da1, a1, out=da1)
+            db1 = H.reduce_rows(dy1.view(-1, dy1.shape[2]), out=tb1, accumulate=tb1 is not None and _acc())
+            if i == 0:
+                direct = tw1 is not None
+                dw1 = H.stem_conv_wgrad(dy1, xin, out=tw1, accumulate=direct and _acc(), k=3, stride=1)
+                dw1, dx = None if direct else dw1, None
+            else:
+                dw1 = _wgrad(dy1, xin, 3, 1, 1, tw1, precise=precise)
+                dx = _conv_dgrad(dy1, w1, 1, 1, xin.shape[1], precise=precise)
+            grads[4 * i:4 * i + 4] = dw1, None if tb1 is not None else db1, dw2, None if tb2 is not None else db2
+            return dx
+
+        tw, tb = gt[7]
+        direct = tw is not None and tb is not None
+        # (keep[6][2]: up1's second conv output, activated in place -- the map conv_last read)
+        dy2, dwl, dbl = H.unet_out_bwd(dr, keep[6][2], last[0], dw=tw if direct else None, db=tb if direct else None,
+                                       accumulate=direct and _acc())
+        grads[28:30] = (None, None) if direct else (dwl, dbl)
+        dskips = [None] * 3
+        for k in (0, 1, 2):                              # up1, up2, up3: levels 0, 1, 2
+            dcat = double_conv_bwd(6 - k, dy2)
+            c = dcat.shape[2] // 3
+            dskips[k] = dcat[:, :, 2 * c:]
+            # (double_conv 5 - k -- up2, up3, down4 -- left its second conv's output raw for this level's upsample)
+            dy2 = H.unet_relu_upsample2_bwd(dcat[:, :, :2 * c], keep[5 - k][2], dcs[5 - k][3])
+        dp = double_conv_bwd(3, dy2)
+        for k in (2, 1, 0):
+            dy2 = H.unet_pool2_skip_bwd(dp, dskips[k], keep[k][2])
+            dp = double_conv_bwd(k, dy2)
+        return (None, None) + tuple(grads)
 
 
 _STEM_TAIL = True         # inside a training step the stem's last weight-gradient fold rides on the tail launch

@@ -1787,3 +1787,5 @@ from .gradcam_ops import GradCamOutputs, gradcam, gradcam_shape_ok, gradcam_work
 from .gconv_ops import gconv3_ok, gconv3_plan, gconv3_fwd, gconv3_dgrad, gconv3_wgrad   # noqa: E402,F401
 from .autoencoder_ops import (sel_from_bool, sel_to_bool, bn_maxpool2_idx_plan, bn_maxpool2_idx_fwd,   # noqa: E402,F401
                               bn_maxpool2_idx_bwd, unpool2_fwd, unpool2_bwd, ae_out_fwd, ae_out_bwd)
+from .unet_ops import (unet_plan, unet_bias_relu, unet_bias_relu_pool2_fwd, unet_relu_upsample2_fwd,   # noqa: E402,F401
+                       unet_relu_upsample2_bwd, unet_pool2_skip_bwd, unet_relu_bwd, unet_out_fwd, unet_out_bwd)

@@ -115,7 +115,8 @@ class AutoencoderCNN(nn.Module):
 
 
 class AutoencoderNetwork(nn.Module):
-    """(B, NB, 1, L) windows (and the metadata the driver passes) -> recon (B NB, 1, L): all B NB rows one BatchNorm batch."""
+    """(B, NB, 1, L) windows (and the metadata the driver passes) -> recon (B NB, 1, L): all B NB rows one BatchNorm batch.
+    ``base_network``: an AutoencoderCNN, or a ``models.unet.UNet`` (no BatchNorm; it takes no ``sels``)."""
 
     def __init__(self, base_network):
         super(AutoencoderNetwork, self).__init__()

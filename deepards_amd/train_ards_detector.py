@@ -1045,8 +1045,9 @@ class RegressorMixin(object):
 
 class AutoencoderModel(BaseTraining, RegressorMixin):
     """:1102-1116.  NOT in ``network_map`` (its key set is pinned): reached through ``python -m deepards_amd.autoencoder -n
-    autoencoder`` (``autoencoder_network_map``) or built directly.  The network is ``AutoencoderNetwork(AutoencoderCNN())``
-    whatever ``--base-network`` says (the reference's ``basic_cnn_ae``); any prepared dataset serves, its targets are ignored.
+    autoencoder`` (``autoencoder_network_map``) or built directly.  The network is ``AutoencoderNetwork(UNet(1))`` for
+    ``--base-network unet`` and ``AutoencoderNetwork(AutoencoderCNN())`` for every other value (the reference's ``basic_cnn_ae``); any
+    prepared dataset serves, its targets are ignored.
     ``get_optimizer`` returns an ``AutoencoderTrainer``; the test epoch runs under ``model.eval()`` and books ``test_loss``,
     ``test_mae``, ``r2`` and ``test_mse`` per batch.  One GPU, no folds in flight (BatchNorm over the whole batch is a different
     function when the batch is split); ``--load-base-network`` / ``--freeze-base-network`` are refused: they belong to the second
@@ -1054,18 +1055,23 @@ class AutoencoderModel(BaseTraining, RegressorMixin):
 
     def __init__(self, args):
         if getattr(args, 'load_base_network', None):
-            raise NotImplementedError('--load-base-network with -n autoencoder: the network is always a fresh AutoencoderCNN; a saved '
+            raise NotImplementedError('--load-base-network with -n autoencoder: the network is always a fresh AutoencoderCNN / UNet; a saved '
                                       'autoencoder resumes through --load-checkpoint, and a classifier\'s breath_block has no '
                                       'decoder to load')
         if _flag(args, 'freeze_base_network'):
             raise NotImplementedError('--freeze-base-network with -n autoencoder: the base network IS the model being pretrained; '
                                       'freezing it leaves nothing to train')
+        unet = getattr(args, 'base_network', None) == 'unet'
         if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            if unet:
+                raise NotImplementedError('autoencoder pretraining with --base-network unet runs on one GPU: the sharded step is not '
+                                          'built and was not run')
             raise NotImplementedError('autoencoder pretraining runs on one GPU: its BatchNorm takes its statistics over the whole '
                                       'batch, which a batch sharded over ranks changes')
         n_flight = getattr(args, 'folds_in_flight', None)
         if n_flight is not None and int(n_flight) > 1:
-            raise NotImplementedError('--folds-in-flight > 1 with -n autoencoder: the folds run one after the other')
+            raise NotImplementedError('--folds-in-flight > 1 with -n autoencoder: %s' %
+                                      ('not built and not run for the UNet' if unet else 'the folds run one after the other'))
         args.folds_in_flight = 1
         super(AutoencoderModel, self).__init__(args)
 
@@ -1079,7 +1085,7 @@ class AutoencoderModel(BaseTraining, RegressorMixin):
         return self.criterion(outputs, inputs.reshape(inputs.shape[0] * inputs.shape[1], inputs.shape[2], inputs.shape[3]))
 
     def get_base_network(self):
-        return M.AutoencoderCNN()
+        return M.UNet(1) if self.args.base_network == 'unet' else M.AutoencoderCNN()
 
     def get_network(self, base_network):
         return M.AutoencoderNetwork(base_network)

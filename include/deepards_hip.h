@@ -691,6 +691,40 @@ int da_ae_out_fwd(const float* v, const float* bias3, const uint32_t* sel1, cons
 int da_ae_out_bwd(const float* dr, const float* v, const float* bias3, const uint32_t* sel1, const float* w4, float* dv, float* dw4,
                   float* db4, float* workspace, int rows, int L, int accumulate, da_stream_t stream);
 
+/* ---- the UNet's layers between its convs (csrc/unet.hip; reference models/unet.py): bias + ReLU (no BatchNorm), ReLU +
+ * MaxPool1d(2) that keeps the full-resolution map as the skip, ReLU + Upsample(x2, linear, align_corners=True), Conv1d(64, 1, 1)
+ * + MSELoss.  float activations [rows][L][C] channels-last, float storage only; C a multiple of 32; an operand named with a pitch
+ * may be C channels of a pitched buffer (ld >= C, ld % 4 == 0, rows L ld < 2^32); anything else, or a NULL operand, ->
+ * DA_EINVAL before any launch.  relu(v) = v > 0 ? v : +0.0; no pool decision is stored (the winner is re-derived from the stored
+ * activation: the second member only when strictly greater).  Every sum runs in an order fixed by the shape (no atomics); each
+ * entry launches on `stream` only, allocates nothing and never synchronises.
+ *   da_unet_plan                 blocks (of 256 threads) and workspace bytes of entry point `op` (0 ... 7, in the order below) on
+ *                                (rows, L, C) with widest pitch ld, launching nothing; L as the entry point takes it
+ *   da_unet_bias_relu            y = relu(y + bias) in place
+ *   da_unet_bias_relu_pool2_fwd  y = relu(y + bias) in place (L even); pooled [rows][L / 2][C][j] = max(y[2j], y[2j+1])
+ *   da_unet_relu_upsample2_fwd   x = relu(y + bias) (y [rows][L][C], x never stored), D = 2 L - 1: out [rows][2 L][ld_out],
+ *                                out[2j+1] = fma((L-1-j)/D, x[j+1], ((L+j)/D) x[j]);  out[2j] = fma(j/D, x[j-1], ((D-j)/D) x[j])
+ *   da_unet_relu_upsample2_bwd   dy[j] = [y + bias > 0] (((L+j)/D) d[2j+1] + ((D-j)/D) d[2j] + ((L-j)/D) d[2j-1] + ((j+1)/D) d[2j+2]),
+ *                                the terms in that order, those outside the row left out
+ *   da_unet_pool2_skip_bwd       dy[2j+w] = [a > 0] (dskip[2j+w] + dpooled[j]), dy[2j+1-w] = [a > 0] dskip[2j+1-w]; w = a[2j+1] > a[2j]
+ *   da_unet_relu_bwd             dy = [a > 0] dout (dy may be dout)
+ *   da_unet_out_fwd              a [rows][L][64]: recon[n][l] = bias + sum_c a[n][l][c] w[c];  dr = 2 (recon - x) / (rows L);
+ *                                loss[0] = mean (recon - x)^2 from per-block partials (the plan's workspace) in block order
+ *   da_unet_out_bwd              dy = dr w [a > 0];  dw[c] (+)= sum dr a[c],  db (+)= sum dr: block records folded in block order */
+int da_unet_plan(int op, int rows, int L, int C, int ld, int* blocks, size_t* workspace);
+int da_unet_bias_relu(float* y, int ld, const float* bias, int rows, int L, int C, da_stream_t stream);
+int da_unet_bias_relu_pool2_fwd(float* y, int ld, const float* bias, float* pooled, int rows, int L, int C, da_stream_t stream);
+int da_unet_relu_upsample2_fwd(const float* y, const float* bias, float* out, int ld_out, int rows, int L, int C, da_stream_t stream);
+int da_unet_relu_upsample2_bwd(const float* d, int ld, const float* y, const float* bias, float* dy, int rows, int L, int C,
+                               da_stream_t stream);
+int da_unet_pool2_skip_bwd(const float* dpooled, const float* dskip, int ld, const float* a, int ld_a, float* dy, int rows, int L,
+                           int C, da_stream_t stream);
+int da_unet_relu_bwd(const float* dout, const float* a, int ld_a, float* dy, int rows, int L, int C, da_stream_t stream);
+int da_unet_out_fwd(const float* a, const float* w, const float* bias, const float* x, float* recon, float* dr, float* partials,
+                    float* loss, int rows, int L, da_stream_t stream);
+int da_unet_out_bwd(const float* dr, const float* a, const float* w, float* dy, float* dw, float* db, float* workspace, int rows,
+                    int L, int accumulate, da_stream_t stream);
+
 int da_gather_rows(const float* src, const int64_t* idx, float* out, int B, int width, da_stream_t stream);
 
 /* ---- batched Grad-CAM of a cnn_linear + DenseNet model from the norm5 map alone (gradcam.py:28-205) ----------------------
