@@ -19,12 +19,10 @@ Refused: more than one GPU and folds in flight (BatchNorm runs over the WHOLE ba
 f32x3p arithmetic, ``--load-base-network`` / ``--freeze-base-network`` (the second stage is not built), lengths that are no
 multiple of 16.  A saved autoencoder is not accepted as a base network (``checkpoint.load_autoencoder`` reads it back).
 """
-import torch
-
 from . import functional as F_
 from .models.autoencoder import AutoencoderCNN, AutoencoderNetwork
 from .models.unet import UNet
-from .train import HotPathTrainer, epoch_shards_on_device
+from .train import SelfSupervisedTrainer, epoch_shards_on_device
 
 AUTOENCODER_NETWORKS = ('autoencoder',)
 AUTOENCODER_BASE_NETWORK = 'basic_cnn_ae'
@@ -32,43 +30,34 @@ AUTOENCODER_BASE_NETWORKS = (AUTOENCODER_BASE_NETWORK, 'unet')       # the refer
 AUTOENCODER_DATASET_TYPE = 'unpadded_downsampled_autoencoder_sequences'
 
 
-class AutoencoderTrainer(HotPathTrainer):
+class AutoencoderTrainer(SelfSupervisedTrainer):
     """One autoencoder on one GPU.  ``train_step(inputs)``: one iteration of the reference's batch loop on windows (B, NB, 1, L)
     (an ``AutoencoderNetwork``) or rows (N, 1, L) (an ``AutoencoderCNN``) -- eager, or a captured graph per input shape -- with the
     optimiser and clamp of ``HotPathTrainer``; returns the device-resident loss (``last_loss``; ``last_logits`` is the
-    reconstruction).  ``test_step(inputs)``: the forward under ``model.eval()`` -> recon (N, 1, L); ``last_test_loss`` its MSE."""
+    reconstruction).  ``test_step(inputs)``: the forward under ``model.eval()`` -> recon (N, 1, L); ``last_test_loss`` its MSE.
+
+    The step scaffold -- the placeholder target (the input is its own), the refusals, forward/backward around
+    ``_loss_and_output`` and ``model.eval()`` in the test step -- is ``train.SelfSupervisedTrainer``."""
+    batch_alone = 'an autoencoder step takes the batch alone: the input is its own target'
 
     def __init__(self, model, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9, clip_grad=True, clip_val=0.01,
                  world_size=1, rank=0, process_group=None, use_graph=True, folds_in_flight=None):
         if not isinstance(model, (AutoencoderNetwork, AutoencoderCNN, UNet)):
             raise TypeError('AutoencoderTrainer trains an AutoencoderNetwork / AutoencoderCNN / UNet, got %s' % type(model).__name__)
         unet = isinstance(model.base_network if isinstance(model, AutoencoderNetwork) else model, UNet)
-        if world_size != 1:
-            if unet:
-                raise NotImplementedError('the autoencoder trainer runs on one GPU: a UNet step sharded over %d ranks (the gradient '
-                                          'all-reduce of this trainer) is not built and was not run' % world_size)
-            raise NotImplementedError('the autoencoder trainer runs on one GPU: its BatchNorm takes its statistics over the whole '
-                                      'batch, so a batch sharded over %d ranks is a different function' % world_size)
-        if folds_in_flight is not None and int(folds_in_flight) > 1:
-            if unet:
-                raise NotImplementedError('folds in flight with the autoencoder trainer: not built and not run for the UNet')
-            raise NotImplementedError('folds in flight with the autoencoder trainer: one model, one whole-batch BatchNorm per step')
+        if unet:
+            one_gpu = ('the autoencoder trainer runs on one GPU: a UNet step sharded over %d ranks (the gradient all-reduce of '
+                       'this trainer) is not built and was not run')
+            no_folds = 'folds in flight with the autoencoder trainer: not built and not run for the UNet'
+        else:
+            one_gpu = ('the autoencoder trainer runs on one GPU: its BatchNorm takes its statistics over the whole batch, so a '
+                       'batch sharded over %d ranks is a different function')
+            no_folds = 'folds in flight with the autoencoder trainer: one model, one whole-batch BatchNorm per step'
+        super(AutoencoderTrainer, self).__init__(model, one_gpu, no_folds, world_size=world_size, folds_in_flight=folds_in_flight,
+                                                 optimizer=optimizer, learning_rate=learning_rate, weight_decay=weight_decay,
+                                                 momentum=momentum, clip_grad=clip_grad, clip_val=clip_val, use_graph=use_graph)
         (F_._unet_f32_only if unet else F_._ae_f32_only)()
-        super(AutoencoderTrainer, self).__init__(model, optimizer=optimizer, learning_rate=learning_rate, weight_decay=weight_decay,
-                                                 momentum=momentum, clip_grad=clip_grad, clip_val=clip_val, world_size=1, rank=0,
-                                                 process_group=None, use_graph=use_graph)
-        self.eval_test = True                             # BatchNorm on running statistics: built for this network
         self.last_test_loss = None
-        self._no_target = None
-
-    def _placeholder(self, inputs):
-        """The base class's steps carry a target; there is none here (the input is its own target)."""
-        ent = self._graphs.get(tuple(inputs.shape))
-        if ent is not None:
-            return ent[1][1]
-        if self._no_target is None or self._no_target.device != inputs.device:
-            self._no_target = torch.zeros(1, device=inputs.device, dtype=torch.float32)
-        return self._no_target
 
     def _check_batch(self, batch):
         want = 4 if isinstance(self.model, AutoencoderNetwork) else 3
@@ -76,40 +65,11 @@ class AutoencoderTrainer(HotPathTrainer):
             raise ValueError('an autoencoder step takes %s, got %s' %
                              ('(B, NB, 1, L) windows' if want == 4 else '(N, 1, L) rows', tuple(batch.shape)))
 
-    def _forward_backward(self, inputs, target, zero_grad=False):
-        if zero_grad:
-            self.bucket.zero_grad()
-        with F_.training_step(self.model):
-            loss, recon = self.model.forward_loss(inputs)
-            F_.flush_forward(defer=True)
-            torch.autograd.backward(loss, grad_tensors=self._one(loss))
-            F_.flush_backward()
-        return loss.detach(), recon
-
-    def train_step(self, batch, target=None, reset=None):
-        if target is not None or reset is not None:
-            raise ValueError('an autoencoder step takes the batch alone: the input is its own target')
-        self._check_batch(batch)
-        return super(AutoencoderTrainer, self).train_step(batch, self._placeholder(batch))
-
-    def _test_forward(self, inputs, target):
-        with torch.no_grad(), F_.training_step(self.model):
-            loss, recon = self.model.forward_loss(inputs)
-            F_.flush_forward()
-        return loss, recon
+    def _loss_and_output(self, inputs):
+        return self.model.forward_loss(inputs)
 
     def test_step(self, batch, target=None, reset=None):
-        if target is not None or reset is not None:
-            raise ValueError('an autoencoder step takes the batch alone: the input is its own target')
-        self._check_batch(batch)
-        if not self.use_graph:
-            if self.model.training:
-                self.model.eval()
-            loss, recon = self._test_forward(batch, None)
-        else:
-            ent = self._test_graphs.get((tuple(batch.shape), (1,)))
-            loss, recon = super(AutoencoderTrainer, self).test_step(batch, ent[1][1] if ent is not None else self._placeholder(batch))
-        self.last_test_loss = loss
+        self.last_test_loss, recon = super(AutoencoderTrainer, self).test_step(batch, target, reset)
         return recon
 
 
@@ -143,22 +103,8 @@ def build_parser():
 
 def main(argv=None):
     """``python -m deepards_amd.autoencoder -n autoencoder <the driver's flags>``."""
-    import sys
     from . import train_ards_detector as T
-    from .config import Configuration
-    argv = sys.argv[1:] if argv is None else list(argv)
-    for a in argv:
-        if a.split('=')[0] in T.OUT_OF_SCOPE_FLAGS:
-            raise SystemExit('%s steers code outside the accelerated hot path and is not accepted by this build' % a.split('=')[0])
-    args = Configuration(build_parser().parse_args(argv), dict(T.BUILD_DEFAULTS))
-    if args.network not in AUTOENCODER_NETWORKS:
-        raise SystemExit('-n must be one of %s' % ', '.join(AUTOENCODER_NETWORKS))
-    if args.save_model_per_epoch and not args.save_model:
-        raise Exception('Must specify a filename to save your model using --save-model')
-    cls = T.autoencoder_network_map[args.network](args)
-    results = cls.train_and_test()
-    cls.perform_post_modeling_actions()
-    return cls, results
+    return T.stage_main(argv, build_parser(), AUTOENCODER_NETWORKS, T.autoencoder_network_map, dict(T.BUILD_DEFAULTS))
 
 
 def __getattr__(name):

@@ -26,11 +26,10 @@ flight for these trainers, k-folds (the reference's dataset is not meant for the
 import numpy as np
 import torch
 
-from . import functional as F_
 from . import siamese_ops as SO
 from .data import DeviceTileStore
 from .models.siamese import _SiameseNetwork
-from .train import HotPathTrainer, refuse_eval_on_running_stats
+from .train import SelfSupervisedTrainer
 
 SIAMESE_NETWORKS = ('siamese_cnn_linear', 'siamese_cnn_lstm', 'siamese_cnn_transformer')
 
@@ -184,43 +183,32 @@ class SiameseTileStore(object):
         return self.store._gather(idx, out), idx
 
 
-class SiameseTrainer(HotPathTrainer):
+class SiameseTrainer(SelfSupervisedTrainer):
     """One siamese network on one GPU.  ``train_step(batch)``: one iteration of SiameseMixin.run_train_epoch (:613-624) on the
     windows ``SiameseTileStore.triplet_batch(..., literal=not share_anchor)`` gathered -- eager, or a captured graph per input
     shape -- with the optimiser and clamp of ``HotPathTrainer``; returns the device-resident loss (``last_loss``; ``last_logits``
     is z (2, B, 2)).  ``test_step(batch)``: the body of run_test_epoch (:636-649) under ``model.eval()`` -> (loss (1,),
     accuracy (1,) of argmax(cat(z_pos, z_neg)) against B ones then B zeros, z (2, B, 2)), all on the device.
 
-    ``share_anchor`` (see the module docstring) departs from the reference; the default does not."""
+    ``share_anchor`` (see the module docstring) departs from the reference; the default does not.  The step scaffold -- the
+    placeholder target, the refusals, forward/backward around ``_loss_and_output``, ``model.eval()`` in the test step and its
+    refusal on running statistics -- is ``train.SelfSupervisedTrainer``; here is only what is siamese."""
+    batch_alone = 'a siamese step takes the triplet batch alone'
 
     def __init__(self, model, share_anchor=False, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9,
                  clip_grad=True, clip_val=0.01, world_size=1, rank=0, process_group=None, use_graph=True, folds_in_flight=None):
         if not isinstance(model, _SiameseNetwork):
             raise TypeError('SiameseTrainer trains a siamese network, got %s' % type(model).__name__)
-        if world_size != 1:
-            raise NotImplementedError('the siamese trainer runs on one GPU: the triplet draw and its batch are not sharded over '
-                                      '%d ranks' % world_size)
-        if folds_in_flight is not None and int(folds_in_flight) > 1:
-            raise NotImplementedError('folds in flight with the siamese trainer: its dataset has no folds (dataset.py:1597)')
-        super(SiameseTrainer, self).__init__(model, optimizer=optimizer, learning_rate=learning_rate, weight_decay=weight_decay,
-                                             momentum=momentum, clip_grad=clip_grad, clip_val=clip_val, world_size=1, rank=0,
-                                             process_group=None, use_graph=use_graph)
+        super(SiameseTrainer, self).__init__(
+            model, 'the siamese trainer runs on one GPU: the triplet draw and its batch are not sharded over %d ranks',
+            'folds in flight with the siamese trainer: its dataset has no folds (dataset.py:1597)', world_size=world_size,
+            folds_in_flight=folds_in_flight, optimizer=optimizer, learning_rate=learning_rate, weight_decay=weight_decay,
+            momentum=momentum, clip_grad=clip_grad, clip_val=clip_val, use_graph=use_graph)
         self.share_anchor = bool(share_anchor)
-        self.eval_test = True                             # the siamese test epoch calls model.eval() (:635); see test_step
-        self._no_target = None
 
     @property
     def windows_per_triplet(self):
         return 3 if self.share_anchor else 4
-
-    def _placeholder(self, inputs):
-        """The base class's steps carry a target; there is none here (the head knows its two targets)."""
-        ent = self._graphs.get(tuple(inputs.shape))
-        if ent is not None:
-            return ent[1][1]                              # the captured step's own (unread) buffer: no copy per step
-        if self._no_target is None or self._no_target.device != inputs.device:
-            self._no_target = torch.zeros(1, device=inputs.device, dtype=torch.float32)
-        return self._no_target
 
     def _check_batch(self, batch):
         k = self.windows_per_triplet
@@ -228,44 +216,16 @@ class SiameseTrainer(HotPathTrainer):
             raise ValueError('a %s-anchor step takes (%d B, NB, C, 224) windows, got %s' %
                              ('shared' if self.share_anchor else 'separate', k, tuple(batch.shape)))
 
-    def _forward_backward(self, inputs, target, zero_grad=False):
-        if zero_grad:
-            self.bucket.zero_grad()
-        with F_.training_step(self.model):
-            loss, z = self.model.triplet_head(inputs, literal=not self.share_anchor)
-            F_.flush_forward(defer=True)
-            torch.autograd.backward(loss, grad_tensors=self._one(loss))
-            F_.flush_backward()
-        return loss, z
-
-    def train_step(self, batch, target=None, reset=None):
-        if target is not None or reset is not None:
-            raise ValueError('a siamese step takes the triplet batch alone')
-        self._check_batch(batch)
-        return super(SiameseTrainer, self).train_step(batch, self._placeholder(batch))
+    def _loss_and_output(self, inputs):
+        return self.model.triplet_head(inputs, literal=not self.share_anchor)
 
     def _test_forward(self, inputs, target):
-        with torch.no_grad(), F_.training_step(self.model):
-            loss, z = self.model.triplet_head(inputs, literal=not self.share_anchor)
-            F_.flush_forward()
-            b = z.shape[1]
-            pred = z.argmax(dim=-1).reshape(-1)                                     # cat(z_pos, z_neg).argmax(1)  (:656-657)
-            want = (torch.arange(2 * b, device=z.device) < b).to(pred.dtype)       # B ones, then B zeros         (:654-655)
-            acc = (pred == want).to(torch.float32).mean().reshape(1)
+        loss, z = super(SiameseTrainer, self)._test_forward(inputs, target)
+        b = z.shape[1]
+        pred = z.argmax(dim=-1).reshape(-1)                                     # cat(z_pos, z_neg).argmax(1)  (:656-657)
+        want = (torch.arange(2 * b, device=z.device) < b).to(pred.dtype)       # B ones, then B zeros         (:654-655)
+        acc = (pred == want).to(torch.float32).mean().reshape(1)
         return loss, acc, z
-
-    def test_step(self, batch, target=None, reset=None):
-        if target is not None or reset is not None:
-            raise ValueError('a siamese step takes the triplet batch alone')
-        refuse_eval_on_running_stats(self.model)
-        self._check_batch(batch)
-        if not self.use_graph:
-            if self.model.training:
-                self.model.eval()
-            return self._test_forward(batch, None)
-        key = (tuple(batch.shape), (1,))
-        ent = self._test_graphs.get(key)
-        return super(SiameseTrainer, self).test_step(batch, ent[1][1] if ent is not None else self._placeholder(batch))
 
 
 def epoch_anchor_batches(store, batch_size, shuffle=True, generator=None):
@@ -313,23 +273,8 @@ def build_parser():
 
 def main(argv=None):
     """``python -m deepards_amd.siamese -n siamese_cnn_linear|siamese_cnn_lstm|siamese_cnn_transformer <the driver's flags>``."""
-    import sys
     from . import train_ards_detector as T
-    from .config import Configuration
-    argv = sys.argv[1:] if argv is None else list(argv)
-    for a in argv:
-        if a.split('=')[0] in T.OUT_OF_SCOPE_FLAGS:
-            raise SystemExit('%s steers code outside the accelerated hot path and is not accepted by this build' % a.split('=')[0])
-    defaults = dict(T.BUILD_DEFAULTS, share_anchor=None)
-    args = Configuration(build_parser().parse_args(argv), defaults)
-    if args.network not in SIAMESE_NETWORKS:
-        raise SystemExit('-n must be one of %s' % ', '.join(SIAMESE_NETWORKS))
-    if args.save_model_per_epoch and not args.save_model:
-        raise Exception('Must specify a filename to save your model using --save-model')
-    cls = T.siamese_network_map[args.network](args)
-    results = cls.train_and_test()
-    cls.perform_post_modeling_actions()
-    return cls, results
+    return T.stage_main(argv, build_parser(), SIAMESE_NETWORKS, T.siamese_network_map, dict(T.BUILD_DEFAULTS, share_anchor=None))
 
 
 if __name__ == '__main__':

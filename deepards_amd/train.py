@@ -262,7 +262,11 @@ class HotPathTrainer(object):
     ``loss_calc='last_breath'`` (CNNLSTMModel.calc_loss, :820-821) takes the loss and its gradient on ``outputs[:, -1, :]``.
     ``carry_state=True`` (cnn_lstm --unshuffled, :841-849, :868-875; one window per step): the LSTM's (hx, cx) stay in a
     device buffer from one step to the next, detached; ``train_step`` / ``test_step`` take ``reset``, a one-element int64
-    DEVICE tensor -- 0: start from zeros (a new patient), 1: from the carried state.  Nothing is read back per step."""
+    DEVICE tensor -- 0: start from zeros (a new patient), 1: from the carried state.  Nothing is read back per step.
+
+    Subclasses replace ``_forward_backward`` / ``_test_forward`` (and ``ProtoPNetTrainer`` the update); the capture, its
+    allocator warm-up (``_warm_up``), the replay and ``snapshot`` / ``restore`` are here for all of them.  The trainers whose
+    step takes no target share ``SelfSupervisedTrainer`` below."""
 
     def __init__(self, model, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9,
                  clip_grad=True, clip_val=0.01, world_size=1, rank=0, process_group=None, use_graph=True,
@@ -482,24 +486,27 @@ class HotPathTrainer(object):
         return loss, logits
 
     # ---- graph replay ------------------------------------------------------------------------
-    def _capture(self, inputs, target):
-        """Capture the step for this batch shape.  Every shape keeps its own graph (an epoch's tail batch has another
-        shape than the full ones: it is captured once, not twice per epoch)."""
-        static = (inputs.clone(), target.clone())
-        # Warm the caching allocator on a side stream with a forward+backward whose side effects
-        # (BN running stats, dropout seed) are rolled back, so capture adds no training step.
+    def _warm_up(self, run):
+        """Warm the caching allocator for a capture: ``run()`` once on a side stream, its side effects on the module
+        buffers (BN running stats, dropout seed) and the carried LSTM state rolled back, so a capture adds no step."""
         saved = [b.clone() for b in self.model.buffers()]
         carry = self._carry.clone() if self._carry is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        F_._OV['ok'] = True
         with torch.cuda.stream(s):
-            self._forward_backward(*static, zero_grad=True)
+            run()
             for b, c in zip(self.model.buffers(), saved):
                 b.copy_(c)
             if carry is not None:
                 self._carry.copy_(carry)
         torch.cuda.current_stream().wait_stream(s)
+
+    def _capture(self, inputs, target):
+        """Capture the step for this batch shape.  Every shape keeps its own graph (an epoch's tail batch has another
+        shape than the full ones: it is captured once, not twice per epoch)."""
+        static = (inputs.clone(), target.clone())
+        F_._OV['ok'] = True
+        self._warm_up(lambda: self._forward_backward(*static, zero_grad=True))
         # Did every gradient destination get exactly one write, by a writer with an overwrite form (functional._OV)?  Then
         # the captured step needs no zero-fill of the gradient bucket: its writers overwrite (6 us a step at B = 64).
         self.grad_overwrite = _GRAD_OVERWRITE and F_._OV['ok']
@@ -712,17 +719,7 @@ class HotPathTrainer(object):
         ent = self._test_graphs.get(key)
         if ent is None:
             static = (inputs.clone(), target.clone())
-            saved = [b.clone() for b in self.model.buffers()]
-            carry = self._carry.clone() if self._carry is not None else None
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):                           # allocator warm-up, side effects rolled back
-                self._test_forward(*static)
-                for b, c in zip(self.model.buffers(), saved):
-                    b.copy_(c)
-                if carry is not None:
-                    self._carry.copy_(carry)
-            torch.cuda.current_stream().wait_stream(s)
+            self._warm_up(lambda: self._test_forward(*static))
             g = torch.cuda.CUDAGraph()
             with _capture_graph(g):
                 out = self._test_forward(*static)
@@ -732,6 +729,71 @@ class HotPathTrainer(object):
         static[1].copy_(target)
         g.replay()
         return tuple(o.clone() for o in out)                     # never hand out the graph's own buffers
+
+
+class SelfSupervisedTrainer(HotPathTrainer):
+    """``HotPathTrainer`` for steps without a target (``SiameseTrainer``, ``AutoencoderTrainer``): ``train_step(batch)`` /
+    ``test_step(batch)`` take the batch alone and hand the base class's steps a one-element placeholder where they carry a
+    target.  A subclass supplies its model type check, ``_check_batch(batch)``, ``_loss_and_output(inputs)`` -> (loss (1,)
+    with its autograd node, the step's output), the sentence ``batch_alone`` and its two reasons for one GPU and one fold
+    at a time.  The test step runs under ``model.eval()``."""
+    batch_alone = 'a step takes the batch alone'
+
+    def __init__(self, model, one_gpu, no_folds, world_size=1, folds_in_flight=None, **kw):
+        if world_size != 1:
+            raise NotImplementedError(one_gpu % world_size)
+        if folds_in_flight is not None and int(folds_in_flight) > 1:
+            raise NotImplementedError(no_folds)
+        super(SelfSupervisedTrainer, self).__init__(model, world_size=1, rank=0, process_group=None, **kw)
+        # model.eval() in the test step, as the reference's siamese (:635) and autoencoder test epochs do.  Set HERE and not
+        # through the constructor, which refuses eval_test on a breath block whose BatchNorm keeps running statistics: such
+        # a siamese network must still construct and train, so the refusal is made by test_step, where it applies.  (The
+        # autoencoder's BatchNorm on running statistics is built.)
+        self.eval_test = True
+        self._no_target = None
+
+    def _placeholder(self, inputs):
+        """The base class's steps carry a target; there is none here."""
+        ent = self._graphs.get(tuple(inputs.shape))
+        if ent is not None:
+            return ent[1][1]                              # the captured step's own (unread) buffer: no copy per step
+        if self._no_target is None or self._no_target.device != inputs.device:
+            self._no_target = torch.zeros(1, device=inputs.device, dtype=torch.float32)
+        return self._no_target
+
+    def _refuse_operands(self, target, reset):
+        if target is not None or reset is not None:
+            raise ValueError(self.batch_alone)
+
+    def _forward_backward(self, inputs, target, zero_grad=False):
+        if zero_grad:
+            self.bucket.zero_grad()
+        with F_.training_step(self.model):
+            loss, out = self._loss_and_output(inputs)
+            F_.flush_forward(defer=True)
+            torch.autograd.backward(loss, grad_tensors=self._one(loss))
+            F_.flush_backward()
+        return loss.detach(), out
+
+    def _test_forward(self, inputs, target):
+        with torch.no_grad(), F_.training_step(self.model):
+            loss, out = self._loss_and_output(inputs)
+            F_.flush_forward()
+        return loss, out
+
+    def train_step(self, batch, target=None, reset=None):
+        self._refuse_operands(target, reset)
+        self._check_batch(batch)
+        return super(SelfSupervisedTrainer, self).train_step(batch, self._placeholder(batch))
+
+    def test_step(self, batch, target=None, reset=None):
+        """-> what ``_test_forward`` returns.  A replay copies nothing for the placeholder: the captured test step is handed
+        its own static buffer, and torch skips a copy of a tensor onto itself."""
+        self._refuse_operands(target, reset)
+        refuse_eval_on_running_stats(self.model)
+        self._check_batch(batch)
+        ent = self._test_graphs.get((tuple(batch.shape), (1,)))
+        return super(SelfSupervisedTrainer, self).test_step(batch, ent[1][1] if ent is not None else self._placeholder(batch))
 
 
 def run_train_epoch(trainer, loader, batch_size=None):

@@ -30,6 +30,7 @@ runs the hot path on MI355X.  What differs, and why:
 There is no CPU path: constructing a model class with neither ``--cuda`` nor ``--cuda-no-dp`` raises.
 """
 import argparse
+import contextlib
 import os
 
 import torch
@@ -106,6 +107,17 @@ class Results(object):
 def _flag(args, name, default=False):
     v = getattr(args, name, default)
     return default if v is None else v
+
+
+def _one_gpu_one_fold_at_a_time(args, one_gpu, no_folds):
+    """The refusal of the families whose trainer is neither sharded over ranks nor run with folds in flight (ProtoPNet, the
+    siamese and the autoencoder stage), each with its own two reasons; the fold loop then runs the folds one after the other."""
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise NotImplementedError(one_gpu)
+    n_flight = getattr(args, 'folds_in_flight', None)
+    if n_flight is not None and int(n_flight) > 1:
+        raise NotImplementedError(no_folds)
+    args.folds_in_flight = 1
 
 
 class BaseTraining(object):
@@ -198,12 +210,16 @@ class BaseTraining(object):
     def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
         """:416-422: Adam(lr) or SGD(lr, momentum .9, weight_decay, nesterov) + the clamp of get_model, as the trainer
         that owns the captured step."""
+        return HotPathTrainer(model, **self._trainer_kwargs(world_size, rank, process_group), **self._loss_kwargs())
+
+    def _trainer_kwargs(self, world_size, rank, process_group):
+        """The keywords every family's trainer takes from the command line (its own ``get_optimizer`` adds the rest)."""
         a = self.args
         if a.optimizer not in ('adam', 'sgd'):
             raise ValueError('optimizer must be adam or sgd')
-        return HotPathTrainer(model, optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
-                              clip_grad=bool(_flag(a, 'clip_grad')), clip_val=a.clip_val, world_size=world_size, rank=rank,
-                              process_group=process_group, use_graph=_flag(a, 'use_graph', True), **self._loss_kwargs())
+        return dict(optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
+                    clip_grad=bool(_flag(a, 'clip_grad')), clip_val=a.clip_val, world_size=world_size, rank=rank,
+                    process_group=process_group, use_graph=_flag(a, 'use_graph', True))
 
     def _loss_kwargs(self):
         """What set_loss_criterion chose, as the trainer's keywords (the criterion runs inside its captured step)."""
@@ -301,17 +317,42 @@ class BaseTraining(object):
         """:139-159.  ``optimizer`` is the trainer from get_optimizer; every batch is one gather kernel + one graph
         replay; the per-batch losses stay on the device until a meter is read.  The permutation comes from the seed when
         one is given; data-parallel ranks always shard ONE permutation (rank 0's seed is broadcast per epoch)."""
-        store, batch_size, shuffle = train_loader
         if optimizer.model is not model:
             raise ValueError('optimizer was built for another model')
-        gen = None
-        if self.args.seed is not None:
-            gen = torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num)
-        for loss in run_train_epoch_from_store(optimizer, store, batch_size=batch_size, shuffle=shuffle, generator=gen):
-            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
-            self.results.update_meter('loss', fold_num, loss)
+        for loss in self._train_losses(optimizer, train_loader, self._epoch_generator(fold_num, epoch_num)):
+            self._book_train_loss(optimizer, loss, epoch_num, fold_num)
             if _flag(self.args, 'debug'):
                 break
+
+    def _train_epoch_iterator(self):
+        """What yields an epoch's per-batch losses: the one piece of the train epoch a family replaces."""
+        return run_train_epoch_from_store
+
+    def _train_losses(self, optimizer, train_loader, generator):
+        store, batch_size, shuffle = train_loader
+        return self._train_epoch_iterator()(optimizer, store, batch_size=batch_size, shuffle=shuffle, generator=generator)
+
+    def _book_train_loss(self, optimizer, loss, epoch_num, fold_num):
+        self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
+        self.results.update_meter('loss', fold_num, loss)
+
+    def _epoch_generator(self, fold_num, epoch_num, offset=0):
+        """The generator of one epoch's permutation: seeded from --seed, the fold and the epoch; ``offset`` keeps a test
+        epoch (500009) and ProtoPNet's last-layer passes apart from the train epoch.  None without a seed."""
+        if self.args.seed is None:
+            return None
+        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + offset)
+
+    @contextlib.contextmanager
+    def _test_trainer(self, optimizer, make):
+        """The trainer of a test epoch: the one given, or a throw-away ``make()`` whose graphs are freed on the way out, not
+        in a GC pass."""
+        if optimizer is not None:
+            yield optimizer
+        else:
+            trainer = make()
+            yield trainer
+            trainer.release_graphs()
 
     def handle_train_optimization(self, optimizer, outputs, target, inputs, fold_num, total_batches, batch_idx,
                                   epoch_num, model):
@@ -325,22 +366,19 @@ class BaseTraining(object):
         """:424-465 + record_final_epoch_testing_results (:519-524): no_grad forward with train-mode modules (the
         reference never calls eval()), loss meter, window argmax, per-patient votes -- reduced on the device."""
         store, batch_size, shuffle = test_loader
-        trainer = optimizer if optimizer is not None else HotPathTrainer(model, use_graph=_flag(self.args, 'use_graph', True),
-                                                                         **self._loss_kwargs())
-        trainer.clip_odd_batches = self.clip_odd_batches
-        slot = self.args.test_patient_slot
-        if slot is None:
-            slot = torch.zeros(store.tiles.shape[0], dtype=torch.int64)
-        gen = None                                            # the test loader shuffles too unless --unshuffled (:333-338)
-        if shuffle and self.args.seed is not None:
-            gen = torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + 500009)
-        steps = test_epoch_steps(trainer, store, slot, batch_size=batch_size, shuffle=shuffle, generator=gen)
-        if _steps_only:                                       # folds in flight: the caller walks the steps and finishes
-            return steps
-        for _ in steps:
-            pass
-        if optimizer is None:
-            trainer.release_graphs()                          # a throw-away trainer: free its graphs here, not in a GC pass
+        with self._test_trainer(optimizer, lambda: HotPathTrainer(model, use_graph=_flag(self.args, 'use_graph', True),
+                                                                  **self._loss_kwargs())) as trainer:
+            trainer.clip_odd_batches = self.clip_odd_batches
+            slot = self.args.test_patient_slot
+            if slot is None:
+                slot = torch.zeros(store.tiles.shape[0], dtype=torch.int64)
+            # the test loader shuffles too unless --unshuffled (:333-338)
+            gen = self._epoch_generator(fold_num, epoch_num, 500009) if shuffle else None
+            steps = test_epoch_steps(trainer, store, slot, batch_size=batch_size, shuffle=shuffle, generator=gen)
+            if _steps_only:                                   # folds in flight: the caller walks the steps of ITS trainer and finishes
+                return steps
+            for _ in steps:
+                pass
         return self._finish_test_epoch(steps, epoch_num, fold_num)
 
     def _finish_test_epoch(self, steps, epoch_num, fold_num):
@@ -453,9 +491,7 @@ class BaseTraining(object):
                 if not _flag(a, 'no_train'):
                     plans = []
                     for fold_num, stream, model, optimizer, tr_ds, te_ds in ctx:
-                        gen = None
-                        if a.seed is not None:
-                            gen = torch.Generator().manual_seed(a.seed + 1000 * fold_num + epoch_num)
+                        gen = self._epoch_generator(fold_num, epoch_num)
                         if shuffle:
                             gen = shared_generator(optimizer, gen)
                         with torch.cuda.stream(stream):      # the index upload is ordered before the fold's gathers
@@ -685,12 +721,8 @@ class ProtoPNetModel(object):
     def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
         from .protopnet import ProtoPNetTrainer
         a = self.args
-        if a.optimizer not in ('adam', 'sgd'):
-            raise ValueError('optimizer must be adam or sgd')
-        return ProtoPNetTrainer(model, optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
-                                clust_lambda=a.clust_lambda, sep_lambda=a.sep_lambda, use_l1=bool(_flag(a, 'use_l1')),
-                                world_size=world_size, rank=rank, process_group=process_group,
-                                use_graph=_flag(a, 'use_graph', True))
+        kw = dict(self._trainer_kwargs(world_size, rank, process_group), clip_grad=False)      # never clips (the class docstring)
+        return ProtoPNetTrainer(model, clust_lambda=a.clust_lambda, sep_lambda=a.sep_lambda, use_l1=bool(_flag(a, 'use_l1')), **kw)
 
     def calc_loss(self, model, cls_output, target, min_distances):
         """-> loss, cls_loss, cluster_cost, separation_cost, l1 (:1194-1247), one launch (+ the l1 term with --use-l1)."""
@@ -708,48 +740,32 @@ class ProtoPNetModel(object):
     def _process_test_batch_results(self, outputs, target, inputs, fold_num):
         return outputs.argmax(dim=-1).cpu().tolist()
 
-    def _epoch_generator(self, fold_num, epoch_num, salt=0):
-        if self.args.seed is None:
-            return None
-        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + 100003 * salt)
-
     def run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num):
         """:1255-1329: the warm optimiser while epoch_num <= n_warm_epochs, the joint one after; from push_start_epoch on,
         every push_every_n epochs, the push and n_push_iters last-layer passes over the training set."""
         a = self.args
-        store, batch_size, shuffle = train_loader
-        if optimizer.model is not model:
-            raise ValueError('optimizer was built for another model')
         optimizer.set_phase('warm' if epoch_num <= a.n_warm_epochs else 'joint')
-        for loss in run_train_epoch_from_store(optimizer, store, batch_size=batch_size, shuffle=shuffle,
-                                               generator=self._epoch_generator(fold_num, epoch_num)):
-            parts = optimizer.last_parts.clone()              # (the captured step's own buffer: the next replay refills it)
-            for i, name in ((1, 'cls_loss'), (2, 'clst_loss'), (3, 'sep_loss'), (4, 'l1_loss')):
-                self.results.update_meter(name, fold_num, parts[i])
-            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
-            self.results.update_meter('loss', fold_num, loss)
-            if _flag(a, 'debug'):
-                break
+        BaseTraining.run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num)
         if epoch_num >= a.push_start_epoch and (epoch_num - a.push_start_epoch) % a.push_every_n == 0:
             self.push_func(train_loader, model, epoch_num)
             optimizer.set_phase('last_layer')
             for it in range(a.n_push_iters):
-                for loss in run_train_epoch_from_store(optimizer, store, batch_size=batch_size, shuffle=shuffle,
-                                                       generator=self._epoch_generator(fold_num, epoch_num, it + 1)):
+                for loss in self._train_losses(optimizer, train_loader, self._epoch_generator(fold_num, epoch_num, 100003 * (it + 1))):
                     self.results.update_meter('loss', fold_num, loss)
                 if _flag(a, 'debug'):
                     break
 
+    def _book_train_loss(self, optimizer, loss, epoch_num, fold_num):
+        parts = optimizer.last_parts.clone()                  # (the captured step's own buffer: the next replay refills it)
+        for i, name in ((1, 'cls_loss'), (2, 'clst_loss'), (3, 'sep_loss'), (4, 'l1_loss')):
+            self.results.update_meter(name, fold_num, parts[i])
+        BaseTraining._book_train_loss(self, optimizer, loss, epoch_num, fold_num)
+
     def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
         """:1331-1349: under model.eval(), the loss kernel, softmaxed outputs; the votes as in BaseTraining.run_test_epoch."""
-        made = optimizer is None
-        if made:
-            optimizer = self.get_optimizer(model)
-        res = BaseTraining.run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=optimizer,
-                                          _steps_only=_steps_only)
-        if made and not _steps_only:
-            optimizer.release_graphs()
-        return res
+        with self._test_trainer(optimizer, lambda: self.get_optimizer(model)) as trainer:
+            return BaseTraining.run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=trainer,
+                                               _steps_only=_steps_only)
 
 
 class ProtoPNet1DModel(ProtoPNetModel, BaseTraining, PatientClassifierMixin):
@@ -760,18 +776,11 @@ class ProtoPNet1DModel(ProtoPNetModel, BaseTraining, PatientClassifierMixin):
         if M.backbone_class(args.base_network) is not M.DenseNet:
             raise NotImplementedError('protopnet needs a DenseNet base network (forward_no_pool exists only there), got %r'
                                       % (args.base_network,))
-        if self._world_size() > 1:
-            raise NotImplementedError('protopnet runs on one GPU: its phases and the push are not sharded over ranks')
-        n_flight = getattr(args, 'folds_in_flight', None)
-        if n_flight is not None and int(n_flight) > 1:
-            raise NotImplementedError('--folds-in-flight > 1 with protopnet: the phase schedule and the push walk one fold at '
-                                      'a time; run the folds one after the other')
-        args.folds_in_flight = 1
+        _one_gpu_one_fold_at_a_time(
+            args, 'protopnet runs on one GPU: its phases and the push are not sharded over ranks',
+            '--folds-in-flight > 1 with protopnet: the phase schedule and the push walk one fold at a time; run the folds one '
+            'after the other')
         super(ProtoPNet1DModel, self).__init__(args)
-
-    @staticmethod
-    def _world_size():
-        return int(os.environ.get('WORLD_SIZE', '1'))
 
     def get_network(self, base_network):
         a = self.args
@@ -838,7 +847,19 @@ class LSTMOnlyWithPackingModel(LSTMOnlyModel):
         return M.LSTMOnlyWithPacking(self._hidden_units(), self.args.n_sub_batches)
 
 
-class SiameseMixin(object):
+class MeterSummaryMixin(object):
+    """``perform_post_modeling_actions`` of the pretraining stages (SiameseMixin, RegressorMixin)."""
+
+    def perform_post_modeling_actions(self):
+        """:576-577 / :676-677 save the results object; here: the meters' means, returned and kept as ``self.summary``."""
+        self.summary = {}
+        for (name, fold), vals in self.results.meters.items():
+            host = [float(v.detach()) if isinstance(v, torch.Tensor) else float(v) for v in vals]
+            self.summary['%s/%s' % (name, fold)] = sum(host) / len(host) if host else None
+        return self.summary
+
+
+class SiameseMixin(MeterSummaryMixin):
     """:558-658 for the trainer of ``deepards_amd.siamese``: the datasets are ``SiameseTileStore`` s (``--train-from-pickle`` /
     ``--test-from-pickle``: a SiameseNetworkDataset pickle, read without unpickling, or any prepared ARDSRawDataset pickle /
     .npz; or stores handed in as ``args.train_store`` / ``args.test_store``), ``get_optimizer`` returns a ``SiameseTrainer``,
@@ -854,13 +875,9 @@ class SiameseMixin(object):
         if getattr(args, 'kfolds', None):
             raise ValueError('siamese pretraining is not meant to be run with k-folds (dataset.py:1597): triplets are drawn over '
                              'the whole training set')
-        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-            raise NotImplementedError('siamese pretraining runs on one GPU: the triplet draw and its batch are not sharded over '
-                                      'ranks')
-        n_flight = getattr(args, 'folds_in_flight', None)
-        if n_flight is not None and int(n_flight) > 1:
-            raise NotImplementedError('--folds-in-flight > 1 with siamese pretraining: its dataset has no folds')
-        args.folds_in_flight = 1
+        _one_gpu_one_fold_at_a_time(
+            args, 'siamese pretraining runs on one GPU: the triplet draw and its batch are not sharded over ranks',
+            '--folds-in-flight > 1 with siamese pretraining: its dataset has no folds')
         self._test_skipped = False
         super(SiameseMixin, self).__init__(args)
 
@@ -881,14 +898,6 @@ class SiameseMixin(object):
     def record_testing_results(self, accuracy, epoch_num, fold_num):
         self.results.update_meter('accuracy', fold_num, accuracy)
         self.results.update_meter('accuracy_epoch_{}'.format(epoch_num), fold_num, accuracy)
-
-    def perform_post_modeling_actions(self):
-        """:576-577 saves the results object; here: the meters' means, returned and kept as ``self.summary``."""
-        self.summary = {}
-        for (name, fold), vals in self.results.meters.items():
-            host = [float(v.detach()) if isinstance(v, torch.Tensor) else float(v) for v in vals]
-            self.summary['%s/%s' % (name, fold)] = sum(host) / len(host) if host else None
-        return self.summary
 
     def get_base_datasets(self):
         from .siamese import SiameseTileStore
@@ -915,30 +924,12 @@ class SiameseMixin(object):
 
     def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
         from .siamese import SiameseTrainer
-        a = self.args
-        if a.optimizer not in ('adam', 'sgd'):
-            raise ValueError('optimizer must be adam or sgd')
-        return SiameseTrainer(model, share_anchor=bool(_flag(a, 'share_anchor')), optimizer=a.optimizer,
-                              learning_rate=a.learning_rate, weight_decay=a.weight_decay, clip_grad=bool(_flag(a, 'clip_grad')),
-                              clip_val=a.clip_val, world_size=world_size, rank=rank, process_group=process_group,
-                              use_graph=_flag(a, 'use_graph', True))
+        return SiameseTrainer(model, share_anchor=bool(_flag(self.args, 'share_anchor')),
+                              **self._trainer_kwargs(world_size, rank, process_group))
 
-    def _generator(self, fold_num, epoch_num, salt=0):
-        if self.args.seed is None:
-            return None
-        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + salt)
-
-    def run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num):
+    def _train_epoch_iterator(self):
         from .siamese import run_siamese_train_epoch
-        store, batch_size, shuffle = train_loader
-        if optimizer.model is not model:
-            raise ValueError('optimizer was built for another model')
-        for loss in run_siamese_train_epoch(optimizer, store, batch_size=batch_size, shuffle=shuffle,
-                                            generator=self._generator(fold_num, epoch_num)):
-            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
-            self.results.update_meter('loss', fold_num, loss)
-            if _flag(self.args, 'debug'):
-                break
+        return run_siamese_train_epoch
 
     def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
         from .siamese import run_siamese_test_epoch
@@ -955,15 +946,12 @@ class SiameseMixin(object):
                 self._test_skipped = True
             return None
         store, batch_size, shuffle = test_loader
-        made = optimizer is None
-        trainer = self.get_optimizer(model) if made else optimizer
-        for loss, acc in run_siamese_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
-                                                generator=self._generator(fold_num, epoch_num, 500009)):
-            self.results.update_meter('test_loss', fold_num, loss)
-            self.results.update_meter('test_loss_epoch_{}'.format(epoch_num), fold_num, loss)
-            self.record_testing_results(acc, epoch_num, fold_num)
-        if made:
-            trainer.release_graphs()
+        with self._test_trainer(optimizer, lambda: self.get_optimizer(model)) as trainer:
+            for loss, acc in run_siamese_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
+                                                    generator=self._epoch_generator(fold_num, epoch_num, 500009)):
+                self.results.update_meter('test_loss', fold_num, loss)
+                self.results.update_meter('test_loss_epoch_{}'.format(epoch_num), fold_num, loss)
+                self.record_testing_results(acc, epoch_num, fold_num)
         return {'accuracy': self.results.get_meter('accuracy_epoch_{}'.format(epoch_num), fold_num),
                 'test_loss': self.results.get_meter('test_loss_epoch_{}'.format(epoch_num), fold_num)}
 
@@ -1019,7 +1007,7 @@ def regression_scores(target, preds):
     return mae, float(np.mean(r2)), mse
 
 
-class RegressorMixin(object):
+class RegressorMixin(MeterSummaryMixin):
     """:661-677: a test batch's (n_samples, n_outputs) targets and predictions booked as ``test_mae``, ``r2`` and ``test_mse``."""
 
     def record_testing_results(self, target, batch_preds, fold_num):
@@ -1033,14 +1021,6 @@ class RegressorMixin(object):
 
     def set_loss_criterion(self):
         self.criterion = torch.nn.MSELoss()        # (for calc_loss on tensors somebody already has; the step computes it in-kernel)
-
-    def perform_post_modeling_actions(self):
-        """:676-677 saves the results object; here: the meters' means, returned and kept as ``self.summary``."""
-        self.summary = {}
-        for (name, fold), vals in self.results.meters.items():
-            host = [float(v.detach()) if isinstance(v, torch.Tensor) else float(v) for v in vals]
-            self.summary['%s/%s' % (name, fold)] = sum(host) / len(host) if host else None
-        return self.summary
 
 
 class AutoencoderModel(BaseTraining, RegressorMixin):
@@ -1062,17 +1042,13 @@ class AutoencoderModel(BaseTraining, RegressorMixin):
             raise NotImplementedError('--freeze-base-network with -n autoencoder: the base network IS the model being pretrained; '
                                       'freezing it leaves nothing to train')
         unet = getattr(args, 'base_network', None) == 'unet'
-        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-            if unet:
-                raise NotImplementedError('autoencoder pretraining with --base-network unet runs on one GPU: the sharded step is not '
-                                          'built and was not run')
-            raise NotImplementedError('autoencoder pretraining runs on one GPU: its BatchNorm takes its statistics over the whole '
-                                      'batch, which a batch sharded over ranks changes')
-        n_flight = getattr(args, 'folds_in_flight', None)
-        if n_flight is not None and int(n_flight) > 1:
-            raise NotImplementedError('--folds-in-flight > 1 with -n autoencoder: %s' %
-                                      ('not built and not run for the UNet' if unet else 'the folds run one after the other'))
-        args.folds_in_flight = 1
+        if unet:
+            one_gpu = 'autoencoder pretraining with --base-network unet runs on one GPU: the sharded step is not built and was not run'
+        else:
+            one_gpu = ('autoencoder pretraining runs on one GPU: its BatchNorm takes its statistics over the whole batch, which a '
+                       'batch sharded over ranks changes')
+        _one_gpu_one_fold_at_a_time(args, one_gpu, '--folds-in-flight > 1 with -n autoencoder: %s' %
+                                    ('not built and not run for the UNet' if unet else 'the folds run one after the other'))
         super(AutoencoderModel, self).__init__(args)
 
     def _process_test_batch_results(self, outputs, target, inputs, fold_num):
@@ -1098,42 +1074,21 @@ class AutoencoderModel(BaseTraining, RegressorMixin):
 
     def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
         from .autoencoder import AutoencoderTrainer
-        a = self.args
-        if a.optimizer not in ('adam', 'sgd'):
-            raise ValueError('optimizer must be adam or sgd')
-        return AutoencoderTrainer(model, optimizer=a.optimizer, learning_rate=a.learning_rate, weight_decay=a.weight_decay,
-                                  clip_grad=bool(_flag(a, 'clip_grad')), clip_val=a.clip_val, world_size=world_size, rank=rank,
-                                  process_group=process_group, use_graph=_flag(a, 'use_graph', True))
+        return AutoencoderTrainer(model, **self._trainer_kwargs(world_size, rank, process_group))
 
-    def _generator(self, fold_num, epoch_num, salt=0):
-        if self.args.seed is None:
-            return None
-        return torch.Generator().manual_seed(self.args.seed + 1000 * fold_num + epoch_num + salt)
-
-    def run_train_epoch(self, model, train_loader, optimizer, epoch_num, fold_num):
+    def _train_epoch_iterator(self):
         from .autoencoder import run_autoencoder_train_epoch
-        store, batch_size, shuffle = train_loader
-        if optimizer.model is not model:
-            raise ValueError('optimizer was built for another model')
-        for loss in run_autoencoder_train_epoch(optimizer, store, batch_size=batch_size, shuffle=shuffle,
-                                                generator=self._generator(fold_num, epoch_num)):
-            self.results.update_meter('loss_epoch_{}'.format(epoch_num), fold_num, loss)
-            self.results.update_meter('loss', fold_num, loss)
-            if _flag(self.args, 'debug'):
-                break
+        return run_autoencoder_train_epoch
 
     def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
         from .autoencoder import run_autoencoder_test_epoch
         store, batch_size, shuffle = test_loader
-        made = optimizer is None
-        trainer = self.get_optimizer(model) if made else optimizer
         self.preds = []
-        for x, recon, loss in run_autoencoder_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
-                                                         generator=self._generator(fold_num, epoch_num, 500009)):
-            self.results.update_meter('test_loss', fold_num, loss)
-            self.preds += self._process_test_batch_results(recon, None, x, fold_num)
-        if made:
-            trainer.release_graphs()
+        with self._test_trainer(optimizer, lambda: self.get_optimizer(model)) as trainer:
+            for x, recon, loss in run_autoencoder_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
+                                                             generator=self._epoch_generator(fold_num, epoch_num, 500009)):
+                self.results.update_meter('test_loss', fold_num, loss)
+                self.preds += self._process_test_batch_results(recon, None, x, fold_num)
         return {k: self.results.get_meter(k, fold_num) for k in ('test_mae', 'r2', 'test_mse')}
 
 
@@ -1260,6 +1215,26 @@ def build_parser():
                         'as e.g. 2 groups x 2 ranks).  Default 1: every fold over all ranks')
     parser.add_argument('--act-dtype', choices=['f32', 'bf16'], help='activation storage under --conv-dtype bf16 (default bf16 for ResNets)')
     return parser
+
+
+def stage_main(argv, parser, networks, stage_map, defaults):
+    """The command line of a pretraining stage (``deepards_amd.siamese`` / ``deepards_amd.autoencoder``): the stage's own
+    ``parser``, the ``-n`` names it allows, its map of driver classes and its defaults -> (the driver class, its results).
+    One GPU, so none of the distributed set-up of ``main``."""
+    import sys
+    argv = sys.argv[1:] if argv is None else list(argv)
+    for a in argv:
+        if a.split('=')[0] in OUT_OF_SCOPE_FLAGS:
+            raise SystemExit('%s steers code outside the accelerated hot path and is not accepted by this build' % a.split('=')[0])
+    args = Configuration(parser.parse_args(argv), defaults)
+    if args.network not in networks:
+        raise SystemExit('-n must be one of %s' % ', '.join(networks))
+    if args.save_model_per_epoch and not args.save_model:
+        raise Exception('Must specify a filename to save your model using --save-model')
+    cls = stage_map[args.network](args)
+    results = cls.train_and_test()
+    cls.perform_post_modeling_actions()
+    return cls, results
 
 
 def main(argv=None):

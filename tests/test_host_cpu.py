@@ -1044,3 +1044,19 @@ def test_driver_and_checkpoint_loader_build_through_one_function(monkeypatch, tm
     kw = {'base_network': 'vgg13', 'resnet_kwargs': {'initial_planes': 128}}
     net = C.load_base_network(path, M.base_networks, kw)
     assert calls[1:] == [('vgg13', kw)] and float(net.weight.detach()) == 3.0
+
+
+def test_epoch_generator_seeds_are_pinned():
+    """One seed formula for every family's epochs: seed + 1000 fold + epoch (+ 500009 for a test epoch, + 100003 (it + 1)
+    for ProtoPNet's last-layer pass ``it``); no seed, no generator (torch's global RNG, like a DataLoader)."""
+    import types
+    from deepards_amd import train_ards_detector as T
+    gen = T.BaseTraining._epoch_generator
+    drv = types.SimpleNamespace(args=types.SimpleNamespace(seed=3))
+    assert gen(drv, 1, 2).initial_seed() == 1005
+    assert gen(drv, 1, 2, 500009).initial_seed() == 501014
+    assert gen(drv, 1, 2, 100003 * (0 + 1)).initial_seed() == 101008
+    drv.args.seed = None
+    assert gen(drv, 1, 2) is None and gen(drv, 1, 2, 500009) is None
+    for cls in (T.ProtoPNet1DModel, T.SiameseCNNLinearModel, T.AutoencoderModel, T.CNNLinearModel):
+        assert cls._epoch_generator is gen and not hasattr(cls, '_generator')       # the families share the one formula
