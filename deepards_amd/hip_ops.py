@@ -1789,3 +1789,5 @@ from .autoencoder_ops import (sel_from_bool, sel_to_bool, bn_maxpool2_idx_plan, 
                               bn_maxpool2_idx_bwd, unpool2_fwd, unpool2_bwd, ae_out_fwd, ae_out_bwd)
 from .unet_ops import (unet_plan, unet_bias_relu, unet_bias_relu_pool2_fwd, unet_relu_upsample2_fwd,   # noqa: E402,F401
                        unet_relu_upsample2_bwd, unet_pool2_skip_bwd, unet_relu_bwd, unet_out_fwd, unet_out_bwd)
+from .regress_ops import (regress_rows_per_block, regress_shape_ok, regress_workspace, regress_fwd, regress_bwd,   # noqa: E402,F401
+                          regress_head_loss)

@@ -430,14 +430,25 @@ class IngestedDataset(object):
     None when loaded from an anonymised export), patient_slot (N,) int64 (first-appearance order), hours (N, NB)
     float64 (NaN padded), metadata (N, M) float64 or None, scaling_factors {fold|None: (mu (C,), std (C,))},
     kfold_patient_splits {fold: {'train': slots, 'test': slots}} or None, plus n_sub_batches / dataset_type / train /
-    total_kfolds."""
+    total_kfolds.
+
+    ``breath_level`` (the ``*_bm_target`` datasets, dataset.py:522-529): one sequence per breath -- windows are the rows (N, 1, L),
+    targets the raw breath metadata (N, M) float64, hours all NaN, n_sub_batches 1.  ``regressor.BreathMetaStore`` takes such a
+    dataset; ``to_store`` refuses it."""
 
     def __init__(self, windows, targets, patients, hours, scaling_factors, n_sub_batches, dataset_type, train=True,
-                 total_kfolds=None, kfold_patient_splits=None, metadata=None, patient_slot=None):
+                 total_kfolds=None, kfold_patient_splits=None, metadata=None, patient_slot=None, breath_level=False):
+        self.breath_level = bool(breath_level)
         self.windows = np.ascontiguousarray(windows, dtype=np.float64)
-        self.targets = np.ascontiguousarray(targets, dtype=np.float32)
-        if self.windows.ndim != 4 or self.targets.shape != (self.windows.shape[0], 2):
-            raise ValueError('windows must be (N, NB, C, L) and targets (N, 2)')
+        if self.breath_level:
+            self.targets = np.ascontiguousarray(targets, dtype=np.float64)
+            if self.windows.ndim != 3 or self.windows.shape[1] != 1 or self.targets.ndim != 2 or \
+                    self.targets.shape[0] != self.windows.shape[0] or self.targets.shape[1] < 1:
+                raise ValueError('a breath-level dataset holds rows (N, 1, L) and targets (N, M)')
+        else:
+            self.targets = np.ascontiguousarray(targets, dtype=np.float32)
+            if self.windows.ndim != 4 or self.targets.shape != (self.windows.shape[0], 2):
+                raise ValueError('windows must be (N, NB, C, L) and targets (N, 2)')
         self.patients = None if patients is None else np.asarray(patients).astype(str)
         if patient_slot is None and self.patients is not None:
             slots, seen = [], {}
@@ -469,6 +480,8 @@ class IngestedDataset(object):
         out = dict(x=self.windows, target=self.targets, hours=self.hours,
                    n_sub_batches=self.n_sub_batches, dataset_type=str(self.dataset_type), train=self.train,
                    total_kfolds=-1 if self.total_kfolds is None else self.total_kfolds)
+        if self.breath_level:
+            out['breath_level'] = True
         if self.patient_slot is not None:
             out['patient_slot'] = self.patient_slot
         for k, (mu, std) in self.scaling_factors.items():
@@ -504,6 +517,9 @@ class IngestedDataset(object):
         derived from all windows when the pickle holds none).  K-fold datasets: ``enable_kfolds`` is applied with the
         pickled patient splits / factors when present (``from_pickle`` keeps them too, dataset.py:740-741)."""
         from .data import DeviceTileStore
+        if self.breath_level:
+            raise ValueError('a breath-level dataset (%s) has no one-hot window targets: it is read by '
+                             'deepards_amd.regressor.BreathMetaStore.from_dataset' % self.dataset_type)
         chans = self.windows.shape[2]
         key = fold if fold in self.scaling_factors else None
         if key in self.scaling_factors:
@@ -549,6 +565,8 @@ def dataset_from_tree(root):
     seqs = st.get('all_sequences')
     if not isinstance(seqs, list) or not seqs:
         raise ValueError('the dataset holds no sequences')
+    if len(list(seqs[0])) == 4 and np.ndim(resolve(list(seqs[0])[1])) == 2:
+        return _breath_level_from_state(st, seqs)
     windows, targets, patients, hours, metas = [], [], [], [], []
     for seq in seqs:
         seq = list(seq)
@@ -596,6 +614,42 @@ def dataset_from_tree(root):
                            metadata=np.stack(metas) if metas else None, patient_slot=np.array(slots, dtype=np.int64))
 
 
+def _breath_level_from_state(st, seqs):
+    """The ``*_bm_target`` datasets (dataset.py:522-529): one sequence ``[patient, (1, L) flow, meta (M,), [nan]]`` per breath;
+    ``__getitem__`` hands the loader ``meta`` in the target's place (:1359-1361).  -> a breath-level IngestedDataset.  A stored
+    factor array is taken as it is through ``_channel_scalars`` (every entry of the reference's broadcast holds one number)."""
+    rows, metas, patients = [], [], []
+    for i, seq in enumerate(seqs):
+        seq = list(seq)
+        if len(seq) != 4:
+            raise ValueError('breath-level sequence %d has %d items, not [patient, data, meta, target]' % (i, len(seq)))
+        data = np.asarray(resolve(seq[1]), dtype=np.float64)
+        meta = np.asarray(resolve(seq[2]), dtype=np.float64).reshape(-1)
+        if data.ndim != 2 or data.shape[0] != 1:
+            raise ValueError('breath-level sequence %d: a (1, L) row expected, got %s' % (i, data.shape))
+        if metas and meta.shape != metas[0].shape:
+            raise ValueError('breath-level sequence %d: %d metadata values where the first breath has %d' %
+                             (i, meta.size, metas[0].size))
+        if not np.all(np.isfinite(meta)):
+            raise ValueError('breath-level sequence %d has a non-finite target %s: the reference drops such breaths when it builds '
+                             'the dataset (dataset.py:912-962)' % (i, meta.tolist()))
+        rows.append(data)
+        metas.append(meta)
+        patients.append(_plain(seq[0]))
+    factors = {}
+    sf = st.get('scaling_factors')
+    if isinstance(sf, dict):
+        for k, v in sf.items():
+            k = _plain(k)
+            mu, std = (_channel_scalars(q) for q in v)
+            factors[None if k is None else int(k)] = (np.ravel(mu)[:1], np.ravel(std)[:1])
+    total = _plain(st.get('total_kfolds'))
+    n = len(rows)
+    return IngestedDataset(np.stack(rows), np.stack(metas), patients, np.full((n, 1), np.nan), factors, 1,
+                           _plain(st.get('dataset_type', 'padded_breath_by_breath_with_full_bm_target')),
+                           train=bool(_plain(st.get('train', True))), total_kfolds=total, breath_level=True)
+
+
 def _iter_array(v):
     """Items of a patient-id container: a str / bytes ndarray, a list, or an OBJECT-dtype ndarray (pandas'
     ``.unique()`` of strings, dataset.py:779-781), whose pickled payload is a plain list of str -- read as that list."""
@@ -634,6 +688,7 @@ def load_npz(path):
             f = int(k.split('/')[1])
             splits[f] = {'train': z[k], 'test': z['split/%d/test' % f]}
     total = int(z['total_kfolds']) if 'total_kfolds' in files else -1
+    breath_level = bool(z['breath_level']) if 'breath_level' in files else False
     return IngestedDataset(
         z['x'], z['target'], z['patients'] if 'patients' in files else None,
         z['hours'] if 'hours' in files else np.full((n, z['x'].shape[1]), np.nan), factors,
@@ -641,7 +696,7 @@ def load_npz(path):
         str(z['dataset_type']) if 'dataset_type' in files else 'unpadded_centered_sequences',
         train=bool(z['train']) if 'train' in files else True, total_kfolds=None if total < 0 else total,
         kfold_patient_splits=splits or None, metadata=z['metadata'] if 'metadata' in files else None,
-        patient_slot=z['patient_slot'] if 'patient_slot' in files else None)
+        patient_slot=z['patient_slot'] if 'patient_slot' in files else None, breath_level=breath_level)
 
 
 def load_dataset(path):

@@ -17,6 +17,7 @@ from .lstm_only import LSTMOnlyNetwork, LSTMOnlyWithPacking             # noqa: 
 from .siamese import Identity, SiameseCNNLinearNetwork, SiameseCNNLSTMNetwork, SiameseCNNTransformerNetwork         # noqa: F401
 from .autoencoder import AutoencoderCNN, AutoencoderNetwork             # noqa: F401  (not a Backbone: no row in the tables below)
 from .unet import UNet                                                  # noqa: F401  (the autoencoder route's other base network: no row either)
+from .regressor import CNNRegressor                                     # noqa: F401  (breath-metadata pretraining: a head on any Backbone)
 
 # the 1-D BasicBlock / growth-32 entries of the reference's base_networks (train_ards_detector.py:45-69); resnet34 is in
 # its models/resnet.py (:178) though not in that dict; se_resnet18 is the SE net its experiment scripts sweep; se_resnet50 /

@@ -1095,6 +1095,113 @@ class AutoencoderModel(BaseTraining, RegressorMixin):
 autoencoder_network_map = {'autoencoder': AutoencoderModel}
 
 
+class CNNRegressorModel(BaseTraining, RegressorMixin):
+    """:1081-1099.  NOT in ``network_map`` (its key set is pinned): reached through ``python -m deepards_amd.regressor -n
+    cnn_regressor`` (``regressor_network_map``) or built directly.  The datasets are ``BreathMetaStore`` s (``--train-from-pickle`` /
+    ``--test-from-pickle``: a ``*_bm_target`` pickle, read without unpickling, its .npz, or a window dataset with per-breath
+    metadata; or stores handed in as ``args.train_store`` / ``args.test_store``).  ``n_bm_features`` comes from the dataset type
+    (3 / 7 / 9), for a window dataset from the width of its metadata.  ``get_optimizer`` returns a ``RegressorTrainer``; the test
+    epoch is ``BaseTraining.run_test_epoch`` (:424-465: train-mode modules under ``no_grad``, no ``model.eval()``) and books
+    ``test_loss``, ``test_mae``, ``r2`` and ``test_mse`` per batch.  One GPU, no folds in flight, no k-folds;
+    ``--load-base-network`` is accepted (the generic path), ``--freeze-base-network`` is not."""
+
+    def __init__(self, args):
+        from .regressor import BM_TARGET_TYPES
+        if getattr(args, 'kfolds', None):
+            raise ValueError('--kfolds with -n cnn_regressor: the breath-metadata dataset has no class to stratify patients by '
+                             '(its target slot holds [nan])')
+        if _flag(args, 'freeze_base_network'):
+            raise NotImplementedError('--freeze-base-network with -n cnn_regressor: the base network is what is being pretrained')
+        if getattr(args, 'loss_func', None) not in (None, 'bce'):          # ('bce' is what defaults.yml merges in for "unset")
+            raise ValueError('-loss %s with -n cnn_regressor: the regressor\'s loss is MSELoss (train_ards_detector.py:674), '
+                             'there is no choice' % args.loss_func)
+        if getattr(args, 'conv_dtype', None) not in (None, 'f32') or getattr(args, 'act_dtype', None) == 'bf16':
+            raise NotImplementedError('--conv-dtype %s / --act-dtype %s with -n cnn_regressor: the regression head reads float '
+                                      'maps only' % (getattr(args, 'conv_dtype', None), getattr(args, 'act_dtype', None)))
+        _one_gpu_one_fold_at_a_time(
+            args, 'breath-metadata pretraining runs on one GPU: BatchNorm takes its statistics over the whole batch, which a '
+                  'batch sharded over ranks changes',
+            '--folds-in-flight > 1 with -n cnn_regressor: its dataset has no folds')
+        if args.dataset_type in BM_TARGET_TYPES:
+            self.n_bm_features = BM_TARGET_TYPES[args.dataset_type]
+        if getattr(args, 'loss_func', None) is None:
+            args.loss_func = 'bce'                         # (BaseTraining checks the name; set_loss_criterion below ignores it)
+        super(CNNRegressorModel, self).__init__(args)
+
+    def calc_loss(self, outputs, target, inputs):
+        return self.criterion(outputs, target)
+
+    def _process_test_batch_results(self, outputs, target, inputs, fold_num):
+        batch_preds = outputs.cpu().numpy()
+        target = target.cpu()
+        self.record_testing_results(target, batch_preds, fold_num)
+        return batch_preds.tolist()
+
+    def get_network(self, base_network):
+        try:
+            self.n_bm_features
+        except AttributeError:
+            raise Exception('You have specified cnn regressor without specifying which dataset you want to use. Do so with the '
+                            '-dt flag')
+        return M.CNNRegressor(base_network, self.n_bm_features)
+
+    def get_base_datasets(self):
+        from .regressor import BM_TARGET_TYPES, BreathMetaStore
+        a = self.args
+        if a.train_store is not None:
+            train, test = a.train_store, a.test_store
+        else:
+            if not a.train_from_pickle:
+                raise ValueError('no dataset: pass --train-from-pickle <dataset.pkl|.npz> (or args.train_store / args.test_store); '
+                                 'building one from raw ventilator files (--data-path) is outside the accelerated path')
+            train = BreathMetaStore.from_pickle(a.train_from_pickle, device=self.device)
+            # test_dataset.scaling_factors = train_dataset.scaling_factors (:285)
+            test = BreathMetaStore.from_pickle(a.test_from_pickle, device=self.device, scaling_from=train) \
+                if a.test_from_pickle else None
+        if not isinstance(train, BreathMetaStore) or not (test is None or isinstance(test, BreathMetaStore)):
+            raise TypeError('breath-metadata pretraining takes BreathMetaStore datasets')
+        for ds, name in ((train, 'train'), (test, 'test')):
+            if ds is None:
+                continue
+            want = BM_TARGET_TYPES.get(a.dataset_type)
+            if want is not None and ds.n_targets != want:
+                raise ValueError('-dt %s means %d breath-metadata targets, the %s dataset has %d' %
+                                 (a.dataset_type, want, name, ds.n_targets))
+            if ds.n_targets != train.n_targets:
+                raise ValueError('the test dataset has %d targets, the train dataset %d' % (ds.n_targets, train.n_targets))
+        if a.dataset_type not in BM_TARGET_TYPES and train.dataset_type not in BM_TARGET_TYPES:
+            self.n_bm_features = train.n_targets           # a window dataset's metadata (BreathMetaStore.from_windows)
+        if any(v is not None for v in self._filter_kwargs().values()) or a.train_store is None:
+            for ds in (train, test):
+                if ds is not None:
+                    ds.set_filters(**self._filter_kwargs())
+        return train, test
+
+    def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
+        from .regressor import RegressorTrainer
+        return RegressorTrainer(model, **self._trainer_kwargs(world_size, rank, process_group))
+
+    def _train_epoch_iterator(self):
+        from .regressor import run_regressor_train_epoch
+        return run_regressor_train_epoch
+
+    def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
+        from .regressor import run_regressor_test_epoch
+        if test_dataset is None:
+            return None
+        store, batch_size, shuffle = test_loader
+        self.preds = []
+        with self._test_trainer(optimizer, lambda: self.get_optimizer(model)) as trainer:
+            for target, out, loss in run_regressor_test_epoch(trainer, store, batch_size=batch_size, shuffle=shuffle,
+                                                              generator=self._epoch_generator(fold_num, epoch_num, 500009)):
+                self.results.update_meter('test_loss', fold_num, loss)
+                self.preds += self._process_test_batch_results(out, target, None, fold_num)
+        return {k: self.results.get_meter(k, fold_num) for k in ('test_mae', 'r2', 'test_mse')}
+
+
+regressor_network_map = {'cnn_regressor': CNNRegressorModel}
+
+
 network_map = {
     'cnn_lstm': CNNLSTMModel,
     'cnn_linear': CNNLinearModel,
@@ -1253,6 +1360,10 @@ def main(argv=None):
         if a.split('=')[0] in OUT_OF_SCOPE_FLAGS:
             raise SystemExit('%s steers code outside the accelerated cnn_linear hot path (SURVEY.md section 2) and is not '
                              'accepted by this build' % a.split('=')[0])
+    for i, a in enumerate(argv):
+        if (a in ('-n', '--network') and argv[i + 1:i + 2] == ['cnn_regressor']) or a == '--network=cnn_regressor':
+            raise SystemExit('-n cnn_regressor is a pretraining stage with its own command line (the network_map of this driver '
+                             'is pinned): python -m deepards_amd.regressor -n cnn_regressor ...')
     args = Configuration(build_parser().parse_args(argv), BUILD_DEFAULTS)
     if args.save_model_per_epoch and not args.save_model:
         raise Exception('Must specify a filename to save your model using --save-model')

@@ -872,6 +872,32 @@ int da_gconv3_dgrad(const float* dy, const float* w, float* dx, int rows, int Li
 int da_gconv3_wgrad(const float* dy, const float* x, float* dw, float* workspace, int rows, int Lin, int C, int stride,
                     int accumulate, da_stream_t stream);
 
+/* ---- breath-metadata regression (csrc/regress.hip): the head of CNNRegressor, models/torch_cnn_bm_regressor.py -----------
+ *     feat[r][c] = (sum_{p < 7} x[r][p][c]) / 7 (form 1: the map [R][7][F], position pitch ld) | x[r][c] (form 0: [R][F], row pitch ld)
+ *     out[r][m]  = bias[m] + sum_c W[m][c] feat[r][c];    loss[0] = sum (out - target)^2 / (R M)
+ *     d = 2 (out - target) gscale / (R M);  dfeat = W^T d (m rising) -> dx = dfeat / 7 at the seven positions | dflat;
+ *     dW[m][c] (+)= sum_r d[r][m] feat[r][c];  db[m] (+)= sum_r d[r][m]
+ * All float32; W [M][F], bias [M], target / out [R][M].  Shapes (da_regress_shape_ok): R in [1, 2^24], F in [1, 2^20], M in
+ * [1, 16], form 0 / 1, 7 R F < 2^40; anything else, ld / ldf / ldg < F or a NULL operand -> DA_EINVAL before any launch.
+ * 16-byte loads and stores when F and the pitches are multiples of 4 and the pointers 16-byte aligned; a scalar path
+ * otherwise.  No float atomics: every sum's order is a function of (R, F, M, form) and of that path, the same bits every
+ * call.  Each entry launches on `stream` only (two launches), allocates nothing and never synchronises.
+ *   da_regress_fwd    form 1 writes feat [R][F] (what the backward reads instead of the map); form 0 writes none (feat may be
+ *                     NULL: the backward takes x itself).  out and loss written.
+ *   da_regress_bwd    feat: the forward's (ldf = F) or the flat operand (ldf = ld).  dx rows of pitch ldg (form 1: position
+ *                     pitch), every element of the F columns written; dW, db (+)= with `accumulate`; gscale multiplies the
+ *                     gradients only.  workspace: da_regress_workspace bytes (one partial [M][F] per row block), written before
+ *                     it is read.
+ *   da_regress_rows_per_block   rows one block of the two row kernels takes (tests place R around it). */
+int da_regress_rows_per_block(void);
+int da_regress_shape_ok(int R, int F, int M, int form);
+size_t da_regress_workspace(int R, int F, int M);
+int da_regress_fwd(const float* x, int ld, int form, const float* W, const float* bias, const float* target, float* feat,
+                   float* out, float* loss, int R, int F, int M, da_stream_t stream);
+int da_regress_bwd(const float* feat, int ldf, const float* W, const float* out, const float* target, float* dx, int ldg,
+                   int form, float* dW, float* db, float* workspace, float gscale, int accumulate, int R, int F, int M,
+                   da_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
