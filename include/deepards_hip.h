@@ -898,6 +898,33 @@ int da_regress_bwd(const float* feat, int ldf, const float* W, const float* out,
                    int form, float* dW, float* db, float* workspace, float gscale, int accumulate, int R, int F, int M,
                    da_stream_t stream);
 
+/* ---- dynamic time warping (csrc/dtw.hip): dtw_lib.py's `dtw(x, y)` (dtwco's defaults as its documentation states them; never
+ * compared with dtwco itself), P pairs per launch, and the ordered means dtw_lib takes of the distances --------------------
+ *     c(i,j) = |x[i] - y[j]| (metric 0) | (x[i] - y[j])^2 (metric 1, the product rounded on its own);  +inf where band >= 0
+ *              and |i - j| > band
+ *     D(i,j) = c(i,j) + min(D(i-1,j), D(i,j-1), D(i-1,j-1)),  D(-1,-1) = 0, every other missing neighbour +inf;  dtw = D(n-1,m-1)
+ * in the accumulation type (acc 0: float, 1: double), one IEEE operation per line: the result is defined bit for bit, does not
+ * depend on the order of the cells, dtw(x,y) == dtw(y,x), dtw(x,x) == +0.  NaN input: unspecified.
+ * Operands: two tables of rows, ta [Sa][lda] with n used columns and tb [Sb][ldb] with m (the same table is fine), each float
+ * (a64 / b64 = 0) or double (1), pitches in elements and >= the length; pair p is row ia[p] of ta against row ib[p] of tb
+ * (int32, device).  acc 0 takes float tables only; acc 1 widens float elements exactly.  Shapes (da_dtw_shape_ok):
+ * 1 <= n, m <= da_dtw_max_len() = 4608; anything else, a pitch below the length, P < 1 or a NULL operand -> DA_EINVAL before
+ * any launch, never truncated.  An index outside [0, Sa) / [0, Sb) gives NaN for its pair and reads nothing.  out [P] in the
+ * accumulation type, every element written; a pair's result does not depend on P, on its position or on the other pairs.  No
+ * atomics.  Each entry launches on `stream` only (one launch), allocates nothing and never synchronises.
+ *   da_dtw_plan          out[7] = lanes of the 64 that hold columns, columns per lane (the class of m), steps of the wavefront
+ *                        (n + lanes - 1), pairs (waves) per block, grid, threads per block, LDS bytes -- from the expressions
+ *                        the launch itself uses; launches nothing.
+ *   da_dtw_segment_mean  out[g] = (((0 + d[off[g]]) + d[off[g] + 1]) + ...) / (off[g+1] - off[g]) in double, index order, for the
+ *                        G segments of the offsets [G + 1] (int32, device) over the distances d [P] (float, d64 = 0, or double);
+ *                        an empty segment, or one that leaves [0, P], gives NaN.  One thread per segment. */
+int da_dtw_max_len(void);
+int da_dtw_shape_ok(int n, int m, int acc, int a64, int b64);
+int da_dtw_plan(int n, int m, int P, int acc, int* out);
+int da_dtw_pairs(const void* ta, int a64, int lda, int Sa, int n, const void* tb, int b64, int ldb, int Sb, int m, const int* ia,
+                 const int* ib, int P, int acc, int metric, int band, void* out, da_stream_t stream);
+int da_dtw_segment_mean(const void* dist, int d64, int P, const int* offsets, int G, double* out, da_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
