@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('DA_LIB_PATH') or os.path.join(_HERE, 'libdeepards_hip
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
            'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip',
-           'siamese.hip', 'conv_grouped.hip', 'autoencoder.hip', 'unet.hip', 'regress.hip', 'dtw.hip']
+           'siamese.hip', 'conv_grouped.hip', 'autoencoder.hip', 'unet.hip', 'regress.hip', 'dtw.hip', 'seq_wide.hip']
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -269,6 +269,11 @@ SIGNATURES = {
     'da_dtw_plan': (_I, [_I] * 4 + [_IP]),
     'da_dtw_pairs': (_I, [_P] + [_I] * 4 + [_P] + [_I] * 4 + [_P, _P] + [_I] * 4 + [_P, _P]),
     'da_dtw_segment_mean': (_I, [_P, _I, _I, _P, _I, _P, _P]),
+    'da_seqw_shape_ok': (_I, [_I] * 3),
+    'da_seqw_rnn_fwd': (_I, [_P] * 5 + [_I] * 3 + [_P]),
+    'da_seqw_rnn_bwd': (_I, [_P] * 4 + [_I] * 3 + [_P]),
+    'da_seqw_lstm_fwd': (_I, [_P] * 7 + [_I] * 3 + [_P]),
+    'da_seqw_lstm_bwd': (_I, [_P] * 5 + [_I] * 3 + [_P]),
 }
 
 

@@ -251,10 +251,10 @@ def _own_module_classes():
     deepards_amd.models.* and torch.nn's own module classes (containers, Conv1d / BatchNorm1d / Linear / LSTM ... that
     the models hold as parameter containers)."""
     import inspect
-    from .models import (autoencoder, densenet, regressor, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, unet,
+    from .models import (autoencoder, densenet, nested, regressor, resnet, senet, seresnext, siamese, torch_cnn_linear_network, transformer, unet,
                          vgg)
     allow = []
-    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese, autoencoder, unet, regressor):
+    for mod in (resnet, densenet, senet, seresnext, vgg, torch_cnn_linear_network, transformer, siamese, autoencoder, unet, regressor, nested):
         allow += [c for c in vars(mod).values()
                   if inspect.isclass(c) and issubclass(c, torch.nn.Module) and c.__module__ == mod.__name__]
     allow += [c for c in vars(torch.nn).values() if inspect.isclass(c) and issubclass(c, torch.nn.Module)]

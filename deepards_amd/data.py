@@ -211,6 +211,18 @@ class DeviceTileStore(object):
         ox, ot = out if out is not None else (None, None)
         return self._gather(idx, ox), H.gather_rows(self.targets, idx, out=ot)
 
+    def batch_absolute(self, abs_idx, out=None):
+        """``batch`` for ABSOLUTE window indices, whatever fold is selected (whole-patient items list a patient's windows
+        by their place in the dataset); bounds are checked here against the whole store."""
+        idx = torch.as_tensor(abs_idx, dtype=torch.int64)
+        if idx.dim() != 1:
+            raise ValueError('abs_idx must be a 1-D index list')
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.tiles.shape[0]):
+            raise IndexError('window index out of range [0, %d)' % self.tiles.shape[0])
+        idx = idx.to(self.tiles.device).contiguous()
+        ox, ot = out if out is not None else (None, None)
+        return self._gather(idx, ox), H.gather_rows(self.targets, idx, out=ot)
+
     def device_indices(self, rel_idx):
         """Absolute window indices ON THE DEVICE for a whole list of fold-relative indices (an epoch's permutation): one
         bounds check and one upload per epoch instead of one per batch -- a per-batch host-to-device copy of the

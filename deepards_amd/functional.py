@@ -13,6 +13,7 @@ import torch
 from torch.autograd import Function
 
 from . import hip_ops as H
+from . import seq_wide_ops as SW
 
 POOL_MAX, POOL_AVG = 0, 1
 POOL_MAX_CEIL = 2            # MaxPool1d(3, 2, ceil_mode=True) without padding: SENet.layer0 (H.pool_out_len)
@@ -1625,6 +1626,81 @@ class LSTMFunction(Function):
             H.reduce_rows(dgates.view(rows, g4), out=tbh, accumulate=True)
             return dfeat.view(rows, f), None, None, None, None, None, None, None
         return dfeat.view(rows, f), dw_ih.view(g4, f), dw_hh, db, db.clone(), None, None, None
+
+
+class _WideRecurrence(Function):
+    """Base of the whole-patient recurrences of the nested networks (reference models/cnn_to_nested_layer.py:15,42 / :54,81:
+    nn.RNN(128, 128) / nn.LSTM(128, 128), batch_first, zero state): feat (S * T, 128) -> hs (S, T, 128), S sequences of T
+    window vectors (the networks use S = 1).  Only the recurrence itself is sequential (seq_wide_ops: one workgroup per
+    sequence, w_hh in registers for all T steps); the input projection runs in front of it and dW_ih = dz^T x,
+    dW_hh = dz^T h_prev, db = sum_t dz and dx = dz W_ih behind it, on the conv GEMM kernels (1x1 conv = GEMM) and
+    reduce_rows -- as LSTMFunction does for the short LSTM.  h_prev is hs shifted by one step with a zero row at t = 0."""
+
+    @staticmethod
+    def _project(ctx, feat, w_ih, w_hh, b_ih, b_hh, S):
+        rows, f = feat.shape
+        if S < 1 or rows % S or rows == 0:
+            raise ValueError('wide recurrence: %d feature rows are not S = %d sequences of T >= 1 steps' % (rows, S))
+        g = w_ih.shape[0]
+        x3 = feat.contiguous().view(rows, 1, f)
+        gx = H.conv_fwd(x3, w_ih.view(1, g, f), 1, 0)                       # W_ih is already the forward pack
+        ctx.S = S
+        ctx.gt = _tgt(w_ih, w_hh, b_ih, b_hh)
+        return x3, gx.view(S, rows // S, g)
+
+    @staticmethod
+    def _parameter_grads(ctx, dz, x3, w_ih, hs):
+        tih, thh, tbi, tbh = ctx.gt
+        rows, _, f = x3.shape
+        g, h = w_ih.shape[0], hs.shape[2]
+        dz3 = dz.view(rows, 1, g)
+        dfeat = H.conv_dgrad(dz3, H.repack_weight(w_ih.view(g, f, 1), False, True)[1], 1, 0, 1)
+        hprev = torch.zeros_like(hs)
+        hprev[:, 1:] = hs[:, :-1]
+        direct = tih is not None
+        if direct:
+            _plain_writer()
+        dw_ih = H.conv_wgrad(dz3, x3, 1, 1, 0, out=tih.view(g, f, 1) if direct else None, accumulate=direct)
+        dw_hh = H.conv_wgrad(dz3, hprev.view(rows, 1, h), 1, 1, 0, out=thh.view(g, h, 1) if direct else None, accumulate=direct)
+        db = H.reduce_rows(dz.view(rows, g), out=tbi if direct else None, accumulate=direct)
+        if direct:
+            H.reduce_rows(dz.view(rows, g), out=tbh, accumulate=True)
+            return dfeat.view(rows, f), None, None, None, None, None
+        return dfeat.view(rows, f), dw_ih.view(g, f), dw_hh.view(g, h), db, db.clone(), None
+
+
+class WideRNNFunction(_WideRecurrence):
+    """h_t = tanh(x_t W_ih^T + b_ih + W_hh h_{t-1} + b_hh); nothing is saved beside the output."""
+
+    @staticmethod
+    def forward(ctx, feat, w_ih, w_hh, b_ih, b_hh, S):
+        x3, gx = _WideRecurrence._project(ctx, feat, w_ih, w_hh, b_ih, b_hh, S)
+        hs = SW.rnn_fwd(gx, w_hh, b_ih, b_hh)
+        ctx.save_for_backward(x3, w_ih, w_hh, hs)
+        return hs
+
+    @staticmethod
+    def backward(ctx, dhs):
+        x3, w_ih, w_hh, hs = ctx.saved_tensors
+        dz = SW.rnn_bwd(dhs.contiguous(), w_hh, hs)
+        return _WideRecurrence._parameter_grads(ctx, dz, x3, w_ih, hs)
+
+
+class WideLSTMFunction(_WideRecurrence):
+    """The LSTM cell (gate order i, f, g, o); saved for the backward: cs and the activated gates, 2 560 bytes per step."""
+
+    @staticmethod
+    def forward(ctx, feat, w_ih, w_hh, b_ih, b_hh, S):
+        x3, gx = _WideRecurrence._project(ctx, feat, w_ih, w_hh, b_ih, b_hh, S)
+        hs, cs, gates = SW.lstm_fwd(gx, w_hh, b_ih, b_hh)
+        ctx.save_for_backward(x3, w_ih, w_hh, hs, cs, gates)
+        return hs
+
+    @staticmethod
+    def backward(ctx, dhs):
+        x3, w_ih, w_hh, hs, cs, gates = ctx.saved_tensors
+        dz = SW.lstm_bwd(dhs.contiguous(), w_hh, cs, gates)
+        return _WideRecurrence._parameter_grads(ctx, dz, x3, w_ih, hs)
 
 
 class TransformerBlockFunction(Function):

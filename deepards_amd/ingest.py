@@ -568,6 +568,7 @@ def dataset_from_tree(root):
     if len(list(seqs[0])) == 4 and np.ndim(resolve(list(seqs[0])[1])) == 2:
         return _breath_level_from_state(st, seqs)
     windows, targets, patients, hours, metas = [], [], [], [], []
+    whole_patient = False
     for seq in seqs:
         seq = list(seq)
         if len(seq) == 4:
@@ -577,10 +578,26 @@ def dataset_from_tree(root):
             pt, data, meta, target, hrs = seq
         else:
             raise NotImplementedError('sequences of %d items (dataset.py:1359-1361) are outside the hot path' % len(seq))
-        windows.append(resolve(data))
+        data = resolve(data)
+        hrs = [float(_plain(h)) for h in (hrs if isinstance(hrs, (list, tuple)) else [hrs])]
+        if np.ndim(data) == 4:
+            # a pickle written with whole_patient_super_batch=True (dataset.py:1021-1081, super_batch_tmp_arr): ONE item per
+            # patient, data (W, NB, C, L) with W varying, the patient's target, and the hours of its LAST window only.  Read
+            # as W windows of that patient in order; the windows whose hours the reference dropped get NaN.
+            if meta is not None:
+                raise NotImplementedError('whole-patient items with breath metadata (*_with_bm datasets) are refused: '
+                                          'dataset.py:1084-1085 refuses whole_patient_super_batch with them too')
+            whole_patient = True
+            for w in range(data.shape[0]):
+                windows.append(data[w])
+                targets.append(np.asarray(resolve(target), dtype=np.float64))
+                patients.append(_plain(pt))
+                hours.append(hrs if w == data.shape[0] - 1 else [])
+            continue
+        windows.append(data)
         targets.append(np.asarray(resolve(target), dtype=np.float64))
         patients.append(_plain(pt))
-        hours.append([float(_plain(h)) for h in (hrs if isinstance(hrs, (list, tuple)) else [hrs])])
+        hours.append(hrs)
         if meta is not None:
             metas.append(np.asarray(resolve(meta), dtype=np.float64).reshape(-1))
     x = np.stack(windows)
@@ -608,10 +625,12 @@ def dataset_from_tree(root):
                                dtype=np.int64)
                 for part in ('train', 'test')}
     total = _plain(st.get('total_kfolds'))
-    return IngestedDataset(x, np.stack(targets), patients, hr, factors, _plain(st.get('n_sub_batches', nb)),
-                           _plain(st.get('dataset_type', 'unpadded_centered_sequences')),
-                           train=bool(_plain(st.get('train', True))), total_kfolds=total, kfold_patient_splits=splits,
-                           metadata=np.stack(metas) if metas else None, patient_slot=np.array(slots, dtype=np.int64))
+    ds = IngestedDataset(x, np.stack(targets), patients, hr, factors, _plain(st.get('n_sub_batches', nb)),
+                         _plain(st.get('dataset_type', 'unpadded_centered_sequences')),
+                         train=bool(_plain(st.get('train', True))), total_kfolds=total, kfold_patient_splits=splits,
+                         metadata=np.stack(metas) if metas else None, patient_slot=np.array(slots, dtype=np.int64))
+    ds.whole_patient = whole_patient            # the pickle held one item per patient (nested.PatientSequenceStore regroups them)
+    return ds
 
 
 def _breath_level_from_state(st, seqs):

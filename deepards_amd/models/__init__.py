@@ -18,6 +18,7 @@ from .siamese import Identity, SiameseCNNLinearNetwork, SiameseCNNLSTMNetwork, S
 from .autoencoder import AutoencoderCNN, AutoencoderNetwork             # noqa: F401  (not a Backbone: no row in the tables below)
 from .unet import UNet                                                  # noqa: F401  (the autoencoder route's other base network: no row either)
 from .regressor import CNNRegressor                                     # noqa: F401  (breath-metadata pretraining: a head on any Backbone)
+from .nested import CNNToNestedRNNNetwork, CNNToNestedLSTMNetwork, CNNToNestedTransformerNetwork        # noqa: F401  (whole-patient heads on densenet18)
 
 # the 1-D BasicBlock / growth-32 entries of the reference's base_networks (train_ards_detector.py:45-69); resnet34 is in
 # its models/resnet.py (:178) though not in that dict; se_resnet18 is the SE net its experiment scripts sweep; se_resnet50 /

@@ -269,15 +269,22 @@ class HotPathTrainer(object):
     step takes no target share ``SelfSupervisedTrainer`` below."""
 
     def __init__(self, model, optimizer='sgd', learning_rate=1e-3, weight_decay=1e-4, momentum=0.9,
-                 clip_grad=True, clip_val=0.01, world_size=1, rank=0, process_group=None, use_graph=True,
+                 clip_grad=True, clip_val=0.01, world_size=1, rank=0, process_group=None, use_graph=None,
                  loss='bce', loss_param=None, loss_calc='all_breaths', carry_state=False, eval_test=False):
         if optimizer not in ('sgd', 'adam'):
             raise ValueError('optimizer must be sgd or adam')
         if loss_calc not in LOSS_CALCS:
             raise ValueError('loss_calc must be one of %s, got %r' % (', '.join(LOSS_CALCS), loss_calc))
         from . import models as M_
-        per_breath = isinstance(model, (M_.CNNLSTMNetwork, M_.CNNSingleBreathLinearNetwork, M_.CNNTransformerNetwork))
+        # the nested networks' (1, W, 2) is a per-"breath" output: one patient per step, the target repeated over its W windows
+        nested = isinstance(model, (M_.CNNToNestedRNNNetwork, M_.CNNToNestedLSTMNetwork))
+        per_breath = nested or isinstance(model, (M_.CNNLSTMNetwork, M_.CNNSingleBreathLinearNetwork, M_.CNNTransformerNetwork))
         check_loss_choice(loss, per_breath and loss_calc == 'all_breaths')
+        if nested and loss != 'bce':
+            raise ValueError('the nested networks train with BCEWithLogitsLoss only (NestedMixin.set_loss_criterion fixes it, '
+                             'train_ards_detector.py:681-682): loss_func %s is refused' % loss)
+        if nested and world_size > 1:
+            raise ValueError('the nested networks run one patient per step on one GPU: %d ranks are not built, not run' % world_size)
         if carry_state and not isinstance(model, M_.CNNLSTMNetwork):
             raise ValueError('carry_state needs a CNNLSTMNetwork')
         if carry_state and world_size > 1:
@@ -294,7 +301,9 @@ class HotPathTrainer(object):
         self.lr, self.wd, self.momentum = learning_rate, weight_decay, momentum
         self.clip = clip_val if clip_grad else 0.0
         self.world_size, self.rank, self.group = world_size, rank, process_group
-        self.use_graph = use_graph
+        # None: the captured step, except for the nested networks -- W changes from patient to patient and every W would keep
+        # a graph of its own (gigabytes at large W): they run eagerly unless asked otherwise
+        self.use_graph = (not nested) if use_graph is None else bool(use_graph)
         self.bucket = None
         self.state = {}
         self.steps = 0

@@ -53,7 +53,7 @@ BUILD_DEFAULTS = dict(
     kfolds=None, only_fold=None, load_checkpoint=None, load_base_network=None, save_model=None, saved_models_dir=None,
     train_from_pickle=None, train_to_pickle=None, test_from_pickle=None, test_to_pickle=None,
     experiment_name='deepards_amd', config_override=None, folds_in_flight=None, fold_groups=None, transformer_blocks=2,
-    use_l1=None, average_linear_layer=None, share_anchor=None,
+    use_l1=None, average_linear_layer=None, share_anchor=None, nested_graph=None,
 )
 
 # make_args(): the merged view with every reference default, for callers that build ``args`` in Python
@@ -75,6 +75,7 @@ DEFAULTS = dict(
     butter_low=None, butter_high=None, fft_filtering_low=None, fft_filtering_high=None, post_hoc_downsampling=None,
     n_warm_epochs=3, push_start_epoch=6, push_every_n=6, n_push_iters=5, clust_lambda=0.8, sep_lambda=0.2, n_prototypes=10,
     incorrect_strength=-0.5, use_l1=False, average_linear_layer=False, folds_in_flight=None, share_anchor=False,
+    nested_graph=False,
 )
 
 
@@ -1200,6 +1201,137 @@ class CNNRegressorModel(BaseTraining, RegressorMixin):
 
 
 regressor_network_map = {'cnn_regressor': CNNRegressorModel}
+
+
+class NestedMixin(object):
+    """:680-769 for the nested networks (``deepards_amd.models.nested``): one item is a whole patient.  The datasets are
+    ``nested.PatientSequenceStore`` s over any prepared window dataset (``--train-from-pickle`` / ``--test-from-pickle``, or stores
+    handed in as ``args.train_store`` / ``args.test_store``); k-folds split patients as the window path does; a step is one patient
+    (``args.batch_size`` is forced to 1, :774,785); ``calc_loss`` is BCE on every window or on the last (``--loss-calc``,
+    :750-755); the test epoch runs train-mode modules under no_grad and every window's argmax votes for its patient
+    (``_process_test_batch_results`` / ``transform_obs_idx``, :684-687,764-765) through the ``Results`` path of the other
+    classifiers.  The step runs EAGERLY unless ``nested_graph`` (``--graph``) is set: W changes from patient to patient and
+    a captured step is kept per W; ``use_graph`` is not read.  One GPU, the folds one after the other."""
+    per_breath_outputs = True
+
+    def _init_nested(self, args):
+        args.batch_size = 1
+        if args.loss_func != 'bce':
+            raise ValueError('the nested networks train with BCEWithLogitsLoss only (NestedMixin.set_loss_criterion fixes it, '
+                             'train_ards_detector.py:681-682): -loss %s is refused' % args.loss_func)
+        legacy = getattr(args, 'oversample', None)
+        if _flag(args, 'oversample_minority') or legacy:
+            raise NotImplementedError('currently oversampling with whole patient super batch does not work')     # dataset.py:443
+        _one_gpu_one_fold_at_a_time(
+            args, 'the nested networks on more than one GPU: not built, not run (a step is one patient on one GPU)',
+            '--folds-in-flight > 1 with the nested networks: not built, not run (the folds run one after the other)')
+
+    def set_loss_criterion(self):
+        from . import functional as F_
+        self.criterion = F_.bce_with_logits
+
+    def _loss_calc(self):
+        lc = getattr(self.args, 'loss_calc', None) or 'all_breaths'
+        if lc not in ('all_breaths', 'last_breath'):
+            raise ValueError('loss_calc must be all_breaths or last_breath, got %r' % (lc,))
+        return lc
+
+    def calc_loss(self, outputs, target, inputs):
+        if self._loss_calc() == 'all_breaths':
+            return self.criterion(outputs, target.reshape(-1, 1, 2).repeat((1, outputs.shape[1], 1)))
+        return self.criterion(outputs[:, -1], target)
+
+    def _process_test_batch_results(self, outputs, target, inputs, fold_num):
+        return outputs.argmax(dim=-1).cpu().view(-1).tolist()
+
+    def transform_obs_idx(self, obs_idx, outputs):
+        return obs_idx.reshape((outputs.shape[0], 1)).repeat((1, outputs.shape[1])).view(-1)
+
+    def get_base_datasets(self):
+        from .nested import PatientSequenceStore
+        from .ingest import load_dataset
+        a = self.args
+        if a.train_store is not None:
+            train, test = a.train_store, a.test_store
+        else:
+            if not a.train_from_pickle:
+                raise ValueError('no dataset: pass --train-from-pickle <dataset.pkl|.npz> (or args.train_store / args.test_store); '
+                                 'building whole-patient datasets from raw ventilator files is outside the accelerated path')
+            ds = load_dataset(a.train_from_pickle)
+            if a.kfolds is not None and ds.total_kfolds is None:
+                ds.total_kfolds = a.kfolds
+            ds.train = True
+            train = PatientSequenceStore.from_windows(ds, device=self.device, random_kfold=bool(_flag(a, 'random_kfold')))
+            train.store.set_filters(**self._filter_kwargs())
+            if a.test_from_pickle:
+                tds = load_dataset(a.test_from_pickle)
+                tds.train, tds.total_kfolds = False, None
+                test = PatientSequenceStore.from_windows(tds, device=self.device)
+                test.store.mu, test.store.std = train.store.mu, train.store.std          # the TRAIN set's factors (:285)
+                test.store.set_filters(**self._filter_kwargs())
+            elif a.kfolds is not None:
+                test = train.make_test_store_if_kfold()
+            else:
+                raise ValueError('a holdout run needs --test-from-pickle (or --kfolds)')
+        if not isinstance(train, PatientSequenceStore) or not isinstance(test, PatientSequenceStore):
+            raise TypeError('the nested networks take PatientSequenceStore datasets')
+        self.n_sub_batches = int(train.store.tiles.shape[1])
+        return train, test
+
+    def get_optimizer(self, model, world_size=1, rank=0, process_group=None):
+        kw = self._trainer_kwargs(world_size, rank, process_group)
+        kw['use_graph'] = bool(_flag(self.args, 'nested_graph'))
+        return HotPathTrainer(model, **kw, **self._loss_kwargs())
+
+    def _train_epoch_iterator(self):
+        from .nested import run_nested_train_epoch
+        return run_nested_train_epoch
+
+    def run_test_epoch(self, epoch_num, model, test_dataset, test_loader, fold_num, optimizer=None, _steps_only=False):
+        from .nested import run_nested_test_epoch
+        store = test_loader[0]
+        with self._test_trainer(optimizer, lambda: self.get_optimizer(model)) as trainer:
+            res = run_nested_test_epoch(trainer, store)
+        self.preds, self.pred_idx = res['window_pred'].tolist(), res['window_abs_index'].tolist()
+        self.results.update_meter('test_loss', fold_num, res['mean_loss'])
+        self.results.patient_results[(fold_num, epoch_num)] = res
+        return res
+
+    def perform_post_modeling_actions(self):
+        """:767-769 save the results object; here: per (fold, epoch) the patient-level accuracy over the patients served,
+        returned and kept as ``self.summary``."""
+        self.summary = {}
+        for key, res in self.results.patient_results.items():
+            self.summary[key] = dict(patients=res['patients'].tolist(), prediction=res['prediction'][res['patients']].tolist(),
+                                     mean_loss=res['mean_loss'])
+        return self.summary
+
+
+class CNNToNestedRNNModel(NestedMixin, BaseTraining):
+    """:772-778.  NOT in ``network_map`` (its key set is pinned, as for cnn_transformer): reached through
+    ``python -m deepards_amd.nested -n cnn_to_nested_rnn`` (``nested_network_map``) or built directly."""
+
+    def __init__(self, args):
+        self._init_nested(args)
+        super(CNNToNestedRNNModel, self).__init__(args)
+
+    def get_network(self, base_network):
+        return M.CNNToNestedRNNNetwork(base_network, self.args.n_sub_batches, True)
+
+
+class CNNToNestedLSTMModel(NestedMixin, BaseTraining):
+    """:781-789.  NOT in ``network_map`` (pinned key set): ``python -m deepards_amd.nested -n cnn_to_nested_lstm``."""
+    clip_odd_batches = True
+
+    def __init__(self, args):
+        self._init_nested(args)
+        super(CNNToNestedLSTMModel, self).__init__(args)
+
+    def get_network(self, base_network):
+        return M.CNNToNestedLSTMNetwork(base_network, self.args.n_sub_batches, True)
+
+
+nested_network_map = {'cnn_to_nested_rnn': CNNToNestedRNNModel, 'cnn_to_nested_lstm': CNNToNestedLSTMModel}
 
 
 network_map = {

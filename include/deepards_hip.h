@@ -540,6 +540,23 @@ size_t da_lstm_seq_proj_bwd_workspace(int N, int K, int F);
 int da_lstm_seq_proj_bwd(const float* dy, const float* hs, const float* W, float* dhs, float* dW, float* dbias, float* workspace,
                          int accumulate, int N, int K, int F, da_stream_t stream);
 
+/* ---- nested networks: whole-patient recurrences (csrc/seq_wide.hip; reference models/cnn_to_nested_layer.py:
+ * nn.RNN(128, 128) / nn.LSTM(128, 128), batch_first, zero initial state, over the W window vectors of one patient).
+ * kind 0: tanh RNN (G = H), kind 1: LSTM (G = 4H, gate order i,f,g,o).  gx [S][T][G] = x W_ih^T for all steps (a GEMM outside),
+ * w_hh [G][H], b_ih / b_hh [G].  One workgroup per sequence holds w_hh in registers for all T steps.  H == 128, T >= 1,
+ * S >= 0; anything else: -1, outputs untouched.  Forward: hs [S][T][H]; the LSTM also keeps cs [S][T][H] and its activated
+ * gates [S][T][H][4] (unit-major) for the backward.  Backward: dhs [S][T][H] -> the pre-activation gradient dz [S][T][G]
+ * (torch's row order); dW_ih, dW_hh, both bias gradients and dx are GEMMs / row sums of dz the caller runs afterwards.  No
+ * gradient into the initial state.  Every sum in an order fixed by H; a sequence's bits do not depend on S or its index. */
+int da_seqw_shape_ok(int kind, int H, int T);          /* 1 / 0, launches nothing */
+int da_seqw_rnn_fwd(const float* gx, const float* w_hh, const float* b_ih, const float* b_hh, float* hs, int S, int T, int H,
+                    da_stream_t stream);
+int da_seqw_rnn_bwd(const float* dhs, const float* w_hh, const float* hs, float* dz, int S, int T, int H, da_stream_t stream);
+int da_seqw_lstm_fwd(const float* gx, const float* w_hh, const float* b_ih, const float* b_hh, float* hs, float* cs, float* gates,
+                     int S, int T, int H, da_stream_t stream);
+int da_seqw_lstm_bwd(const float* dhs, const float* w_hh, const float* cs, const float* gates, float* dz, int S, int T, int H,
+                     da_stream_t stream);
+
 /* ---- cnn_transformer head: one Block of Transformer (reference models/transformer.py:13-88; CNNTransformerNetwork
  * models/cnn_transformer.py:8-44) in three fp32 launches.  x, y [B][T][D]; `params` = the block's sixteen parameter
  * pointers in named_parameters() order (q / k / v / joint_linear weight, bias; attention_norm; ff.0; ff.2; ff_norm), each
