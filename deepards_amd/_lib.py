@@ -15,6 +15,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepards_hip.h')
 SOURCES = ['conv_gemm.hip', 'conv_wino.hip', 'conv_bf16.hip', 'conv_x3p.hip', 'bn.hip', 'stem_pool.hip', 'head_optim.hip', 'transformer.hip',
            'filters.hip', 'se.hip', 'se_wide.hip', 'vgg.hip', 'gradcam.hip', 'protopnet.hip', 'lstm_seq.hip',
            'siamese.hip', 'conv_grouped.hip', 'autoencoder.hip', 'unet.hip', 'regress.hip', 'dtw.hip', 'seq_wide.hip']
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h'))      # every one is a rebuild dependency of every source
 
 _P, _I, _F, _Z, _U, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_double
 _IP = ctypes.POINTER(ctypes.c_int)
@@ -287,7 +288,7 @@ def header_symbols():
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 every csrc/*.hip into deepards_amd/libdeepards_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ('common.h', 'se_tail.h')]
+    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

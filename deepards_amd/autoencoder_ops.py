@@ -51,8 +51,7 @@ def _sel(sel, rows, lo, c, who, name='sel'):
 
 # ---- BatchNorm + MaxPool1d(2) with its decisions ---------------------------------------------------------------------------------
 def _pool_y(y, R, who):
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the autoencoder stages run with float activation storage only' % who)
+    _H._float_storage_only(who, 'the autoencoder stages run')
     _H._rlc(y, 'y')
     rows, l, c, w, wn = _H._bn_win(y, R)
     if c % 32 or l < 2 or l % 2 or rows < 1 or rows * l * c >= 1 << 32:
@@ -119,8 +118,7 @@ def bn_maxpool2_idx_bwd(dout, sel, y, R, mean, invstd, gamma, beta, out=None):
 
 # ---- MaxUnpool1d(2) --------------------------------------------------------------------------------------------------------------
 def _unpool_v(v, who, name, div=1):
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the autoencoder stages run with float activation storage only' % who)
+    _H._float_storage_only(who, 'the autoencoder stages run')
     rows, l, c = _H._rlc(v, name).shape
     if c % 32 or l < div or l % div or rows < 1 or rows * l * c * (2 // div) >= 1 << 32:
         raise ValueError('%s: %s %s needs C %% 32 == 0 and fewer than 2^32 elements' % (who, name, tuple(v.shape)))
@@ -149,8 +147,7 @@ def unpool2_bwd(dout, sel, out=None):
 
 # ---- the output stage ------------------------------------------------------------------------------------------------------------
 def _out_operands(v, bias3, sel1, w4, who):
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the autoencoder stages run with float activation storage only' % who)
+    _H._float_storage_only(who, 'the autoencoder stages run')
     rows, lo, c = _H._rlc(v, 'v').shape
     if c != OUT_C or rows < 1 or lo < 1 or rows * lo * c >= 1 << 31:
         raise ValueError('%s: v %s must be a (rows, L / 2, %d) map of fewer than 2^31 elements' % (who, tuple(v.shape), OUT_C))

@@ -14,7 +14,7 @@
 //
 // Every sum runs in an order fixed by the shape alone (thread-private chains, xor-shuffle trees, LDS folds in slot order, chunk
 // or block partials folded in index order): no atomics, the same bits every call.  Nothing is allocated or synchronised here.
-#include "common.h"
+#include "layer_shared.h"      // Bn4, loss_fold_kernel
 
 #define AE_CG 32                      // channels per block of the pool backward: 8 quads x 32 slots = 256 threads
 #define AE_SLOTS 32
@@ -22,31 +22,6 @@
 #define AE_OUT_POS 16                 // pooled positions per block pass of the output stage: 16 quads x 16 positions
 #define AE_OUT_BLOCKS 512             // most blocks (= partials) of an output-stage launch
 #define AE_OUT_REC 196                // floats per block record of the output backward: dw4 [64][3], db4, padding
-
-static inline int ae_grid(size_t threads) {
-  const size_t b = (threads + 255) / 256;
-  return (int)(b < 16384 ? b : 16384);
-}
-
-static inline bool ae_fits32(size_t rows, size_t l, size_t ld) { return rows * l * ld < 0x100000000ull; }
-
-// scale / shift, mean and invstd of 4 channels of window w
-struct AeBn4 {
-  f32x4 sc, sh, mu, is;
-  __device__ __forceinline__ void load(const float* __restrict__ mean, const float* __restrict__ invstd,
-                                       const float* __restrict__ gamma, const float* __restrict__ beta, size_t w, int C, int c0) {
-    mu = *reinterpret_cast<const f32x4*>(mean + w * C + c0);
-    is = *reinterpret_cast<const f32x4*>(invstd + w * C + c0);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0), be = *reinterpret_cast<const f32x4*>(beta + c0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a, b;
-      bn_scale_shift(mu[e], is[e], ga[e], be[e], a, b);
-      sc[e] = a;
-      sh[e] = b;
-    }
-  }
-};
 
 // ---- pool forward: thread = 4 channels of one pooled position; idx / 8 is the decision word, 4 (idx % 8) the nibble's shift --
 __global__ __launch_bounds__(256) void ae_pool_fwd_kernel(const float* __restrict__ y, int ldy, float* __restrict__ out,
@@ -59,7 +34,7 @@ __global__ __launch_bounds__(256) void ae_pool_fwd_kernel(const float* __restric
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int c0 = (int)(idx % nq) * 4;
     const size_t pr = idx / nq, row = pr / Lo, j = pr - row * Lo;
-    AeBn4 bn;
+    Bn4 bn;
     bn.load(mean, invstd, gamma, beta, row / R, C, c0);
     const float* p = y + (row * Lin + 2 * j) * (size_t)ldy + c0;
     const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + ldy);
@@ -306,21 +281,6 @@ __global__ __launch_bounds__(256) void ae_out_fwd_kernel(const float* __restrict
   }
 }
 
-// loss[0] = inv_n sum of the block partials: thread t takes partials t, t + 256, ... in order, then the 256 in order
-__global__ __launch_bounds__(256) void ae_loss_fold_kernel(const float* __restrict__ partials, int n, float inv_n,
-                                                           float* __restrict__ loss) {
-  __shared__ float red[256];
-  float t = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) t += partials[i];
-  red[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < 256; ++i) s += red[i];
-    loss[0] = s * inv_n;
-  }
-}
-
 // rec[block][c * 3 + t] = sum over the block's positions of (v + bias3)[c] dr[2j + sel - 1 + t];  rec[block][192] = sum dr
 __global__ __launch_bounds__(256) void ae_out_bwd_kernel(const float* __restrict__ drp, const float* __restrict__ v,
                                                          const float* __restrict__ bias3, const uint32_t* __restrict__ sel1,
@@ -399,7 +359,7 @@ extern "C" {
 
 static bool ae_pool_shape_ok(int rows, int R, int Lin, int C, int ldy) {
   return rows >= 0 && R >= 1 && rows % R == 0 && Lin >= 2 && Lin % 2 == 0 && C >= 32 && C % 32 == 0 && C / AE_CG <= 65535 && ldy >= C &&
-         ldy % 4 == 0 && ae_fits32((size_t)rows, (size_t)Lin, (size_t)ldy);
+         ldy % 4 == 0 && fits32((size_t)rows, (size_t)Lin, (size_t)ldy);
 }
 
 // Chunk geometry of da_bn_maxpool2_idx_bwd, without launching: the R (Lin / 2) pooled positions of a window are cut into
@@ -441,7 +401,7 @@ int da_bn_maxpool2_idx_fwd(const float* y, int ldy, float* out, uint32_t* sel, c
   if (rows == 0) return DA_OK;
   const int Lo = Lin / 2;
   const size_t npairs = (size_t)rows * Lo;
-  hipLaunchKernelGGL(ae_pool_fwd_kernel, dim3(ae_grid(npairs * (C / 4))), dim3(256), 0, stream, y, ldy, out, sel, sel_in, npairs, Lo,
+  hipLaunchKernelGGL(ae_pool_fwd_kernel, dim3(grid_stride_blocks(npairs * (C / 4))), dim3(256), 0, stream, y, ldy, out, sel, sel_in, npairs, Lo,
                      Lin, R, C, mean, invstd, gamma, beta);
   DA_CHECK_LAUNCH();
   return DA_OK;
@@ -473,7 +433,7 @@ int da_bn_maxpool2_idx_bwd(const float* dout, const uint32_t* sel, const float* 
 }
 
 static bool ae_unpool_shape_ok(int rows, int Lo, int C) {
-  return rows >= 0 && Lo >= 1 && C >= 32 && C % 32 == 0 && ae_fits32((size_t)rows, 2 * (size_t)Lo, (size_t)C);
+  return rows >= 0 && Lo >= 1 && C >= 32 && C % 32 == 0 && fits32((size_t)rows, 2 * (size_t)Lo, (size_t)C);
 }
 
 // v [rows][Lo][C] (+ bias[C], or NULL) -> out [rows][2 Lo][C]: every element written
@@ -483,7 +443,7 @@ int da_unpool2_fwd(const float* v, const float* bias, const uint32_t* sel, float
   if (!v || !sel || !out || !ae_unpool_shape_ok(rows, Lo, C)) return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const size_t npairs = (size_t)rows * Lo;
-  hipLaunchKernelGGL(ae_unpool_fwd_kernel, dim3(ae_grid(npairs * (C / 4))), dim3(256), 0, stream, v, bias, sel, out, npairs, C);
+  hipLaunchKernelGGL(ae_unpool_fwd_kernel, dim3(grid_stride_blocks(npairs * (C / 4))), dim3(256), 0, stream, v, bias, sel, out, npairs, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -495,7 +455,7 @@ int da_unpool2_bwd(const float* dout, const uint32_t* sel, float* dv, int rows, 
   if (!dout || !sel || !dv || !ae_unpool_shape_ok(rows, Lo, C)) return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const size_t npairs = (size_t)rows * Lo;
-  hipLaunchKernelGGL(ae_unpool_bwd_kernel, dim3(ae_grid(npairs * (C / 4))), dim3(256), 0, stream, dout, sel, dv, npairs, C);
+  hipLaunchKernelGGL(ae_unpool_bwd_kernel, dim3(grid_stride_blocks(npairs * (C / 4))), dim3(256), 0, stream, dout, sel, dv, npairs, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -530,7 +490,7 @@ int da_ae_out_fwd(const float* v, const float* bias3, const uint32_t* sel1, cons
   hipLaunchKernelGGL(ae_out_fwd_kernel, dim3(blocks), dim3(256), 0, stream, v, bias3, sel1, w4, bias4, x, recon, dr, partials, npos,
                      L / 2, 2.0f / n);
   DA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ae_loss_fold_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, 1.0f / n, loss);
+  hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, 1.0f / n, loss);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

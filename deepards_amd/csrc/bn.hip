@@ -1473,8 +1473,7 @@ int da_bn_relu_ss(const float* x, int ldx, float* out, int ldo, int W, int Wn, i
   if (W == 0) return DA_OK;
   const size_t npos = (size_t)W * Wn;
   if (npos >= 0xffffffffull) return DA_EINVAL;
-  size_t g = (npos * (C >> 2) + 255) / 256;
-  if (g > 16384) g = 16384;
+  const int g = grid_stride_blocks(npos * (C >> 2));
   hipLaunchKernelGGL(bn_relu_ss_kernel, dim3((unsigned)g), dim3(256), 0, stream, x, ldx, out, ldo, Wn, C, npos, mean, invstd,
                      ldstat, gamma, beta, make_fastdiv((uint32_t)Wn));
   DA_CHECK_LAUNCH();

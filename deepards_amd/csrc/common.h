@@ -194,6 +194,39 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Sum over a block of BT threads through the LDS array s[BT], a fixed halving tree: all BT threads call; result in every thread
+template <int BT>
+__device__ __forceinline__ float block_tree_sum(float v, float* s) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  s[tid] = v;
+  __syncthreads();
+  for (int o = BT / 2; o > 0; o >>= 1) {
+    if (tid < o) s[tid] += s[tid + o];
+    __syncthreads();
+  }
+  return s[0];
+}
+
+template <int Q>
+__device__ __forceinline__ float quad_bcast(float v) {                // lane Q of the caller's quad
+  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), Q * 0x55, 0xf, 0xf, true));
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }   // exp overflow: 1 / inf = 0
+
+__device__ __forceinline__ f32x4 ld4(const float* p) { return Act<float>::ld4(p); }
+__device__ __forceinline__ void st4(float* p, const f32x4& v) { Act<float>::st4(p, v); }
+
+// blocks of a grid-stride launch of 256-thread blocks over `threads` work items
+static inline int grid_stride_blocks(size_t threads) {
+  const size_t b = (threads + 255) / 256;
+  return (int)(b < 16384 ? b : 16384);
+}
+// a (rows, l, ld) map whose element offsets fit 32 bits
+static inline bool fits32(size_t rows, size_t l, size_t ld) { return rows * l * ld < 0x100000000ull; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // BatchNorm + ReLU as ONE fused multiply-add per element: h = max(fmaf(x, sc, sh), 0) with sc = gamma invstd,
 // sh = beta - mean sc.  The dense-block path (models/densenet.py:18-44,68-81) never stores relu(norm(x)): the convolutions
 // apply this while they stage their operand, the weight gradients do the same, and the BatchNorm backward recomputes the

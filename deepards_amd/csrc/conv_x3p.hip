@@ -605,8 +605,7 @@ int da_x3_split(const float* x, int ld, void* out, size_t npos, int C, hipStream
   DA_ENTER();
   if (!x || !out || C % 16 || ld < C || ld % 4) return DA_EINVAL;
   if (npos == 0) return DA_OK;
-  size_t g = (npos * (C >> 2) + 255) / 256;
-  if (g > 16384) g = 16384;
+  const int g = grid_stride_blocks(npos * (C >> 2));
   hipLaunchKernelGGL(x3_split_kernel, dim3((unsigned)g), dim3(256), 0, stream, x, ld, reinterpret_cast<__bf16*>(out), npos, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
@@ -616,8 +615,7 @@ int da_x3_merge(const void* x, float* out, int ld, size_t npos, int C, hipStream
   DA_ENTER();
   if (!x || !out || C % 16 || ld < C || ld % 4) return DA_EINVAL;
   if (npos == 0) return DA_OK;
-  size_t g = (npos * (C >> 2) + 255) / 256;
-  if (g > 16384) g = 16384;
+  const int g = grid_stride_blocks(npos * (C >> 2));
   hipLaunchKernelGGL(x3_merge_kernel, dim3((unsigned)g), dim3(256), 0, stream, reinterpret_cast<const __bf16*>(x), out, ld, npos, C);
   DA_CHECK_LAUNCH();
   return DA_OK;

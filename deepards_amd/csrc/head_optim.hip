@@ -821,8 +821,6 @@ __global__ __launch_bounds__(256) void window_median_bwd_kernel(const float* __r
 // gradients are 1x1-conv GEMMs (da_conv_gemm / da_conv_wgrad); these two kernels run the recurrence: one block per
 // window, one thread per gate unit (4H <= 1024), T steps inside the kernel.  Gate order i, f, g, o.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __global__ __launch_bounds__(1024) void lstm_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                         const float* __restrict__ bih, const float* __restrict__ bhh,
                                                         const float* __restrict__ h0, const float* __restrict__ c0,

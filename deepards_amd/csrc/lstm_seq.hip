@@ -34,16 +34,11 @@ struct SeqCfg {
   static constexpr int SPB = BT / TPS;                                // sequences per block: 2 at H = 8, else 1
 };
 
-template <int Q>
-__device__ __forceinline__ float quad_bcast(float v) {                // lane Q of the caller's quad
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), Q * 0x55, 0xf, 0xf, true));
-}
-
 // tanh(z) or sigmoid(z) from the library's expf / tanhf and a true division, as da_lstm_fwd takes them: the errors of 224
 // dependent steps are judged against stock float32 torch, so the fast v_exp_f32 / v_rcp_f32 forms (and tanh as
 // 2 sigmoid(2 z) - 1, which loses the small arguments) stay out.  exp overflow gives 1 / inf = 0, never a NaN.
 __device__ __forceinline__ float gate_act(float z, bool is_tanh) {
-  return is_tanh ? tanhf(z) : 1.0f / (1.0f + expf(-z));
+  return is_tanh ? tanhf(z) : sigmoidf_(z);
 }
 
 template <int H>

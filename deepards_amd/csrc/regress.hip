@@ -30,24 +30,6 @@ constexpr int RG_BT = 256;
 constexpr int RG_MAXM = 16;
 constexpr int RG_POOL = 7;
 
-__device__ __forceinline__ float rg_block_tree_sum(float v, float* s) {    // all RG_BT threads call; result in every thread
-  const int tid = threadIdx.x;
-  __syncthreads();
-  s[tid] = v;
-  __syncthreads();
-  for (int o = RG_BT / 2; o > 0; o >>= 1) {
-    if (tid < o) s[tid] += s[tid + o];
-    __syncthreads();
-  }
-  return s[0];
-}
-
-__device__ __forceinline__ float rg_wave_xor_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // x: row r's first element at x + r rstride; position p of the map form at + p ld
 template <bool VEC, bool MAP>
 __global__ __launch_bounds__(RG_BT) void regress_rows_fwd_kernel(const float* __restrict__ x, int ld, const float* __restrict__ W,
@@ -97,7 +79,7 @@ __global__ __launch_bounds__(RG_BT) void regress_rows_fwd_kernel(const float* __
 #pragma unroll
     for (int m = 0; m < RG_MAXM; ++m) {
       if (m < M) {                                                          // (M is uniform: every lane shuffles)
-        const float s = rg_wave_xor_sum(acc[m]);
+        const float s = wave_sum(acc[m]);
         if (lane == 0) out[(size_t)r * M + m] = bias[m] + s;
       }
     }
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(RG_BT) void regress_finish_fwd_kernel(const float* 
     const float e = out[i] - target[i];
     local = fmaf(e, e, local);
   }
-  const float s = rg_block_tree_sum(local, red);
+  const float s = block_tree_sum<RG_BT>(local, red);
   if (threadIdx.x == 0) loss[0] = s / (float)n;
 }
 
@@ -206,12 +188,11 @@ __global__ __launch_bounds__(RG_BT) void regress_finish_bwd_kernel(const float* 
   for (int m = 0; m < M; ++m) {
     float local = 0.f;
     for (int r = tid; r < R; r += RG_BT) local += 2.0f * (out[(size_t)r * M + m] - target[(size_t)r * M + m]) * gs;
-    const float s = rg_block_tree_sum(local, red);
+    const float s = block_tree_sum<RG_BT>(local, red);
     if (tid == 0) db[m] = accumulate ? db[m] + s : s;
   }
 }
 
-static inline bool rg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // form 0: flat features (R, F); form 1: the map (R, 7, F)
 static inline bool rg_shape_ok(int R, int F, int M, int form) {
@@ -237,7 +218,7 @@ int da_regress_fwd(const float* x, int ld, int form, const float* W, const float
   if (!rg_shape_ok(R, F, M, form) || ld < F || !x || !W || !bias || !target || !out || !loss || (form == 1 && !feat))
     return DA_EINVAL;
   const int G = (R + RG_ROWS - 1) / RG_ROWS;
-  const bool vec = F % 4 == 0 && ld % 4 == 0 && rg_aligned16(x) && rg_aligned16(W) && (form == 0 || rg_aligned16(feat));
+  const bool vec = F % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(W) && (form == 0 || aligned16(feat));
   if (form == 1) {
     if (vec)
       hipLaunchKernelGGL((regress_rows_fwd_kernel<true, true>), dim3(G), dim3(RG_BT), 0, stream, x, ld, W, bias, feat, out, R, F, M);
@@ -262,8 +243,8 @@ int da_regress_bwd(const float* feat, int ldf, const float* W, const float* out,
     return DA_EINVAL;
   const int G = (R + RG_ROWS - 1) / RG_ROWS;
   const float gs = gscale / (float)(R * M);
-  const bool vec = F % 4 == 0 && ldf % 4 == 0 && ldg % 4 == 0 && rg_aligned16(feat) && rg_aligned16(W) && rg_aligned16(dx) &&
-                   rg_aligned16(workspace);
+  const bool vec = F % 4 == 0 && ldf % 4 == 0 && ldg % 4 == 0 && aligned16(feat) && aligned16(W) && aligned16(dx) &&
+                   aligned16(workspace);
   const int per = vec ? 256 : 64, waves = (F + per - 1) / per;
   const int bt = 64 * (waves < 2 ? 2 : (waves > 4 ? 4 : waves));            // (>= RG_ROWS * RG_MAXM threads for the prologue)
   if (form == 1) {

@@ -15,7 +15,7 @@
 // Every sum runs in an order fixed by the shape alone (thread-private chains, LDS folds in slot order, partials folded in
 // chunk order): no atomics, the same bits every call.
 #include "common.h"
-#include "se_tail.h"      // SeBn4, the elementwise scale kernels and the partials' fold: shared with se_wide.hip
+#include "se_tail.h"      // Bn4, the elementwise scale kernels and the partials' fold: shared with se_wide.hip
 
 #define SE_TR 4                       // rows per workgroup of the gate kernels: W1 / W2 are read once for all of them (8 rows a
                                       // workgroup measured slower at every stage but the last: too few workgroups at B = 64)
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void se_bwd_reduce_kernel(const float* __restr
   const int row = blockIdx.x, nq = C >> 2, slots = 256 / nq;
   const int q = threadIdx.x % nq, slot = threadIdx.x / nq, c0 = q * 4;
   if (slot < slots) {
-    SeBn4 bn;
+    Bn4 bn;
     bn.load(mean, invstd, gamma, beta, (size_t)(row / R), C, c0);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int l = slot; l < L; l += slots) {
@@ -293,7 +293,7 @@ int da_se_scale_fwd(const float* y2, const float* res, float* out, void* mask, i
     return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const size_t npos = (size_t)rows * L;
-  hipLaunchKernelGGL(se_scale_fwd_kernel, dim3(se_grid(npos * (C / 8))), dim3(256), 0, stream, y2, res, out, (unsigned char*)mask,
+  hipLaunchKernelGGL(se_scale_fwd_kernel, dim3(grid_stride_blocks(npos * (C / 8))), dim3(256), 0, stream, y2, res, out, (unsigned char*)mask,
                      npos, L, R * L, C, mean, invstd, gamma, beta, s);
   DA_CHECK_LAUNCH();
   return DA_OK;
@@ -354,7 +354,7 @@ int da_se_bwd_scale(const float* g, const float* s, const float* dpool, float* d
   if (!g || !s || !dpool || !dz || !se_shape_ok(rows, L, C, 16)) return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const size_t npos = (size_t)rows * L;
-  hipLaunchKernelGGL(se_bwd_scale_kernel, dim3(se_grid(npos * (C / 4))), dim3(256), 0, stream, g, s, dpool, dz, npos, L, C);
+  hipLaunchKernelGGL(se_bwd_scale_kernel, dim3(grid_stride_blocks(npos * (C / 4))), dim3(256), 0, stream, g, s, dpool, dz, npos, L, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

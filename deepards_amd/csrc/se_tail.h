@@ -1,31 +1,8 @@
 // The pieces of the Squeeze-and-Excitation tail that do not depend on the gate's width, shared by se.hip (C <= 512, the
-// BasicBlock nets) and se_wide.hip (C <= 2048, the bottleneck nets): the recomputed BatchNorm affine of a channel quad, the
-// elementwise scale kernels (grid-stride, any C % 8 == 0) and the fold of the parameter-gradient partials.
+// BasicBlock nets) and se_wide.hip (C <= 2048, the bottleneck nets): the elementwise scale kernels
+// (grid-stride, any C % 8 == 0) and the fold of the parameter-gradient partials.
 #pragma once
-#include "common.h"
-
-// the scale / shift of 4 channels of window w
-struct SeBn4 {
-  f32x4 sc, sh;
-  __device__ __forceinline__ void load(const float* __restrict__ mean, const float* __restrict__ invstd,
-                                       const float* __restrict__ gamma, const float* __restrict__ beta, size_t w, int C, int c0) {
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + w * C + c0), is = *reinterpret_cast<const f32x4*>(invstd + w * C + c0);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0), be = *reinterpret_cast<const f32x4*>(beta + c0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a, b;
-      bn_scale_shift(mu[e], is[e], ga[e], be[e], a, b);
-      sc[e] = a;
-      sh[e] = b;
-    }
-  }
-  __device__ __forceinline__ f32x4 z(const f32x4& y) const {
-    f32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = fmaf(y[e], sc[e], sh[e]);
-    return r;
-  }
-};
+#include "layer_shared.h"      // Bn4: the recomputed BatchNorm affine of a channel quad
 
 // thread = 8 channels of one position: out and one byte of ReLU decisions (bit e = channel c0 + e; byte index = element / 8)
 static __global__ __launch_bounds__(256) void se_scale_fwd_kernel(const float* __restrict__ y2, const float* __restrict__ res,
@@ -42,7 +19,7 @@ static __global__ __launch_bounds__(256) void se_scale_fwd_kernel(const float* _
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int c0 = o8 * 8 + h * 4;
-      SeBn4 bn;
+      Bn4 bn;
       bn.load(mean, invstd, gamma, beta, w, C, c0);
       const f32x4 z = bn.z(*reinterpret_cast<const f32x4*>(y2 + pos * C + c0));
       const f32x4 sv = *reinterpret_cast<const f32x4*>(s + row * C + c0);
@@ -95,8 +72,3 @@ static __global__ __launch_bounds__(256) void se_bwd_scale_kernel(const float* _
   }
 }
 
-
-static inline unsigned se_grid(size_t total) {
-  size_t g = (total + 255) / 256;
-  return (unsigned)(g > 16384 ? 16384 : g);
-}

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void sew_pool_kernel(const float* __restrict__
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)rows * nq) return;
   const int row = (int)(idx / nq), c0 = (int)(idx - (size_t)row * nq) * 4;
-  SeBn4 bn;
+  Bn4 bn;
   bn.load(mean, invstd, gamma, beta, (size_t)(row / R), C, c0);
   const f32x4 rs = *reinterpret_cast<const f32x4*>(rowsum + (size_t)row * C + c0);
   const float fl = (float)L;
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void sew_bwd_reduce_kernel(const float* __rest
   __shared__ __attribute__((aligned(16))) float red[16 * 64];
   const int row = blockIdx.x, cb = blockIdx.y * 64;
   const int q = threadIdx.x & 15, slot = threadIdx.x >> 4, c0 = cb + q * 4;
-  SeBn4 bn;
+  Bn4 bn;
   bn.load(mean, invstd, gamma, beta, (size_t)(row / R), C, c0);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int l = slot; l < L; l += 16) {
@@ -441,7 +441,7 @@ int da_se_wide_scale_fwd(const float* y, const float* res, float* out, void* mas
     return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const size_t npos = (size_t)rows * L;
-  hipLaunchKernelGGL(se_scale_fwd_kernel, dim3(se_grid(npos * (C / 8))), dim3(256), 0, stream, y, res, out, (unsigned char*)mask,
+  hipLaunchKernelGGL(se_scale_fwd_kernel, dim3(grid_stride_blocks(npos * (C / 8))), dim3(256), 0, stream, y, res, out, (unsigned char*)mask,
                      npos, L, R * L, C, mean, invstd, gamma, beta, s);
   DA_CHECK_LAUNCH();
   return DA_OK;
@@ -511,7 +511,7 @@ int da_se_wide_bwd_scale(const float* g, const float* s, const float* dpool, flo
   if (!g || !s || !dpool || !dz || !sew_shape_ok(rows, L, C, 16)) return DA_EINVAL;
   if (rows == 0) return DA_OK;
   const size_t npos = (size_t)rows * L;
-  hipLaunchKernelGGL(se_bwd_scale_kernel, dim3(se_grid(npos * (C / 4))), dim3(256), 0, stream, g, s, dpool, dz, npos, L, C);
+  hipLaunchKernelGGL(se_bwd_scale_kernel, dim3(grid_stride_blocks(npos * (C / 4))), dim3(256), 0, stream, g, s, dpool, dz, npos, L, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -41,14 +41,9 @@
 #define SEQW_BT 512
 #define SEQW_PF 4                       // steps the changing operands are loaded ahead
 
-template <int Q>
-__device__ __forceinline__ float seqw_quad(float v) {                   // lane Q of the caller's quad
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), Q * 0x55, 0xf, 0xf, true));
-}
 __device__ __forceinline__ float seqw_quad_sum(float p) {               // the same bits in all four lanes
-  return (seqw_quad<0>(p) + seqw_quad<1>(p)) + (seqw_quad<2>(p) + seqw_quad<3>(p));
+  return (quad_bcast<0>(p) + quad_bcast<1>(p)) + (quad_bcast<2>(p) + quad_bcast<3>(p));
 }
-__device__ __forceinline__ float seqw_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }   // exp overflow: 1 / inf = 0
 
 // ---- tanh RNN ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SEQW_BT) void seqw_rnn_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
@@ -196,8 +191,8 @@ __global__ __launch_bounds__(SEQW_BT) void seqw_lstm_fwd_kernel(const float* __r
           z = fmaf(w[k + 2], v[2], z);
           z = fmaf(w[k + 3], v[3], z);
         }
-        const float a = g == 2 ? tanhf(z) : seqw_sigmoid(z);
-        const float ai = seqw_quad<0>(a), af = seqw_quad<1>(a), ag = seqw_quad<2>(a), ao = seqw_quad<3>(a);
+        const float a = g == 2 ? tanhf(z) : sigmoidf_(z);
+        const float ai = quad_bcast<0>(a), af = quad_bcast<1>(a), ag = quad_bcast<2>(a), ao = quad_bcast<3>(a);
         c = fmaf(af, c, ai * ag);
         const float h = ao * tanhf(c);
         gout[(size_t)t * 4 * H] = a;
@@ -248,7 +243,7 @@ __global__ __launch_bounds__(SEQW_BT) void seqw_lstm_bwd_kernel(const float* __r
         pd[u] = tn >= 0 ? dh_in[(size_t)tn * H] : 0.f;
         pa[u] = tn >= 0 ? g_in[(size_t)tn * 4 * H] : 0.f;
         pc[u] = tn >= 1 ? c_in[(size_t)(tn - 1) * H] : 0.f;
-        const float ai = seqw_quad<0>(a), af = seqw_quad<1>(a), ag = seqw_quad<2>(a), ao = seqw_quad<3>(a);
+        const float ai = quad_bcast<0>(a), af = quad_bcast<1>(a), ag = quad_bcast<2>(a), ao = quad_bcast<3>(a);
         const float tc = tanhf(ct);
         const float dc = fmaf(dh * ao, 1.f - tc * tc, dc_next);
         const float d = g == 0 ? dc * ag * ai * (1.f - ai)

@@ -26,24 +26,6 @@
 constexpr int SH_ROWS = 8;             // rows of one block of the two row kernels (da_siamese_head_rows_per_block)
 constexpr int SH_BT = 256;
 
-__device__ __forceinline__ float block_tree_sum(float v, float* s) {       // all SH_BT threads call; result in every thread
-  const int tid = threadIdx.x;
-  __syncthreads();
-  s[tid] = v;
-  __syncthreads();
-  for (int o = SH_BT / 2; o > 0; o >>= 1) {
-    if (tid < o) s[tid] += s[tid + o];
-    __syncthreads();
-  }
-  return s[0];
-}
-
-__device__ __forceinline__ float wave_xor_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // dz = (sigmoid(z) - t) gs of logit o of pair p: t = o for the positive pair ([0, 1]), 1 - o for the negative one ([1, 0])
 __device__ __forceinline__ float siamese_dz(float z, int p, int o, float gs) {
   const float t = (float)(p == 0 ? o : 1 - o);
@@ -88,10 +70,10 @@ __global__ __launch_bounds__(SH_BT) void siamese_rows_fwd_kernel(const float* __
         a11 = fmaf(w1, xn, a11);
       }
     }
-    a00 = wave_xor_sum(a00);
-    a01 = wave_xor_sum(a01);
-    a10 = wave_xor_sum(a10);
-    a11 = wave_xor_sum(a11);
+    a00 = wave_sum(a00);
+    a01 = wave_sum(a01);
+    a10 = wave_sum(a10);
+    a11 = wave_sum(a11);
     if (lane == 0) {
       const float c0 = b1[0], c1 = b1[1];
       u[(size_t)r * 2] = a00 + c0;
@@ -118,7 +100,7 @@ __global__ __launch_bounds__(SH_BT) void siamese_finish_fwd_kernel(const float* 
     const float t = (float)(p == 0 ? o : 1 - o);
     local += fmaxf(acc, 0.f) - acc * t + log1pf(expf(-fabsf(acc)));
   }
-  const float s = block_tree_sum(local, red);
+  const float s = block_tree_sum<SH_BT>(local, red);
   if (threadIdx.x == 0) loss[0] = s / (float)(2 * B);
 }
 
@@ -238,7 +220,7 @@ __global__ __launch_bounds__(SH_BT) void siamese_finish_bwd_kernel(const float* 
   for (int o = 0; o < 2; ++o) {
     float local = 0.f;
     for (int pb = tid; pb < 2 * B; pb += SH_BT) local += dzs[pb * 2 + o];
-    const float s = block_tree_sum(local, red);
+    const float s = block_tree_sum<SH_BT>(local, red);
     if (tid == 0) db2[o] = accumulate ? db2[o] + s : s;
   }
   for (int c = 0; c < 2; ++c) {
@@ -247,7 +229,7 @@ __global__ __launch_bounds__(SH_BT) void siamese_finish_bwd_kernel(const float* 
       const int p = i / R, r = i - p * R, b = r / NB, j = (r - b * NB) * 2 + c;
       local += fmaf(W2[j], dzs[(p * B + b) * 2], W2[J + j] * dzs[(p * B + b) * 2 + 1]);
     }
-    const float s = block_tree_sum(local, red);
+    const float s = block_tree_sum<SH_BT>(local, red);
     if (tid == 0) db1[c] = accumulate ? db1[c] + s : s;
   }
 }
@@ -282,7 +264,6 @@ __global__ void siamese_draw_kernel(const int64_t* __restrict__ anchor, const in
   }
 }
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static inline bool head_shape_ok(int B, int NB, int D, int ld) {
   return B >= 1 && NB >= 1 && D >= 1 && ld >= D && (long long)B * NB <= (1 << 24) && (long long)B * NB * 2 * D < (1ll << 40);

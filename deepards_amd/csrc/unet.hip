@@ -16,7 +16,7 @@
 //
 // Every sum runs in an order fixed by the shape alone (thread-private chains, xor-shuffle trees, LDS folds in slot order, block
 // partials folded in index order): no atomics, the same bits every call.  Nothing is allocated or synchronised here.
-#include "common.h"
+#include "layer_shared.h"      // loss_fold_kernel
 
 #define UN_OUT_C 64                   // channels in front of conv_last (Conv1d(64, 1, 1))
 #define UN_OUT_POS 16                 // positions per block pass of the output stage: 16 quads x 16 positions
@@ -25,8 +25,6 @@
 
 enum { UN_BIAS_RELU = 0, UN_POOL_FWD, UN_UP_FWD, UN_UP_BWD, UN_POOL_SKIP_BWD, UN_RELU_BWD, UN_OUT_FWD, UN_OUT_BWD, UN_OPS };
 
-__device__ __forceinline__ f32x4 un_ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void un_st(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ f32x4 un_relu_add(const f32x4& y, const f32x4& b) {
   f32x4 a;
 #pragma unroll
@@ -45,7 +43,7 @@ __global__ __launch_bounds__(256) void un_bias_relu_kernel(float* __restrict__ y
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int c0 = (int)(idx % nq) * 4;
     float* p = y + (idx / nq) * (size_t)ld + c0;
-    un_st(p, un_relu_add(un_ld(p), un_ld(bias + c0)));
+    st4(p, un_relu_add(ld4(p), ld4(bias + c0)));
   }
 }
 
@@ -58,14 +56,14 @@ __global__ __launch_bounds__(256) void un_pool_fwd_kernel(float* __restrict__ y,
     const int c0 = (int)(idx % nq) * 4;
     const size_t pr = idx / nq;
     float* p = y + 2 * pr * (size_t)ld + c0;
-    const f32x4 b = un_ld(bias + c0);
-    const f32x4 a0 = un_relu_add(un_ld(p), b), a1 = un_relu_add(un_ld(p + ld), b);
+    const f32x4 b = ld4(bias + c0);
+    const f32x4 a0 = un_relu_add(ld4(p), b), a1 = un_relu_add(ld4(p + ld), b);
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = a1[e] > a0[e] ? a1[e] : a0[e];
-    un_st(p, a0);
-    un_st(p + ld, a1);
-    un_st(pooled + pr * C + c0, o);
+    st4(p, a0);
+    st4(p + ld, a1);
+    st4(pooled + pr * C + c0, o);
   }
 }
 
@@ -80,10 +78,10 @@ __global__ __launch_bounds__(256) void un_up_fwd_kernel(const float* __restrict_
     const size_t pos = idx / nq;
     const int j = (int)(pos % L);
     const float* p = y + pos * C + c0;
-    const f32x4 b = un_ld(bias + c0), zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 x = un_relu_add(un_ld(p), b);
-    const f32x4 xm = j > 0 ? un_relu_add(un_ld(p - C), b) : zero;          // (weight j / D = 0 at j = 0: never read)
-    const f32x4 xp = j < L - 1 ? un_relu_add(un_ld(p + C), b) : zero;      // (weight (L - 1 - j) / D = 0 at j = L - 1)
+    const f32x4 b = ld4(bias + c0), zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 x = un_relu_add(ld4(p), b);
+    const f32x4 xm = j > 0 ? un_relu_add(ld4(p - C), b) : zero;          // (weight j / D = 0 at j = 0: never read)
+    const f32x4 xp = j < L - 1 ? un_relu_add(ld4(p + C), b) : zero;      // (weight (L - 1 - j) / D = 0 at j = L - 1)
     const float we = (float)(2 * L - 1 - j) / D, wm = (float)j / D;        // out[2j]
     const float wo = (float)(L + j) / D, wp = (float)(L - 1 - j) / D;      // out[2j + 1]
     f32x4 oe, oo;
@@ -93,8 +91,8 @@ __global__ __launch_bounds__(256) void un_up_fwd_kernel(const float* __restrict_
       oo[e] = fmaf(wp, xp[e], wo * x[e]);
     }
     float* o = out + 2 * pos * (size_t)ldo + c0;
-    un_st(o, oe);
-    un_st(o + ldo, oo);
+    st4(o, oe);
+    st4(o + ldo, oo);
   }
 }
 
@@ -111,10 +109,10 @@ __global__ __launch_bounds__(256) void un_up_bwd_kernel(const float* __restrict_
     const int j = (int)(pos % L);
     const float* q = d + 2 * pos * (size_t)ld + c0;                        // d[2j] of this row
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 d1 = un_ld(q + ld), d0 = un_ld(q);
-    const f32x4 dm = j > 0 ? un_ld(q - ld) : zero, dp = j < L - 1 ? un_ld(q + 2 * (size_t)ld) : zero;
+    const f32x4 d1 = ld4(q + ld), d0 = ld4(q);
+    const f32x4 dm = j > 0 ? ld4(q - ld) : zero, dp = j < L - 1 ? ld4(q + 2 * (size_t)ld) : zero;
     const float w1 = (float)(L + j) / D, w0 = (float)(2 * L - 1 - j) / D, wm = (float)(L - j) / D, wp = (float)(j + 1) / D;
-    const f32x4 yv = un_ld(y + pos * C + c0), b = un_ld(bias + c0);
+    const f32x4 yv = ld4(y + pos * C + c0), b = ld4(bias + c0);
     f32x4 g;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -123,7 +121,7 @@ __global__ __launch_bounds__(256) void un_up_bwd_kernel(const float* __restrict_
       if (j < L - 1) t = fmaf(wp, dp[e], t);
       g[e] = yv[e] + b[e] > 0.f ? t : 0.f;
     }
-    un_st(dy + pos * C + c0, g);
+    st4(dy + pos * C + c0, g);
   }
 }
 
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(256) void un_pool_skip_bwd_kernel(const float* __re
     const size_t pr = idx / nq;
     const float* pa = a + 2 * pr * (size_t)lda + c0;
     const float* ps = dskip + 2 * pr * (size_t)ld + c0;
-    const f32x4 a0 = un_ld(pa), a1 = un_ld(pa + lda), s0 = un_ld(ps), s1 = un_ld(ps + ld), dp = un_ld(dpooled + pr * C + c0);
+    const f32x4 a0 = ld4(pa), a1 = ld4(pa + lda), s0 = ld4(ps), s1 = ld4(ps + ld), dp = ld4(dpooled + pr * C + c0);
     f32x4 g0, g1;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -148,8 +146,8 @@ __global__ __launch_bounds__(256) void un_pool_skip_bwd_kernel(const float* __re
       g1[e] = a1[e] > 0.f ? t1 : 0.f;
     }
     float* o = dy + 2 * pr * C + c0;
-    un_st(o, g0);
-    un_st(o + C, g1);
+    st4(o, g0);
+    st4(o + C, g1);
   }
 }
 
@@ -161,11 +159,11 @@ __global__ __launch_bounds__(256) void un_relu_bwd_kernel(const float* dout, con
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int c0 = (int)(idx % nq) * 4;
     const size_t pos = idx / nq;
-    const f32x4 av = un_ld(a + pos * (size_t)lda + c0), d = un_ld(dout + pos * C + c0);
+    const f32x4 av = ld4(a + pos * (size_t)lda + c0), d = ld4(dout + pos * C + c0);
     f32x4 g;
 #pragma unroll
     for (int e = 0; e < 4; ++e) g[e] = av[e] > 0.f ? d[e] : 0.f;
-    un_st(dy + pos * C + c0, g);
+    st4(dy + pos * C + c0, g);
   }
 }
 
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(256) void un_out_fwd_kernel(const float* __restrict
                                                          float* __restrict__ partials, size_t npos, float scale) {
   __shared__ float red[UN_OUT_POS];
   const int quad = threadIdx.x & 15, ps = threadIdx.x >> 4;
-  const f32x4 wv = un_ld(w + quad * 4);
+  const f32x4 wv = ld4(w + quad * 4);
   const float b = bias[0];
   float sq = 0.f;
   for (size_t base = (size_t)blockIdx.x * UN_OUT_POS; base < npos; base += (size_t)gridDim.x * UN_OUT_POS) {
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(256) void un_out_fwd_kernel(const float* __restrict
     const bool valid = pos < npos;
     float r = 0.f;
     if (valid) {
-      const f32x4 av = un_ld(a + pos * UN_OUT_C + quad * 4);
+      const f32x4 av = ld4(a + pos * UN_OUT_C + quad * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) r = fmaf(av[e], wv[e], r);
     }
@@ -206,34 +204,19 @@ __global__ __launch_bounds__(256) void un_out_fwd_kernel(const float* __restrict
   }
 }
 
-// loss[0] = inv_n sum of the block partials: thread t takes partials t, t + 256, ... in order, then the 256 in order
-__global__ __launch_bounds__(256) void un_loss_fold_kernel(const float* __restrict__ partials, int n, float inv_n,
-                                                           float* __restrict__ loss) {
-  __shared__ float red[256];
-  float t = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) t += partials[i];
-  red[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < 256; ++i) s += red[i];
-    loss[0] = s * inv_n;
-  }
-}
-
 // dy = dr w [a > 0];  rec[block][c] = sum over the block's positions of dr a[c];  rec[block][64] = sum dr
 __global__ __launch_bounds__(256) void un_out_bwd_kernel(const float* __restrict__ drp, const float* __restrict__ a,
                                                          const float* __restrict__ w, float* __restrict__ dy, float* __restrict__ rec,
                                                          size_t npos) {
   __shared__ float red[UN_OUT_POS][UN_OUT_C + 1];
   const int quad = threadIdx.x & 15, ps = threadIdx.x >> 4;
-  const f32x4 wv = un_ld(w + quad * 4);
+  const f32x4 wv = ld4(w + quad * 4);
   float acc[4] = {0.f, 0.f, 0.f, 0.f}, sdr = 0.f;
   for (size_t base = (size_t)blockIdx.x * UN_OUT_POS; base < npos; base += (size_t)gridDim.x * UN_OUT_POS) {
     const size_t pos = base + ps;
     if (pos >= npos) continue;
     const float d = drp[pos];
-    const f32x4 av = un_ld(a + pos * UN_OUT_C + quad * 4);
+    const f32x4 av = ld4(a + pos * UN_OUT_C + quad * 4);
     f32x4 g;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -241,7 +224,7 @@ __global__ __launch_bounds__(256) void un_out_bwd_kernel(const float* __restrict
       acc[e] = fmaf(d, av[e], acc[e]);
     }
     sdr += d;
-    un_st(dy + pos * UN_OUT_C + quad * 4, g);
+    st4(dy + pos * UN_OUT_C + quad * 4, g);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) red[ps][quad * 4 + e] = acc[e];
@@ -271,15 +254,10 @@ __global__ __launch_bounds__(256) void un_out_bwd_merge_kernel(const float* __re
   }
 }
 
-static inline int un_grid(size_t threads) {
-  const size_t b = (threads + 255) / 256;
-  return (int)(b < 16384 ? b : 16384);
-}
-
 // a (rows, L, C) map at channel pitch ld: 32-bit element offsets, and L small enough for the upsample's integer weights
 static bool un_shape_ok(int rows, int L, int C, int ld) {
   return rows >= 0 && L >= 1 && L < (1 << 22) && C >= 32 && C % 32 == 0 && ld >= C && ld % 4 == 0 &&
-         (size_t)rows * (size_t)L * (size_t)ld < 0x100000000ull;
+         fits32((size_t)rows, (size_t)L, (size_t)ld);
 }
 
 static int un_out_blocks(int rows, int L) {
@@ -305,7 +283,7 @@ int da_unet_plan(int op, int rows, int L, int C, int ld, int* blocks, size_t* wo
     *workspace = (size_t)*blocks * (op == UN_OUT_FWD ? 1 : UN_OUT_REC) * sizeof(float);
     return DA_OK;
   }
-  *blocks = un_grid((size_t)rows * (pairs ? L / 2 : L) * (C / 4));
+  *blocks = grid_stride_blocks((size_t)rows * (pairs ? L / 2 : L) * (C / 4));
   return DA_OK;
 }
 
@@ -392,7 +370,7 @@ int da_unet_out_fwd(const float* a, const float* w, const float* bias, const flo
   hipLaunchKernelGGL(un_out_fwd_kernel, dim3(blocks), dim3(256), 0, stream, a, w, bias, x, recon, dr, partials, (size_t)rows * L,
                      2.0f / n);
   DA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(un_loss_fold_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, 1.0f / n, loss);
+  hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, 1.0f / n, loss);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -19,36 +19,11 @@
 //
 // Every sum runs in an order fixed by the shape alone (thread-private chains, LDS folds in slot order, partials in chunk order):
 // no atomics, the same bits every call.  Nothing is allocated or synchronised here.
-#include "common.h"
+#include "layer_shared.h"      // Bn4
 
 #define VP_CG 32                      // channels per block of the backward passes: 8 quads x 32 slots = 256 threads
 #define VP_SLOTS 32
 #define VP_CHUNK 256                  // pairs per block (8 per slot)
-
-static inline int vp_grid(size_t threads) {
-  const size_t b = (threads + 255) / 256;
-  return (int)(b < 16384 ? b : 16384);
-}
-
-static inline bool vp_fits32(size_t rows, size_t l, size_t ld) { return rows * l * ld < 0x100000000ull; }
-
-// scale / shift, mean and invstd of 4 channels of window w
-struct VpBn4 {
-  f32x4 sc, sh, mu, is;
-  __device__ __forceinline__ void load(const float* __restrict__ mean, const float* __restrict__ invstd,
-                                       const float* __restrict__ gamma, const float* __restrict__ beta, size_t w, int C, int c0) {
-    mu = *reinterpret_cast<const f32x4*>(mean + w * C + c0);
-    is = *reinterpret_cast<const f32x4*>(invstd + w * C + c0);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0), be = *reinterpret_cast<const f32x4*>(beta + c0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a, b;
-      bn_scale_shift(mu[e], is[e], ga[e], be[e], a, b);
-      sc[e] = a;
-      sh[e] = b;
-    }
-  }
-};
 
 // The gradient of the two members of a pool pair from the pair's gradient d: the pool hands it to the FIRST maximum of
 // (relu(z0), relu(z1)) (ATen's MaxPool1d: the second wins only when strictly greater), the ReLU passes it where z > 0.
@@ -69,7 +44,7 @@ __global__ __launch_bounds__(256) void vp_fwd_kernel(const float* __restrict__ y
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int c0 = (int)(idx % nq) * 4;
     const size_t pr = idx / nq, row = pr / Lo, j = pr - row * Lo;
-    VpBn4 bn;
+    Bn4 bn;
     bn.load(mean, invstd, gamma, beta, row / R, C, c0);
     const float* p = y + (row * Lin + 2 * j) * (size_t)ldy + c0;
     const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + ldy);
@@ -90,7 +65,7 @@ __global__ __launch_bounds__(256) void vp_bwd_partial_kernel(const float* __rest
   const int w = blockIdx.x, cg = blockIdx.y, pc = blockIdx.z, P = gridDim.z;
   const int q = threadIdx.x & 7, slot = threadIdx.x >> 3;
   const int c0 = cg * VP_CG + q * 4;
-  VpBn4 bn;
+  Bn4 bn;
   bn.load(mean, invstd, gamma, beta, (size_t)w, C, c0);
   const int npw = R * Lo, p_beg = pc * VP_CHUNK, p_end = min(npw, p_beg + VP_CHUNK);
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(256) void vp_bwd_apply_kernel(const float* __restri
   const int w = blockIdx.x, cg = blockIdx.y, pc = blockIdx.z, P = gridDim.z;
   const int q = threadIdx.x & 7, slot = threadIdx.x >> 3;
   const int c0 = cg * VP_CG + q * 4;
-  VpBn4 bn;
+  Bn4 bn;
   bn.load(mean, invstd, gamma, beta, (size_t)w, C, c0);
   const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0);
   f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f};
@@ -243,7 +218,7 @@ extern "C" {
 
 static bool vp_shape_ok(int rows, int R, int Lin, int C, int ldy) {
   return rows >= 0 && R >= 1 && rows % R == 0 && Lin >= 2 && C >= 32 && C % 32 == 0 && C / VP_CG <= 65535 && ldy >= C && ldy % 4 == 0 &&
-         vp_fits32((size_t)rows, (size_t)Lin, (size_t)ldy);
+         fits32((size_t)rows, (size_t)Lin, (size_t)ldy);
 }
 
 static int vp_chunks(int R, int Lin) { return (R * (Lin / 2) + VP_CHUNK - 1) / VP_CHUNK; }
@@ -257,7 +232,7 @@ int da_bn_relu_maxpool2_fwd(const float* y, int ldy, float* out, int rows, int R
   if (rows == 0) return DA_OK;
   const int Lo = Lin / 2;
   const size_t npairs = (size_t)rows * Lo;
-  hipLaunchKernelGGL(vp_fwd_kernel, dim3(vp_grid(npairs * (C / 4))), dim3(256), 0, stream, y, ldy, out, npairs, Lo, Lin, R, C, mean,
+  hipLaunchKernelGGL(vp_fwd_kernel, dim3(grid_stride_blocks(npairs * (C / 4))), dim3(256), 0, stream, y, ldy, out, npairs, Lo, Lin, R, C, mean,
                      invstd, gamma, beta);
   DA_CHECK_LAUNCH();
   return DA_OK;
@@ -296,7 +271,7 @@ int da_bn_mean_bias(const float* mean, const float* bias, float* mean_b, int W, 
   if (!mean || !bias || !mean_b || W < 0 || C < 1 || (size_t)W * C >= 0x7fffffffull) return DA_EINVAL;
   if (W == 0 && !dbias) return DA_OK;
   if (W == 0) return DA_EINVAL;
-  hipLaunchKernelGGL(vp_mean_bias_kernel, dim3(vp_grid((size_t)W * C)), dim3(256), 0, stream, mean, bias, mean_b, W, C, dbias);
+  hipLaunchKernelGGL(vp_mean_bias_kernel, dim3(grid_stride_blocks((size_t)W * C)), dim3(256), 0, stream, mean, bias, mean_b, W, C, dbias);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -305,11 +280,12 @@ int da_bn_mean_bias(const float* mean, const float* bias, float* mean_b, int W, 
 int da_adaptive_avgpool_flat_fwd(const float* x, float* feat, int rows, int Lin, int Lout, int C, hipStream_t stream) {
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;
-  if (!x || !feat || rows < 0 || Lin < 1 || Lout < 1 || C < 1 || !vp_fits32((size_t)rows, (size_t)Lin, (size_t)C) ||
-      !vp_fits32((size_t)rows, (size_t)Lout, (size_t)C))
+  if (!x || !feat || rows < 0 || Lin < 1 || Lout < 1 || C < 1 || !fits32((size_t)rows, (size_t)Lin, (size_t)C) ||
+      !fits32((size_t)rows, (size_t)Lout, (size_t)C))
     return DA_EINVAL;
   if (rows == 0) return DA_OK;
-  hipLaunchKernelGGL(ap_flat_fwd_kernel, dim3(vp_grid((size_t)rows * Lout * C)), dim3(256), 0, stream, x, feat, (size_t)rows, Lin, Lout, C);
+  hipLaunchKernelGGL(ap_flat_fwd_kernel, dim3(grid_stride_blocks((size_t)rows * Lout * C)), dim3(256), 0, stream,
+                     x, feat, (size_t)rows, Lin, Lout, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }
@@ -318,11 +294,12 @@ int da_adaptive_avgpool_flat_fwd(const float* x, float* feat, int rows, int Lin,
 int da_adaptive_avgpool_flat_bwd(const float* dfeat, float* dx, int rows, int Lin, int Lout, int C, hipStream_t stream) {
   DA_ENTER();
   if (g_act_bf16) return DA_EINVAL;
-  if (!dfeat || !dx || rows < 0 || Lin < 1 || Lout < 1 || C < 1 || !vp_fits32((size_t)rows, (size_t)Lin, (size_t)C) ||
-      !vp_fits32((size_t)rows, (size_t)Lout, (size_t)C))
+  if (!dfeat || !dx || rows < 0 || Lin < 1 || Lout < 1 || C < 1 || !fits32((size_t)rows, (size_t)Lin, (size_t)C) ||
+      !fits32((size_t)rows, (size_t)Lout, (size_t)C))
     return DA_EINVAL;
   if (rows == 0) return DA_OK;
-  hipLaunchKernelGGL(ap_flat_bwd_kernel, dim3(vp_grid((size_t)rows * Lin * C)), dim3(256), 0, stream, dfeat, dx, (size_t)rows, Lin, Lout, C);
+  hipLaunchKernelGGL(ap_flat_bwd_kernel, dim3(grid_stride_blocks((size_t)rows * Lin * C)), dim3(256), 0, stream,
+                     dfeat, dx, (size_t)rows, Lin, Lout, C);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

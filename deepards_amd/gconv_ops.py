@@ -43,8 +43,7 @@ def gconv3_plan(which, rows, l, c, stride):
 
 def _check(who, t, w, stride, name):
     """-> rows, l, c of the map ``t`` beside the grouped weight ``w`` (C, C / 32, 3)."""
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the grouped convolution runs with float activation storage only' % who)
+    _H._float_storage_only(who, 'the grouped convolution runs')
     rows, l, c = _H._rlc(t, name).shape
     if not gconv3_ok(c, GROUPS, stride):
         raise NotImplementedError('%s: no grouped k3 kernel for C = %d, stride %s (32 groups on 128 / 256 / 512 / 1024 '

@@ -53,6 +53,12 @@ def act_dtype():
     return 'bf16' if ACT == torch.bfloat16 else 'f32'
 
 
+def _float_storage_only(who, what=None):
+    """Refuse bf16 activation storage for the wrapper `who`; `what` names its family ('the SE tail runs')."""
+    if ACT != torch.float32:
+        raise NotImplementedError('%s: %sfloat activation storage only' % (who, what + ' with ' if what else ''))
+
+
 def _rlc(t, name='tensor'):
     if not (t.is_cuda and t.dtype == ACT and t.dim() == 3 and t.is_contiguous()):
         raise ValueError('%s must be a contiguous %s CUDA (rows, L, C) tensor, got %s %s %s' %

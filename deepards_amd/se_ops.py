@@ -26,8 +26,7 @@ def pool_out_len(lin, pool_mode):
 #     out = relu(z * s + res),  z = bn2(y2) (never stored),  s = sigmoid(fc2(relu(fc1(mean_L z))))
 # ------------------------------------------------------------------------------------------------
 def _se_y(y2, R, who):
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the SE tail runs with float activation storage only' % who)
+    _H._float_storage_only(who, 'the SE tail runs')
     _H._rlc(y2, 'y2')
     return _H._bn_win(y2, R)
 
@@ -140,8 +139,7 @@ def se_gate_bwd(dsum, s, hid, pool, w1, w2, grads=None, accumulate=False):
 
 def se_bwd_scale(g, s, dpool, out=None):
     """-> dz = fmaf(g, s, dpool / L): the gradient of z, which bn_bwd(mask_mode=0) of bn2 takes."""
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('se_bwd_scale: the SE tail runs with float activation storage only')
+    _H._float_storage_only('se_bwd_scale', 'the SE tail runs')
     rows, l, c = _H._rlc(g, 'g').shape
     _se_rc(s, rows, c, 's')
     _se_rc(dpool, rows, c, 'dpool')
@@ -197,8 +195,7 @@ def se_wide_stats(y3, R, eps=1e-5):
 def se_wide_gate_fwd(rowsum, R, L, mean, invstd, gamma, beta, w1, b1, w2, b2):
     """rowsum (rows, C) of a (rows, L, C) map -> pool = fmaf(rowsum / L, sc, sh), hid = relu(fc1(pool)), s = sigmoid(fc2(hid)):
     three launches (the elementwise pool, then hid and s as GEMMs on the fp32 matrix cores over tiles of 32 rows)."""
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('se_wide_gate_fwd: the SE tail runs with float activation storage only')
+    _H._float_storage_only('se_wide_gate_fwd', 'the SE tail runs')
     rows, c = _H._f32(rowsum, 'rowsum').shape
     if R < 1 or rows % R or L < 1:
         raise ValueError('se_wide_gate_fwd: rows must be a multiple of R, L >= 1')
@@ -277,8 +274,7 @@ def se_wide_gate_bwd(dsum, s, hid, pool, w1, w2, grads=None, accumulate=False):
 
 def se_wide_bwd_scale(g, s, dpool, out=None):
     """se_bwd_scale at the wide family's widths: -> dz = fmaf(g, s, dpool / L)."""
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('se_wide_bwd_scale: the SE tail runs with float activation storage only')
+    _H._float_storage_only('se_wide_bwd_scale', 'the SE tail runs')
     rows, l, c = _H._rlc(g, 'g').shape
     _se_rc(s, rows, c, 's')
     _se_rc(dpool, rows, c, 'dpool')

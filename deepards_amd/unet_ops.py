@@ -34,8 +34,7 @@ def unet_plan(op, rows, l, c, ld=None):
 
 
 def _f32_only(who):
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the UNet layers run with float activation storage only' % who)
+    _H._float_storage_only(who, 'the UNet layers run')
 
 
 def _slice(t, who, name, even=False):

@@ -9,8 +9,7 @@ from . import hip_ops as _H
 
 
 def _vp_y(y, R, who):
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('%s: the VGG stages run with float activation storage only' % who)
+    _H._float_storage_only(who, 'the VGG stages run')
     _H._rlc(y, 'y')
     rows, l, c, w, wn = _H._bn_win(y, R)
     if c % 32 or l < 2 or rows * l * c >= 1 << 32:
@@ -82,8 +81,7 @@ def bn_mean_bias(mean, bias, dbias=None):
 
 def adaptive_avgpool_flat_fwd(x, lout, out=None):
     """AdaptiveAvgPool1d(lout) + ``view(rows, -1)``: x (rows, L, C) -> (rows, C * lout) float, channel slowest."""
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('adaptive_avgpool_flat_fwd: float activation storage only')
+    _H._float_storage_only('adaptive_avgpool_flat_fwd')
     rows, lin, c = _H._rlc(x, 'x').shape
     if lout < 1 or lin < 1 or rows * max(lin, lout) * c >= 1 << 32:
         raise ValueError('adaptive_avgpool_flat_fwd: x %s -> %d positions is not served' % (tuple(x.shape), lout))
@@ -95,8 +93,7 @@ def adaptive_avgpool_flat_fwd(x, lout, out=None):
 
 def adaptive_avgpool_flat_bwd(dfeat, lin, lout, out=None):
     """dfeat (rows, C * lout) -> dx (rows, lin, C)."""
-    if _H.ACT != torch.float32:
-        raise NotImplementedError('adaptive_avgpool_flat_bwd: float activation storage only')
+    _H._float_storage_only('adaptive_avgpool_flat_bwd')
     _H._f32(dfeat, 'dfeat')
     if dfeat.dim() != 2 or lout < 1 or lin < 1 or dfeat.shape[1] % lout:
         raise ValueError('adaptive_avgpool_flat_bwd: dfeat must be (rows, C * %d), got %s' % (lout, tuple(dfeat.shape)))

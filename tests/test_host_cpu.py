@@ -26,6 +26,19 @@ def test_library_builds_loads_and_exports_header_symbols():
     assert lib.da_stem_wgrad_workspace(1280, 64) == 512 * 64 * 7 * 4
 
 
+def test_every_quoted_include_is_a_rebuild_dependency():
+    """_lib.build() rebuilds when a file of _lib.HEADERS is newer than the library: every `#include "..."` of csrc/ must name
+    one of them, or an edit to that header leaves a stale library behind."""
+    import re
+    from deepards_amd import _lib
+    assert _lib.HEADERS == sorted(_lib.HEADERS) and {'common.h', 'se_tail.h', 'layer_shared.h'} <= set(_lib.HEADERS)
+    files = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith(('.hip', '.h')))
+    assert set(_lib.SOURCES) | set(_lib.HEADERS) == set(files)
+    for f in files:
+        for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(os.path.join(_lib.CSRC, f)).read(), flags=re.M):
+            assert inc in _lib.HEADERS, '%s includes "%s"' % (f, inc)
+
+
 def test_abi_structs_agree_between_header_library_and_binding(tmp_path):
     """The descriptor structs exist three times: in the public header, in the library's sources and as ctypes mirrors.
     sizeof of each must agree: header compiled by gcc, da_abi_sizes() of the built library, ctypes.sizeof."""

@@ -33,7 +33,7 @@ SHAPES += [(7, 7, 3, 64), (33, 3, 3, 64), (40, 20, 5, 64), (66, 3, 3, 64), (66, 
 # Cr = 16 (tpo = 16) at C = 512 (8 strides of a part over the 128 channel quads) and at C = 256
 SHAPES += [(6, 3, 7, 64, 64), (5, 5, 7, 512, 256), (6, 3, 7, 512, 16), (4, 2, 14, 256, 16)]
 MULTI_CHUNK = (66, 3, 3, 64)
-GRID_CAP = 16384 * 256                # threads of a capped elementwise launch (se_grid, csrc/se.hip)
+GRID_CAP = 16384 * 256                # threads of a capped elementwise launch (grid_stride_blocks, csrc/common.h)
 
 
 def log(*a):
